@@ -1,6 +1,13 @@
 """bench.py -- gradient-steps/sec of the iS-DQN replay-sample -> Bellman-update step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5] [--precision bf16x3|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5] [--precision bf16x3|bf16] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.  --full adds what the
+headline figure does not need: the single-replay distribution (`replay_stats`), the oracle's CPU baseline
+(`cpu_baseline`, unless --no-cpu-baseline) and, for c3, the sum tree's status check behind the timed region.
+--dump-outputs DIR writes what the timed path computed in its last step (per-head losses, parameters, Adam moments and,
+for c3, the priorities written back) as DIR/<name>.npy: same arguments, same inputs, so two builds compare output for output.
 
 One "step" = one pass of the hot path over one batch: draw the batch from the device-resident replay
 (uniform PCG64 draw, or float64 sum-tree inverse-CDF query for c3), gather the element rows, run
@@ -238,6 +245,45 @@ def cpu_baseline(workload, seconds_budget=30.0, capacity=1_000_000, min_steps=50
                       f"(os.cpu_count() = {os.cpu_count()}, usable = {usable})"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, reps, prioritized, limit=DUMP_LIMIT_BYTES):
+    """Write what a caller of the timed path holds after its last step -- per-head losses, parameters, Adam moments (the
+    reference's learn_on_batch returns params, optimizer state and losses) and, for c3, the priorities written back -- as
+    `out_dir/<name>.npy` in float32 / float64.  Above `limit` bytes in all, every array of more than 2^20 elements keeps the
+    same fixed, seeded sample of its elements (sorted indices), so that runs with the same arguments stay comparable."""
+    import numpy as np
+
+    arrays = {}
+    for r, x in enumerate(reps):
+        pre = f"replica{r}_" if len(reps) > 1 else ""
+        e = x.eng
+        arrays[pre + "losses"] = e.losses
+        arrays[pre + "params"] = e.params
+        arrays[pre + "adam_m"] = e.adam_m
+        arrays[pre + "adam_v"] = e.adam_v
+        if prioritized:
+            arrays[pre + "priorities"] = e.priorities
+    host = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > limit:
+        big = [k for k, a in host.items() if a.size > (1 << 20)]
+        small = sum(a.nbytes for k, a in host.items() if k not in big)
+        frac = (limit - small) / sum(host[k].nbytes for k in big)
+        for k in big:
+            a = host[k].reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            host[k] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return sorted(host)
+
+
 def max_over_ranks(seconds, device):
     """MAX of a scalar over all ranks (identity when torch.distributed is not initialised)."""
     import torch
@@ -321,10 +367,14 @@ def main():
     ap.add_argument("--rebuild-mirror", action="store_true", help="rebuild the bf16 weight mirror at the head of every replay (the engine's "
                     "default for callers it knows nothing about) instead of declaring, as the trainer does, that all parameter writes are the engine's own")
     ap.add_argument("--min-replays", type=int, default=4, help="fewest graph replays the timed region is cut into")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the "
+                    "single-replay distribution (--replay-stats), the CPU baseline (--no-cpu-baseline skips it), c3's sum-tree status check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's losses, parameters, Adam moments "
+                    "(and c3's priorities) as DIR/<name>.npy, float32 / float64, 64 MB at most")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="wall-clock cap of EACH timed leg of the CPU baseline (50 steps each otherwise)")
     ap.add_argument("--cpu-capacity", type=int, default=1_000_000)
-    ap.add_argument("--replay-stats", type=int, default=200, help="graph replays timed one by one after the run (0 = skip)")
+    ap.add_argument("--replay-stats", type=int, default=200, help="with --full: graph replays timed one by one after the run (0 = skip)")
     ap.add_argument("--replicas-per-gpu", type=int, default=1, help="independent replicas sharing each GPU on their own streams, as the "
                     "reference shares one GPU between seeds (launch_job/atari/normal/train.sh:9-16); the headline number is 1")
     ap.add_argument("--cu-partition", action="store_true", help="with --replicas-per-gpu R: every replica's stream gets its own 1/R of the "
@@ -419,7 +469,11 @@ def main():
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    rep.rb._sampling_distribution._sum_tree.check_status() if w["prioritized"] else None
+    # (before anything else runs on the training state: the replay-stats pass below trains on)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, reps, w["prioritized"])
+    if args.full and w["prioritized"]:
+        rep.rb._sampling_distribution._sum_tree.check_status()
 
     elapsed_max = max_over_ranks(elapsed, device)
     per_rank_ms = [elapsed / args.steps * 1e3]
@@ -430,7 +484,7 @@ def main():
 
     # distribution over single replays (own pass, outside the timed region: every replay bracketed by its own events)
     stats = None
-    if rank == 0 and args.replay_stats > 0:
+    if rank == 0 and args.full and args.replay_stats > 0:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.replay_stats)]
         for a, b in evs:
             a.record()
@@ -488,7 +542,7 @@ def main():
         }
         if stats is not None:
             out["replay_stats"] = stats
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del rep  # (frees nothing the baseline needs; keeps host memory for the 7 GB oracle frame store)
             out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds, args.cpu_capacity)
         print(json.dumps(out), flush=True)

@@ -214,3 +214,33 @@ def test_priorities_ready_event_orders_a_second_stream():
     torch.cuda.synchronize()
     assert torch.equal(early, eng.priorities) and torch.equal(q_early, eng.q_values)
     assert bool((early >= 0).all()) and early.dtype == torch.float64
+
+
+@pytest.mark.parametrize("workload", ["c2", "c3"])
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path, workload):
+    """bench.py without --full: exactly --steps timed steps, the headline fields only (no replay statistics, no CPU baseline), and
+    --dump-outputs writes the last step's results -- bit for bit the same in two fresh processes with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4", "--settle", "0",
+                            "--workload", workload, "--capacity", "4096", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, f"{r.stdout}\n{r.stderr}"
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for d in lines:
+        assert d["steps"] == 8 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+        assert "replay_stats" not in d and "cpu_baseline" not in d
+    names = sorted(os.listdir(tmp_path / "a"))
+    expect = ["adam_m.npy", "adam_v.npy", "losses.npy", "params.npy"] + (["priorities.npy"] if workload == "c3" else [])
+    assert names == sorted(expect) and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), f"{n}: {(a != b).sum()} elements differ between two runs with the same arguments"
+    assert np.load(tmp_path / "a" / "losses.npy").shape == (9,)

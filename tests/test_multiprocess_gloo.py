@@ -101,3 +101,39 @@ def test_launcher_refuses_incomplete_arguments_before_starting_anything():
     assert launch.main(["--", "-en", "_test_launch_local"]) > 0                                   # no first seed
     assert launch.main(["--first_seed", "10", "--last_seed", "1", "--", "-en", "_test_launch_local"]) > 0  # empty seed range
     assert launch.main(["--first_seed", "1", "--last_seed", "3", "--n_seeds", "2", "--", "-en", "_test_launch_local"]) > 0
+
+
+def test_bench_dump_outputs_is_float_and_stays_under_its_limit(tmp_path):
+    """--dump-outputs: every array a caller holds after the last step, float32 / float64 as computed (integers widened); above
+    the size limit the large arrays keep the same seeded sample of their elements on every call."""
+    import types
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def replica(seed):
+        g = torch.Generator().manual_seed(seed)
+        eng = types.SimpleNamespace(losses=torch.rand(9, generator=g), params=torch.rand(3 << 20, generator=g),
+                                    adam_m=torch.rand(3 << 20, generator=g), adam_v=torch.rand(3 << 20, generator=g),
+                                    priorities=torch.rand(256, generator=g, dtype=torch.float64))
+        return types.SimpleNamespace(eng=eng)
+
+    names = bench.dump_outputs(str(tmp_path / "a"), [replica(0)], prioritized=True)
+    assert names == ["adam_m", "adam_v", "losses", "params", "priorities"]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert a["params"].dtype == np.float32 and a["priorities"].dtype == np.float64 and a["params"].size == 3 << 20
+    np.testing.assert_array_equal(a["losses"], replica(0).eng.losses.numpy())
+
+    limit = 16 << 20
+    names = bench.dump_outputs(str(tmp_path / "b"), [replica(0), replica(1)], prioritized=False, limit=limit)
+    assert names == sorted(f"replica{r}_{n}" for r in (0, 1) for n in ("adam_m", "adam_v", "losses", "params"))
+    sizes = sum(os.path.getsize(tmp_path / "b" / f"{n}.npy") for n in names)
+    assert sizes <= limit + len(names) * 256, sizes  # (npy headers)
+    bench.dump_outputs(str(tmp_path / "c"), [replica(0), replica(1)], prioritized=False, limit=limit)
+    for n in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{n}.npy"), np.load(tmp_path / "c" / f"{n}.npy"))
+    full = replica(1).eng.params.numpy()
+    assert np.isin(np.load(tmp_path / "b" / "replica1_params.npy"), full).all()
