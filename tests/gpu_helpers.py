@@ -71,13 +71,18 @@ def device_batch(eng, frames, ids, action, reward, terminal):
     return batch
 
 
-def masked_reference_grads(params, feats, K, A, ref, z_hip, layer_norm=True, gamma_n=0.99, huber_delta=0.0):
+def masked_reference_grads(params, feats, K, A, ref, z_hip, layer_norm=True, gamma_n=0.99, huber_delta=0.0, with_scales=False):
     """float64 torch gradients of the iS-DQN loss (isdqn.py:92-109) in which every ReLU of the ONLINE half takes its
     pass/block decision from the HIP path's own pre-activations `z_hip[layer]` ([B, ...] float32, layer names Conv_0..2,
     Dense_0).  Why: a batch holds 10^5..10^7 ReLU inputs, a few of them within the forward's 1e-5 of zero; where the HIP
     mask differs from an independent forward's, the whole upstream gradient of that image changes by O(1), i.e. the leaves
     by O(1/B) -- as much as a missing image would.  With the decisions pinned, what is left is arithmetic, and the
-    gradient comparison can be held to 1e-4 instead of 3e-3.  Returns a Flax-layout pytree of float64 arrays."""
+    gradient comparison can be held to 1e-4 instead of 3e-3.  Returns a Flax-layout pytree of float64 arrays.
+
+    ``with_scales``: also return, per element, the sum of the magnitudes of the terms that make up the gradient -- sum |dz| |x|
+    for a weight, sum |dz| for a bias, sum |dy| |xhat| / sum |dy| for a LayerNorm scale / bias (the same float64 graph with
+    absolute values): the scale against which a rounding error of the element is measured, however far below the leaf's
+    largest entry the element itself lies."""
     import torch.nn.functional as F
 
     B = len(ref.action)
@@ -88,12 +93,25 @@ def masked_reference_grads(params, feats, K, A, ref, z_hip, layer_norm=True, gam
         tot = max((out - 1) * s + k - size, 0)
         return tot // 2, tot - tot // 2
 
+    saved = []  # (module, its input (padded, NCHW for a convolution), pre-activation z, LayerNorm name, xhat, LayerNorm output)
+
+    def normalize(z):
+        mean = z.mean(-1, keepdim=True)
+        var = ((z * z).mean(-1, keepdim=True) - mean * mean).clamp_min(0)
+        return (z - mean) * torch.rsqrt(var + 1e-6)
+
     def ln(z, name):
         if not layer_norm:
             return z
-        mean = z.mean(-1, keepdim=True)
-        var = ((z * z).mean(-1, keepdim=True) - mean * mean).clamp_min(0)
-        return (z - mean) * torch.rsqrt(var + 1e-6) * P[name]["scale"] + P[name]["bias"]
+        return normalize(z) * P[name]["scale"] + P[name]["bias"]
+
+    def ln_saved(z, name):
+        if not layer_norm:
+            return z, None, None
+        xhat = normalize(z)
+        y = xhat * P[name]["scale"] + P[name]["bias"]
+        y.retain_grad()
+        return y, xhat, y
 
     def relu_with_hip_mask(y, z_name, ln_name):
         # online rows: decision from the HIP pre-activations; next-state rows (no gradient flows there): plain ReLU
@@ -108,17 +126,26 @@ def masked_reference_grads(params, feats, K, A, ref, z_hip, layer_norm=True, gam
         lo_h, hi_h = same(x.shape[1], k, s)
         lo_w, hi_w = same(x.shape[2], k, s)
         xp = F.pad(x.permute(0, 3, 1, 2), (lo_w, hi_w, lo_h, hi_h))
-        z = F.conv2d(xp, P[f"Conv_{i}"]["kernel"].permute(3, 2, 0, 1), P[f"Conv_{i}"]["bias"], stride=s).permute(0, 2, 3, 1)
-        x = relu_with_hip_mask(ln(z, f"LayerNorm_{n_ln}"), f"Conv_{i}", f"LayerNorm_{n_ln}")
+        zc = F.conv2d(xp, P[f"Conv_{i}"]["kernel"].permute(3, 2, 0, 1), P[f"Conv_{i}"]["bias"], stride=s)
+        zc.retain_grad()
+        y, xhat, yk = ln_saved(zc.permute(0, 2, 3, 1), f"LayerNorm_{n_ln}")
+        saved.append((f"Conv_{i}", xp.detach(), zc, f"LayerNorm_{n_ln}", xhat, yk, s))
+        x = relu_with_hip_mask(y, f"Conv_{i}", f"LayerNorm_{n_ln}")
         n_ln += 1
     h = x.reshape(2 * B, -1)
     n_dense = 0
     for width in feats[3:]:
         z = h @ P[f"Dense_{n_dense}"]["kernel"] + P[f"Dense_{n_dense}"]["bias"]
-        h = relu_with_hip_mask(ln(z, f"LayerNorm_{n_ln}"), f"Dense_{n_dense}", f"LayerNorm_{n_ln}")
+        z.retain_grad()
+        y, xhat, yk = ln_saved(z, f"LayerNorm_{n_ln}")
+        saved.append((f"Dense_{n_dense}", h.detach(), z, f"LayerNorm_{n_ln}", xhat, yk, None))
+        h = relu_with_hip_mask(y, f"Dense_{n_dense}", f"LayerNorm_{n_ln}")
         n_ln += 1
         n_dense += 1
-    q = (h @ P[f"Dense_{n_dense}"]["kernel"] + P[f"Dense_{n_dense}"]["bias"]).reshape(2 * B, 1 + K, A)
+    zq = h @ P[f"Dense_{n_dense}"]["kernel"] + P[f"Dense_{n_dense}"]["bias"]
+    zq.retain_grad()
+    saved.append((f"Dense_{n_dense}", h.detach(), zq, None, None, None, None))
+    q = zq.reshape(2 * B, 1 + K, A)
     act = torch.tensor(np.asarray(ref.action), dtype=torch.long)
     qv = q[:B, 1:, :][torch.arange(B), :, act]
     r = torch.tensor(np.asarray(ref.reward, np.float64))
@@ -131,4 +158,56 @@ def masked_reference_grads(params, feats, K, A, ref, z_hip, layer_norm=True, gam
         td = d**2
     loss = td.mean(0).sum()
     loss.backward()
-    return {m: {k: v.grad.numpy() for k, v in d.items()} for m, d in P.items()}
+    grads = {m: {k: v.grad.numpy() for k, v in d.items()} for m, d in P.items()}
+    if not with_scales:
+        return grads
+    scales = {}
+    for mod, xin, z, ln_name, xhat, y, stride in saved:
+        dz = z.grad.abs()
+        w = torch.zeros_like(P[mod]["kernel"], requires_grad=True)
+        if stride is not None:  # a convolution: the same correlation of |x| with |dz| gives sum |dz| |x| per tap
+            za = F.conv2d(xin.abs(), w.permute(3, 2, 0, 1), stride=stride)
+        else:
+            za = xin.abs() @ w
+        (gw,) = torch.autograd.grad((za * dz).sum(), [w])
+        scales[mod] = {"kernel": gw.numpy(), "bias": dz.sum(dim=(0, 2, 3) if stride is not None else 0).numpy()}
+        if xhat is not None:
+            dy = y.grad.abs()
+            red = tuple(range(dy.dim() - 1))
+            scales[ln_name] = {"scale": (dy * xhat.detach().abs()).sum(red).numpy(), "bias": dy.sum(red).numpy()}
+    return grads, scales
+
+
+def hip_preactivations(eng, B):
+    """The HIP path's own pre-activations of the online rows of the last forward, by layer (Conv_0..2, Dense_i; true
+    channels only), in the form masked_reference_grads takes them.  Internal layout: [B][pixels][channels padded to 8]."""
+    h = eng.observation_dim[0]
+    z_hip = {}
+    for i, (k, s) in enumerate(((8, 4), (4, 2), (3, 1))):
+        h = -(-h // s)
+        c = eng.features[i]
+        cp = (c + 7) // 8 * 8
+        z = eng.region(f"z/Conv_{i}").cpu().numpy()[: B * h * h * cp].reshape(B, -1, cp)
+        z_hip[f"Conv_{i}"] = z[:, :, :c].reshape(B, -1)
+    for j, c in enumerate(eng.features[3:]):
+        cp = (c + 7) // 8 * 8
+        z_hip[f"Dense_{j}"] = eng.region(f"z/Dense_{j}").cpu().numpy()[: B * cp].reshape(B, cp)[:, :c]
+    return z_hip
+
+
+# The engine's Adam hyper-parameters are float32 fields (include/isdqn_hip.h): 0.9 and 0.999 as float32 are the constants the
+# kernels multiply by and the bias corrections are computed from (net_kernels.hip: pow_int((double)b1, t)).  1 - b is exact in
+# float32 for both, so a float64 reference with the same two numbers differs from the kernels by rounding alone.
+ADAM_B1, ADAM_B2 = float(np.float32(0.9)), float(np.float32(0.999))
+
+
+def adam64(p0, m0, v0, g, t, lr, eps):
+    """optax.adam on float64 copies (oracle/isdqn.py learn_on_batch, the same expression order): returns new p, m, v, the update
+    u = m_hat / (sqrt(v_hat) + eps) and the denominator.  `t` is the step count after the increment."""
+    p0, m0, v0, g = (np.asarray(a, np.float64) for a in (p0, m0, v0, g))
+    c1, c2 = 1.0 - ADAM_B1 ** t, 1.0 - ADAM_B2 ** t
+    m = ADAM_B1 * m0 + (1 - ADAM_B1) * g
+    v = ADAM_B2 * v0 + (1 - ADAM_B2) * (g * g)
+    den = np.sqrt(v / c2) + eps
+    u = (m / c1) / den
+    return p0 - lr * u, m, v, u, den
