@@ -170,6 +170,23 @@ typedef struct isdqn_net_config {
                                            * learn / loss entry points (DQN) return ISDQN_ERR_UNSUPPORTED with it: the reference's
                                            * DQN cannot run with it either (dqn.py:86 applies the network without a mutable
                                            * batch_stats collection).                                                           */
+    int32_t n_bins;                       /* 0: scalar Q heads (the reference's network).  2..256: HL-Gauss histogram loss ("Stop
+                                           * Regressing", Farebrother et al. 2024; the flags of the reference's
+                                           * add_histogram_loss_parameters, parser_argument.py:199-228): the last Dense has
+                                           * n_heads * n_actions * n_bins outputs, logit ((h * A) + a) * n_bins + j is bin j of
+                                           * action a of head h over the support [hl_min, hl_max] cut into n_bins bins of width
+                                           * eta = (hl_max - hl_min) / n_bins with centres c_j = hl_min + (j + 1/2) eta.
+                                           * Q_h(s, a) = sum_j softmax(l_{h,a})_j c_j -- what forward / best_action(s) return and argmax.
+                                           * learn / loss / grad: target_k = r + (1 - terminal) gamma^n max_a' Q_{tg0+k}(s', a') on
+                                           * expectations; y = clamp(target_k, hl_min, hl_max); u_i = erf((hl_min + i eta - y) /
+                                           * (sqrt(2) hl_sigma)), p_j = (u_{j+1} - u_j) / (u_nb - u_0); loss = mean_b of
+                                           * logsumexp(l) - sum_j p_j l_j on the taken action's bins, dL/dl = (softmax(l) - p) / B.
+                                           * q_values / targets are the expectation and the unclamped scalar target; priorities stay
+                                           * sqrt(mean_k (q - target)^2 + 1e-10) on those expectations, NOT on the cross-entropy (which
+                                           * never falls below the target histogram's entropy, ~1.1 nats at sigma / eta = 0.75, and
+                                           * would flatten prioritized replay).  Not with huber_delta > 0 (ISDQN_ERR_ARG) nor with
+                                           * batch_norm (ISDQN_ERR_UNSUPPORTED).                                                    */
+    float hl_min, hl_max, hl_sigma;       /* n_bins > 0: support [hl_min, hl_max] (hl_max > hl_min) and sigma > 0; ignored at 0 */
 } isdqn_net_config;
 
 /* One parameter tensor inside the flat fp32 parameter buffer.  `name` is the Flax

@@ -14,6 +14,7 @@
 #include "conv_img.h"
 #include "conv_u8_pair.h"
 #include "conv_s8_pair.h"
+#include "hl_gauss.h"
 #include "net_plan.h"
 #include "net_problems.h"
 
@@ -1061,7 +1062,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab, float* _
     s8_store_quad(mirror, (int)o, pp.x, pp.y, pp.z, pp.w);  // S8 mirror of the updated parameters (read by the next step's MFMA stages)
 }
 
-// shift_params (isdqn.py:111-125): rows [0, nha-A) <- rows [A, nha) of the last Dense ([out][in] layout).
+// shift_params (isdqn.py:111-125): rows [0, nha-A) <- rows [A, nha) of the last Dense ([out][in] layout).  (Histogram heads: called
+// with the logit width and A * n_bins, so that whole histograms move.)
 __global__ __launch_bounds__(256) void shift_kernel(float* __restrict__ w, float* __restrict__ bias, int nha, int A,
                                                     int in_p) {
     int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1797,6 +1799,16 @@ extern "C" int isdqn_net_workspace_region(const isdqn_net_config* cfg, const cha
     return ISDQN_ERR_ARG;
 }
 
+// Histogram heads: Q rows ("q" region) <- expectations of the logit rows the forward left in the "logits" region (no-op otherwise).
+static int hl_expect(const Plan& P, float* ws, int n_rows, hipStream_t st) {
+    if (P.hl_nb == 0) return ISDQN_OK;
+    const int64_t waves = (int64_t)n_rows * P.nha;
+    hipLaunchKernelGGL(hl_expect_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, ws + P.logits_off, n_rows, P.nha, P.hl_nb,
+                       P.nlog_p, P.nha_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, ws + P.q_off);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
 static int check_input(const isdqn_net_config* cfg, const uint8_t* frames, int64_t frame_stride,
                        const int32_t* frame_ids, const float* obs) {
     if (cfg->arch != ISDQN_ARCH_FC) {
@@ -1824,7 +1836,9 @@ extern "C" int isdqn_net_forward(const isdqn_net_config* cfg, const float* param
     hipStream_t st = (hipStream_t)stream;
     rc = refresh_mirror(P, params, ws, st);
     if (rc) return rc;
-    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.q_off, st);
+    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.out_off, st);
+    if (rc) return rc;
+    rc = hl_expect(P, ws, n_rows, st);
     if (rc) return rc;
     // q_out is the unpadded (n_rows, nha) view
     ISDQN_HIP_CHECK(hipMemcpy2DAsync(q_out, (size_t)P.nha * 4, ws + P.q_off, (size_t)P.nha_p * 4, (size_t)P.nha * 4,
@@ -1912,7 +1926,8 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
     const Layer& head = P.L[P.n_layers - 1];
     int hc_S = 0, hc_wg = 0;
     static const bool hc_disabled = ISDQN_DEV_ENV("ISDQN_NO_HEAD_CHAIN");
-    if (learn && update && sel == nullptr && !hc_disabled && target_params == nullptr && P.n_layers >= 2 && hid.kind == 1 && !hid.is_head && hid.has_relu &&
+    // (histogram heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
+    if (learn && update && sel == nullptr && !hc_disabled && target_params == nullptr && P.hl_nb == 0 && P.n_layers >= 2 && hid.kind == 1 && !hid.is_head && hid.has_relu &&
         hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0) {
         // transitions per workgroup: the per-transition phases scale with S (the kernel is instruction-issue bound) while
         // every workgroup streams the whole head matrix from L2, so S follows the batch: about 256 workgroups
@@ -1935,12 +1950,12 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
         NetInput nx{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->next_state, nullptr, 0, 2 * stack, stack};
         rc = refresh_mirror(P, target_params, ws, st);
         if (rc) return rc;
-        rc = net_forward(P, x3, target_params, nx, B, 0, ws, ws + P.q_off + (int64_t)B * P.nha_p, st);
+        rc = net_forward(P, x3, target_params, nx, B, 0, ws, ws + P.out_off + (int64_t)B * P.nlog_p, st);
         if (rc) return rc;
         rc = refresh_mirror(P, params, ws, st);
         if (rc) return rc;
         NetInput on{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->state, nullptr, 0, 2 * stack, 0};
-        rc = net_forward(P, x3, params, on, B, B, ws, ws + P.q_off, st);
+        rc = net_forward(P, x3, params, on, B, B, ws, ws + P.out_off, st);
         if (rc) return rc;
     } else {
         // The optimizer writes the updated parameters in both forms, so a learn step leaves the mirror current; a caller
@@ -1951,7 +1966,7 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
             if (rc) return rc;
         }
         // ---- forward on concat(state, next_state) (isdqn.py:95) ----
-        rc = net_forward(P, x3, params, in, P.N2, B, ws, ws + P.q_off, st, hc_S ? P.n_layers - 1 : -1,
+        rc = net_forward(P, x3, params, in, P.N2, B, ws, ws + P.out_off, st, hc_S ? P.n_layers - 1 : -1,
                          hc_S ? P.n_layers - 2 : -1);
         if (rc) return rc;
     }
@@ -1959,7 +1974,8 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
     // ---- targets, loss, dL/dq ----
     float* qv = q_values ? q_values : ws + P.qv_off;
     float* tg = targets ? targets : ws + P.tg_off;
-    const int n_blk = hc_S ? hc_wg : ceil_div(B, TD_ROWS);
+    const int hl_R = P.hl_nb > 0 ? hl_rows_per_wg(K, P.hl_nb) : 0;
+    const int n_blk = hc_S ? hc_wg : hl_R ? ceil_div(B, hl_R) : ceil_div(B, TD_ROWS);
     float* loss_part = ws + P.lpart_off;
     float* dbh_part = loss_part + (int64_t)n_blk * K;
     float* adam_consts = ws + P.adam_tab_off;
@@ -2014,11 +2030,17 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
             ISDQN_HIP_CHECK(hipGetLastError());
         }
     } else {
-        hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K,
-                           on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, cfg->gamma_n, cfg->huber_delta,
-                           learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
+        if (hl_R)
+            hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.hl_nb * sizeof(float), st, ws + P.logits_off, B, hl_R,
+                               K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
+                               batch->action, batch->reward, batch->terminal, cfg->gamma_n, learn ? ws + P.dout_off : nullptr, qv, tg,
+                               priorities, loss_part, dbh_part);
+        else
+            hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K,
+                               on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, cfg->gamma_n, cfg->huber_delta,
+                               learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
         ISDQN_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nha_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nha_p,
+        hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nlog_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nlog_p,
                            losses, loss_accum, learn ? ws + P.dbh_off : nullptr, (learn && update) ? adam_count : nullptr,
                            cfg->adam_b1, cfg->adam_b2, adam_consts);
         ISDQN_HIP_CHECK(hipGetLastError());
@@ -2060,7 +2082,7 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
     const bool tail_swap = ss && P.n_layers >= 3 && !P.L[1].is_head;
     bool forked = false, layer0_chained = false;
     const float* dz_cur = ws + P.dout_off;  // gradient w.r.t. the current layer's pre-activation output
-    int dz_ld = P.nha_p;
+    int dz_ld = P.nlog_p;
     bool dz_fused = false;  // dz of layer i was already produced by the fused data gradient of layer i+1
     ReduceJobs red_jobs;    // partial-row reductions left by the fused data gradients (one launch before Adam)
     red_jobs.n = 0;
@@ -2072,7 +2094,7 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
         hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nha_p, 16)), dim3(256), 0, s2, loss_part, dbh_part, n_blk, B, K, P.nha_p, losses,
                            loss_accum, ws + P.dbh_off, (int*)nullptr, cfg->adam_b1, cfg->adam_b2, adam_consts);
         ISDQN_HIP_CHECK(hipGetLastError());
-        MatSrc A{ws + P.dout_off, P.nha_p, B, head.out_p, 1};
+        MatSrc A{ws + P.dout_off, P.nlog_p, B, head.out_p, 1};
         MatSrc Bm{ws + hid.act_off, head.in_p, B, head.in_p, 1};
         return plain_big<true, true, true, false, 2>(x3, A, nullptr, 0, Bm, ws + head.gw_off, head.in_p, head.out_p, head.in_p, B,
                                                      head.gw_slabs, head.w_size, s2);  // dL/dq fp32, hidden activations S8
@@ -2462,7 +2484,7 @@ extern "C" int isdqn_net_shift_params(const isdqn_net_config* cfg, float* params
     ISDQN_REQUIRE(params != nullptr, ISDQN_ERR_ARG, "null pointer");
     const Layer& l = P.L[P.n_layers - 1];
     hipLaunchKernelGGL(shift_kernel, dim3(ceil_div(l.in_p + 1, 256)), dim3(256), 0, (hipStream_t)stream,
-                       params + l.w_off, params + l.b_off, P.nha, P.n_actions, l.in_p);
+                       params + l.w_off, params + l.b_off, P.nlog, P.n_actions * (P.hl_nb > 0 ? P.hl_nb : 1), l.in_p);
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }
@@ -2483,7 +2505,9 @@ extern "C" int isdqn_net_best_action(const isdqn_net_config* cfg, const float* p
     hipStream_t st = (hipStream_t)stream;
     rc = refresh_mirror(P, params, ws, st);
     if (rc) return rc;
-    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, 1, 0, ws, ws + P.q_off, st);
+    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, 1, 0, ws, ws + P.out_off, st);
+    if (rc) return rc;
+    rc = hl_expect(P, ws, 1, st);
     if (rc) return rc;
     hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(64), 0, st, ws + P.q_off, P.n_actions, P.oh + idx_network, out_action);
     ISDQN_HIP_CHECK(hipGetLastError());
@@ -2511,7 +2535,9 @@ extern "C" int isdqn_net_best_actions(const isdqn_net_config* cfg, const float* 
         rc = refresh_mirror(P, params, ws, st);
         if (rc) return rc;
     }
-    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.q_off, st);
+    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.out_off, st);
+    if (rc) return rc;
+    rc = hl_expect(P, ws, n_rows, st);
     if (rc) return rc;
     hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, st, ws + P.q_off, n_rows, P.nha_p, P.n_actions,
                        P.oh, P.K, idx_networks, out_actions);

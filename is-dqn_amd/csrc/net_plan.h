@@ -88,13 +88,16 @@ struct Plan {
     BnSite bns[MAX_LAYERS + 1 + 2 * IMP_STACKS];
     int64_t x0_off;  // BatchNorm, cnn: the network input frames / 255 as S8 [N2][h * w][8]; fc: concat(state, next_state) fp32 [N2][obs]
     int n_heads, n_actions, nha, nha_p;
+    // head layer width: nha Q-values, or nha * hl_nb logits with the HL-Gauss histogram loss (cfg->n_bins > 0)
+    int nlog, nlog_p, hl_nb;
+    float hl_min, hl_max, hl_sigma;
     // K regressed heads; head k + oh (online rows) is regressed on head k (next-state rows).  iS-DQN: n_heads = 1 + K,
     // oh = 1 (isdqn.py:96-98).  A single head (n_heads = 1) is TF-DQN: K = 1, oh = 0 -- the head is regressed on its own
     // stop-gradient target (tfdqn.py:68-80).
     int K, oh;
     int64_t n_params;
     // workspace (float offsets unless noted)
-    int64_t q_off, dout_off, da_off, slab_off, qv_off, tg_off, dbh_off, adam_tab_off, lpart_off;
+    int64_t q_off, logits_off, out_off, dout_off, da_off, slab_off, qv_off, tg_off, dbh_off, adam_tab_off, lpart_off;
     int64_t wsplit_off;  // S8 mirror of the parameter buffer (same offsets as the fp32 master; weights only are read from it)
     int64_t slab_floats, da_floats;
     int64_t ws_bytes;
@@ -120,6 +123,13 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
                   "bad precision");
     ISDQN_REQUIRE(cfg->huber_delta >= 0.f, ISDQN_ERR_ARG, "huber_delta must be >= 0 (0 = squared error)");
     ISDQN_REQUIRE(cfg->batch_norm == 0 || cfg->batch_norm == 1, ISDQN_ERR_ARG, "batch_norm must be 0 or 1");
+    ISDQN_REQUIRE(cfg->n_bins == 0 || (cfg->n_bins >= 2 && cfg->n_bins <= 256), ISDQN_ERR_ARG, "n_bins must be 0 (off) or in [2, 256]");
+    if (cfg->n_bins > 0) {
+        ISDQN_REQUIRE(cfg->hl_max > cfg->hl_min, ISDQN_ERR_ARG, "histogram loss: hl_max must be > hl_min");
+        ISDQN_REQUIRE(cfg->hl_sigma > 0.f, ISDQN_ERR_ARG, "histogram loss: hl_sigma must be > 0");
+        ISDQN_REQUIRE(cfg->huber_delta == 0.f, ISDQN_ERR_ARG, "huber_delta and the histogram loss (n_bins > 0) exclude each other");
+        ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "the histogram loss is not built for BatchNorm networks");
+    }
     P.regions.clear();
     P.B = cfg->batch_size;
     P.N2 = 2 * P.B;
@@ -133,6 +143,13 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.n_actions = cfg->n_actions;
     P.nha = cfg->n_heads * cfg->n_actions;
     P.nha_p = round_up(P.nha, 8);
+    P.hl_nb = cfg->n_bins;
+    P.hl_min = cfg->hl_min; P.hl_max = cfg->hl_max; P.hl_sigma = cfg->hl_sigma;
+    P.nlog = P.hl_nb > 0 ? P.nha * P.hl_nb : P.nha;
+    P.nlog_p = round_up(P.nlog, 8);
+    ISDQN_REQUIRE(P.hl_nb == 0 || P.K <= 64, ISDQN_ERR_UNSUPPORTED, "the histogram loss is built for at most 64 regressed heads");
+    // (dense_post_kernel stages a whole head row, bias and LayerNorm rows in 64 KB of LDS: 3 * 5456 floats)
+    ISDQN_REQUIRE(P.hl_nb == 0 || P.nlog <= 5456, ISDQN_ERR_UNSUPPORTED, "histogram heads: n_heads * n_actions * n_bins must be <= 5456");
     int nl = 0;
     int n_conv = 0, n_dense = 0, n_ln = 0;
     int64_t poff = 0;
@@ -310,7 +327,7 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         l.has_relu = l.is_head ? 0 : 1;
         l.in_f = in_f; l.in_p = in_p;
         l.in_unpadded_ld = (cfg->arch == ISDQN_ARCH_FC && i == 0) ? in_f : 0;
-        l.out_f = l.is_head ? P.nha : cfg->features[i];
+        l.out_f = l.is_head ? P.nlog : cfg->features[i];
         ISDQN_REQUIRE(l.out_f >= 1 && l.out_f <= 8192, ISDQN_ERR_ARG, "bad dense width");
         l.out_p = round_up(l.out_f, 8);
         l.K = l.in_p;
@@ -501,14 +518,18 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     if (P.bn && cfg->arch == ISDQN_ARCH_FC)  // concat(state, next_state) as one matrix (the first layer's weight gradient contracts over all 2B rows)
         P.x0_off = region("bn/x0", (int64_t)P.N2 * P.L[0].in_f);
     P.q_off = region("q", (int64_t)P.N2 * P.nha_p);
-    P.dout_off = region("dout", (int64_t)P.Bb * P.nha_p);
+    // the head layer's output rows [2B][nlog_p]: the Q-values themselves, or the histogram logits (the "q" rows then hold their
+    // expectations, written by hl_expect_kernel for forward / best_action(s))
+    P.logits_off = P.hl_nb > 0 ? region("logits", (int64_t)P.N2 * P.nlog_p) : -1;
+    P.out_off = P.hl_nb > 0 ? P.logits_off : P.q_off;
+    P.dout_off = region("dout", (int64_t)P.Bb * P.nlog_p);
     P.da_off = region("da", P.da_floats);
     P.slab_off = region("slab", P.slab_floats);
     P.qv_off = region("q_values", (int64_t)P.B * P.K);
     P.tg_off = region("targets", (int64_t)P.B * P.K);
-    P.dbh_off = region("dbh", P.nha_p);
+    P.dbh_off = region("dbh", P.nlog_p);
     P.adam_tab_off = region("adam_consts", 64);
-    P.lpart_off = region("loss_partials", (int64_t)P.B * (P.K + P.nha_p));
+    P.lpart_off = region("loss_partials", (int64_t)P.B * (P.K + P.nlog_p));
     P.wsplit_off = region("wsplit", P.n_params);
     P.ws_bytes = off * 4;
     return ISDQN_OK;

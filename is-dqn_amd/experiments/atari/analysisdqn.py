@@ -17,6 +17,7 @@ import numpy as np
 from experiments.base.dqn import train
 from experiments.atari.common import make_environment, make_replay, seeds
 from experiments.base.utils import prepare_logs
+from experiments.base.parser_argument import histogram_loss_kwargs
 from slimdqn.networks.analysisdqn import AnalysisDQN
 
 
@@ -45,6 +46,7 @@ def run(argvs=sys.argv[1:], root=None):
         adam_eps=1.5e-4,
         batch_size=p["batch_size"],
         precision=p["precision"],
+        **histogram_loss_kwargs(p),
         huber_delta=p["huber_delta"],
     )
     if p["prioritized"]:

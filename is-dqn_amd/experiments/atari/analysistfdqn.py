@@ -16,6 +16,7 @@ import numpy as np
 from experiments.base.dqn import train
 from experiments.atari.common import make_environment, make_replay, seeds
 from experiments.base.utils import prepare_logs
+from experiments.base.parser_argument import histogram_loss_kwargs
 from slimdqn.networks.analysistfdqn import AnalysisTFDQN
 
 
@@ -43,6 +44,7 @@ def run(argvs=sys.argv[1:], root=None):
         adam_eps=1.5e-4,
         batch_size=p["batch_size"],
         precision=p["precision"],
+        **histogram_loss_kwargs(p),
     )
     try:
         out = train(np.random.default_rng(train_seed), p, agent, env, rb)

@@ -41,6 +41,12 @@ _ENGINE = [
     ("-prec", "--precision", dict(type=str, default="bf16x3", choices=["bf16x3", "bf16"], help="MFMA precision of the HIP engine.")),
     ("-per", "--prioritized", dict(action="store_true", default=False, help="Prioritized replay (sum-tree on the GPU) with TD-error writeback.")),
     ("-hd", "--huber_delta", dict(type=float, default=0.0, help="0: squared TD error (the reference's loss); > 0: Huber loss with this delta.")),
+    ("-hl", "--histogram_loss", dict(action="store_true", default=False, help="HL-Gauss histogram loss on the heads (the four flags below; off: scalar heads).")),
+    # add_histogram_loss_parameters (reference parser_argument.py:199-228): names, types and defaults of the reference
+    ("-nb", "--n_bins", dict(type=int, default=50, help="Number of bins composing the histogram.")),
+    ("-minn", "--min_value", dict(type=float, default=-100, help="Value of the lowest learnable value of the target.")),
+    ("-maxn", "--max_value", dict(type=float, default=100, help="Value of the highest learnable value of the target.")),
+    ("-sigma", "--sigma", dict(type=float, default=3, help="Standard deviation of each target sample. If sigma / eta = 0.75, then sigma = 0.75 * (max_value - min_value) / n_bins")),
     ("-nenvs", "--n_envs", dict(type=int, default=1, help="Host environments stepped in lockstep with one batched best_actions forward (1 = the reference's loop).")),
     ("-nworkers", "--n_env_workers", dict(type=int, default=0, help="Host worker processes stepping the -nenvs environments in parallel (0 = in this process).")),
     ("-env", "--env_backend", dict(type=str, default="ale", choices=["ale", "synthetic"], help="'synthetic' replaces ALE by random frames (no ROMs needed).")),
@@ -79,3 +85,8 @@ def add_analysistfdqn_arguments(parser: argparse.ArgumentParser) -> List[str]:
 
 def add_engine_arguments(parser: argparse.ArgumentParser) -> List[str]:
     return _add(parser, _ENGINE)
+
+
+def histogram_loss_kwargs(p) -> dict:
+    """The agents' histogram-loss keywords from parsed parameters: n_bins = 0 (scalar heads) unless -hl is given."""
+    return dict(n_bins=p["n_bins"] if p["histogram_loss"] else 0, min_value=p["min_value"], max_value=p["max_value"], sigma=p["sigma"])

@@ -16,6 +16,7 @@ import numpy as np
 
 from experiments.base.dqn import train
 from experiments.base.utils import prepare_logs
+from experiments.base.parser_argument import histogram_loss_kwargs
 from experiments.lunar_lander.common import make_environment, make_replay, seeds
 from slimdqn.networks.dqn import DQN
 
@@ -42,6 +43,7 @@ def run(argvs=sys.argv[1:], root=None):
         target_update_frequency=p["target_update_frequency"],
         batch_size=p["batch_size"],
         precision=p["precision"],
+        **histogram_loss_kwargs(p),
     )
     out = train(np.random.default_rng(train_seed), p, agent, env, rb)
     replicas.finalize()

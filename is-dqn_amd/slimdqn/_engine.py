@@ -38,6 +38,10 @@ class QNetEngine:
         device: str | None = None,
         huber_delta: float = 0.0,
         batch_norm: bool = False,
+        n_bins: int = 0,
+        min_value: float = -100.0,
+        max_value: float = 100.0,
+        sigma: float = 3.0,
     ):
         _hip.require_gpu()
         self.lib = _hip.lib()
@@ -74,6 +78,10 @@ class QNetEngine:
         cfg.huber_delta = float(huber_delta)  # 0: the reference's squared TD error
         cfg.batch_norm = 1 if batch_norm else 0  # architectures/dqn.py:52-53, 59-60, 66-67, 73-74, 100-101 (csrc/batchnorm.h)
         self.batch_norm = bool(batch_norm)
+        # n_bins > 0: HL-Gauss histogram heads (n_heads * n_actions * n_bins logits, region "logits"); forward still returns Q-values
+        cfg.n_bins = int(n_bins)
+        cfg.hl_min, cfg.hl_max, cfg.hl_sigma = (float(min_value), float(max_value), float(sigma)) if n_bins else (0.0, 0.0, 0.0)
+        self.n_bins = int(n_bins)
         self.cfg = cfg
         self.features = feats
         self.architecture_type = architecture_type

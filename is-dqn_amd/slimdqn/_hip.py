@@ -44,6 +44,10 @@ class NetConfig(ctypes.Structure):
         ("adam_eps", c_float),
         ("huber_delta", c_float),
         ("batch_norm", c_int32),
+        ("n_bins", c_int32),  # 0: scalar heads; > 0: HL-Gauss histogram loss over [hl_min, hl_max] (include/isdqn_hip.h)
+        ("hl_min", c_float),
+        ("hl_max", c_float),
+        ("hl_sigma", c_float),
     ]
 
 

@@ -61,7 +61,8 @@ class EngineAgent:
     """Common state: ``n_heads`` network heads of ``n_actions`` outputs each on the HIP engine."""
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
-                           learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False):
+                           learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
+                           n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0):
         self.n_actions = n_actions
         self.batch_norm = bool(batch_norm)
         self._n_heads = int(n_heads)
@@ -75,6 +76,7 @@ class EngineAgent:
         self.update_horizon = update_horizon
         self.precision = precision
         self.huber_delta = float(huber_delta)
+        self.n_bins, self.min_value, self.max_value, self.sigma = int(n_bins), float(min_value), float(max_value), float(sigma)
         self.device = device
         self._seed = int(key) if not isinstance(key, torch.Generator) else int(key.initial_seed())
         self._engine = None
@@ -90,6 +92,7 @@ class EngineAgent:
             self.observation_dim, self.n_actions, self._n_heads, self.features, self.architecture_type,
             self.layer_norm, batch_size, gamma_n=self.gamma**self.update_horizon, learning_rate=self.learning_rate,
             adam_eps=self.adam_eps, precision=self.precision, device=self.device, huber_delta=self.huber_delta, batch_norm=self.batch_norm,
+            n_bins=self.n_bins, min_value=self.min_value, max_value=self.max_value, sigma=self.sigma,
         )
         if init:
             eng.init_params(self._seed)

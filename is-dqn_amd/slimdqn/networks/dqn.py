@@ -33,14 +33,20 @@ class DQN(EngineAgent):
         precision: str = "bf16x3",
         device: str | None = None,
         use_graph: bool = True,
+        n_bins: int = 0,
+        min_value: float = -100.0,
+        max_value: float = 100.0,
+        sigma: float = 3.0,
     ):
+        """``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
-        self.network = DQNNet([int(f) for f in features], architecture_type, n_actions, layer_norm, False)
+        self.network = DQNNet([int(f) for f in features], architecture_type, n_actions * max(int(n_bins), 1), layer_norm, False)
         self.data_to_update = data_to_update
         self.target_update_frequency = target_update_frequency
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
-                                gamma, update_horizon, adam_eps, batch_size, precision, device)
+                                gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
+                                max_value=max_value, sigma=sigma)
         self.target_params = self.params.copy()  # dqn.py:34
         self.cumulated_loss = 0
 

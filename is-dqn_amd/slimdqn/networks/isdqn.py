@@ -47,11 +47,18 @@ class iSDQN(EngineAgent):
         device: str | None = None,
         use_graph: bool = True,
         huber_delta: float = 0.0,
+        n_bins: int = 0,
+        min_value: float = -100.0,
+        max_value: float = 100.0,
+        sigma: float = 3.0,
     ):
-        """``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss."""
+        """``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss.
+        ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
+        cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
         self.n_bellman_iterations = n_bellman_iterations
         self.last_idx_mlp = len(features) if architecture_type == "fc" else len(features) - 3
-        self.network = DQNNet([int(f) for f in features], architecture_type, (1 + n_bellman_iterations) * n_actions, layer_norm, batch_norm)
+        self.network = DQNNet([int(f) for f in features], architecture_type, (1 + n_bellman_iterations) * n_actions * max(int(n_bins), 1),
+                              layer_norm, batch_norm)
         self.data_to_update = data_to_update
         self.target_update_frequency = target_update_frequency
         # update_online_params on a device replay runs as a captured single step (hipGraph: one launch instead of ~25
@@ -59,7 +66,8 @@ class iSDQN(EngineAgent):
         self.use_graph = bool(use_graph)
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
-                                learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm)
+                                learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
+                                n_bins, min_value, max_value, sigma)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 
