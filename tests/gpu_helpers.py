@@ -211,3 +211,29 @@ def adam64(p0, m0, v0, g, t, lr, eps):
     den = np.sqrt(v / c2) + eps
     u = (m / c1) / den
     return p0 - lr * u, m, v, u, den
+
+
+_U, _TINY = 2.0**-24, 2.0**-149  # float32 unit roundoff; denormal spacing, the absolute error floor of one rounding
+
+
+def adam_bounds(p0, m0, v0, g, t, lr, eps):
+    """float64 Adam and the error the kernels' float32 arithmetic may add (derivation, unit roundoff u = 2^-24):
+      m = b1 m0 + (1 - b1) g: two products and a sum, each rounded once (-ffp-contract=off), 1 - b1 exact:
+          |dm| <= u (b1 |m0| + (1 - b1) |g| + |m|)   (<= 2 ulps of the larger term), + a denormal floor per rounding;
+      v = b2 v0 + ((1 - b2) g) g: three roundings of the g term:  |dv| <= u (b2 v0 + 2 (1 - b2) g^2 + v);
+      p = p0 - lr (m inv_c1) rcp(sqrt(v inv_c2) + eps): given m and v, c1 / c2 / their reciprocals (float casts), the products,
+          the eps sum (each 0.5 ulp), v_sqrt_f32 and v_rcp_f32 (1 ulp each) are about 9 u = 5.4e-7 relative to the step: bounded
+          by 1e-6 |lr u| (ADVICE); the final p0 - lr u rounds to 0.5 ulp(p); and the float32 errors of m and v propagate to first
+          order as lr dm / (c1 den) and lr |u| (dv / 2 v) (sqrt(v_hat) / den)."""
+    p, m, v, u, den = adam64(p0, m0, v0, g, t, lr, eps)
+    c1, c2 = 1.0 - float(np.float32(0.9)) ** t, 1.0 - float(np.float32(0.999)) ** t
+    b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
+    g, m0, v0 = (np.asarray(a, np.float64) for a in (g, m0, v0))
+    em = _U * (b1 * np.abs(m0) + (1 - b1) * np.abs(g) + np.abs(m)) + 3 * _TINY
+    ev = _U * (b2 * v0 + 2 * (1 - b2) * g * g + v) + 4 * _TINY
+    s = np.sqrt(v / c2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dv_rel = np.where(v > 0, ev / (2 * v), 0.0)
+    ep = (1e-6 * lr * np.abs(u) + 0.5 * np.spacing(np.abs(p).astype(np.float32)).astype(np.float64)
+          + lr * em / (c1 * den) + lr * np.abs(u) * dv_rel * s / den)
+    return (p, m, v, u), (ep, em, ev)

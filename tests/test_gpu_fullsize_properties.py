@@ -22,13 +22,17 @@ pytestmark = pytest.mark.gpu
 FEATS = (32, 64, 64, 512)
 GAMMA_N = 0.99
 SHAPES = [pytest.param((256, 9, 9), id="c2-B256-K9-A9"), pytest.param((1024, 32, 4), id="c5-B1024-K32-A4")]
+# bf16: what bench.py --precision bf16 times.  (Not for the permutation test: its 1e-4 holds where the lo halves absorb a hi half
+# that rounds the other way under another summation order; in one pass such a flip moves q by up to ~5e-3.)
+PRECISIONS = ["bf16x3", "bf16"]
 
 
-def _engine(shape, seed=0):
+def _engine(shape, seed=0, precision="bf16x3"):
     from slimdqn._engine import QNetEngine
 
     B, K, A = shape
-    eng = QNetEngine((84, 84, 4), A, 1 + K, FEATS, "cnn", True, B, gamma_n=GAMMA_N, learning_rate=6.25e-5, adam_eps=1.5e-4)
+    eng = QNetEngine((84, 84, 4), A, 1 + K, FEATS, "cnn", True, B, gamma_n=GAMMA_N, learning_rate=6.25e-5, adam_eps=1.5e-4,
+                     precision=precision)
     eng.init_params(seed)
     return eng
 
@@ -45,13 +49,14 @@ def _host_targets(shape, eng, frames, ids, action, reward, terminal):
     return qv, tg
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("shape", SHAPES)
-def test_learn_step_is_bitwise_deterministic_and_matches_forward_path(shape):
+def test_learn_step_is_bitwise_deterministic_and_matches_forward_path(shape, precision):
     B, K, A = shape
     frames, ids, action, reward, terminal, _ = make_frame_batch(B, A, seed=5)
     outs = []
     for _ in range(2):
-        eng = _engine(shape, seed=1)
+        eng = _engine(shape, seed=1, precision=precision)
         batch = device_batch(eng, frames, ids, action, reward, terminal)
         qv, tg = _host_targets(shape, eng, frames, ids, action, reward.astype(np.float64), terminal.astype(np.float64))
         pre = eng.loss_on_batch(batch).cpu().numpy().copy()
@@ -73,8 +78,9 @@ def test_learn_step_is_bitwise_deterministic_and_matches_forward_path(shape):
         np.testing.assert_array_equal(a, b)
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("shape", SHAPES)
-def test_several_steps_and_every_intermediate_are_run_to_run_identical(shape):
+def test_several_steps_and_every_intermediate_are_run_to_run_identical(shape, precision):
     """Several back-to-back steps from identical state, three times: parameters, Adam moments and the backward
     intermediates of the last step must be bit-identical.  (This is the test that exposed compiler-renamed dependent
     MFMAs and an LDS hazard in the pipelined K loops: about 1 % of workgroups returned a tile that lacked one MFMA
@@ -85,7 +91,7 @@ def test_several_steps_and_every_intermediate_are_run_to_run_identical(shape):
              "gw/Conv_0", "gw/Conv_1", "gw/Conv_2"]
     ref = None
     for _ in range(3):
-        eng = _engine(shape, seed=3)
+        eng = _engine(shape, seed=3, precision=precision)
         batch = device_batch(eng, frames, ids, action, reward, terminal)
         for _ in range(4):
             eng.learn_on_batch(batch)

@@ -9,16 +9,17 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _replica(workload, seed=3, capacity=4096):
+def _replica(workload, seed=3, capacity=4096, precision="bf16x3"):
     from bench import Replica
 
-    return Replica(workload, capacity, "bf16x3", seed, "cuda:0")
+    return Replica(workload, capacity, precision, seed, "cuda:0")
 
 
-@pytest.mark.parametrize("workload", ["c2", "c3"])  # uniform (one gather per replay), prioritized (one per step)
-def test_graph_replay_equals_eager_steps(workload):
+@pytest.mark.parametrize("workload,precision", [("c2", "bf16x3"), ("c3", "bf16x3"),  # uniform (one gather per replay), prioritized (one per step)
+                                                ("c2", "bf16"), ("c5", "bf16")])  # what bench.py --precision bf16 times
+def test_graph_replay_equals_eager_steps(workload, precision):
     S, n_replays = 4, 3
-    eager, graphed = _replica(workload), _replica(workload)
+    eager, graphed = _replica(workload, precision=precision), _replica(workload, precision=precision)
     assert torch.equal(eager.eng.params, graphed.eng.params)
     graphed.enable_graph(S)
     for _ in range(S * n_replays):
@@ -34,7 +35,7 @@ def test_graph_replay_equals_eager_steps(workload):
         tb = graphed.rb._sampling_distribution._sum_tree._nodes_dev
         assert torch.equal(ta, tb), "sum tree differs between eager and graph replay"
     # and the step really trained
-    fresh = _replica(workload)
+    fresh = _replica(workload, precision=precision)
     assert not torch.equal(fresh.eng.params, graphed.eng.params)
 
 

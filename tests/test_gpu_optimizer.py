@@ -15,12 +15,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_helpers import adam64, device_batch, hip_preactivations, make_frame_batch, make_pair, masked_reference_grads
+from tests.gpu_helpers import adam_bounds as _adam_bounds
+from tests.gpu_helpers import device_batch, hip_preactivations, make_frame_batch, make_pair, masked_reference_grads
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0**-24  # float32 unit roundoff
-TINY = 2.0**-149  # float32 denormal spacing: the absolute error floor of one rounding
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # Which kernel updates which tensor (net_plan.h: dense weight-gradient slabs s = 1 from 128 output tiles of 128 x 128, else 256 / tiles
@@ -98,29 +97,6 @@ def _plant(g_pre, real, t, eps, rng):
 
 def _bits(t):
     return t.detach().clone().view(torch.int32).cpu().numpy()
-
-
-def _adam_bounds(p0, m0, v0, g, t, lr, eps):
-    """float64 Adam and the error the kernels' float32 arithmetic may add (derivation, unit roundoff u = 2^-24):
-      m = b1 m0 + (1 - b1) g: two products and a sum, each rounded once (-ffp-contract=off), 1 - b1 exact:
-          |dm| <= u (b1 |m0| + (1 - b1) |g| + |m|)   (<= 2 ulps of the larger term), + a denormal floor per rounding;
-      v = b2 v0 + ((1 - b2) g) g: three roundings of the g term:  |dv| <= u (b2 v0 + 2 (1 - b2) g^2 + v);
-      p = p0 - lr (m inv_c1) rcp(sqrt(v inv_c2) + eps): given m and v, c1 / c2 / their reciprocals (float casts), the products,
-          the eps sum (each 0.5 ulp), v_sqrt_f32 and v_rcp_f32 (1 ulp each) are about 9 u = 5.4e-7 relative to the step: bounded
-          by 1e-6 |lr u| (ADVICE); the final p0 - lr u rounds to 0.5 ulp(p); and the float32 errors of m and v propagate to first
-          order as lr dm / (c1 den) and lr |u| (dv / 2 v) (sqrt(v_hat) / den)."""
-    p, m, v, u, den = adam64(p0, m0, v0, g, t, lr, eps)
-    c1, c2 = 1.0 - float(np.float32(0.9)) ** t, 1.0 - float(np.float32(0.999)) ** t
-    b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
-    g, m0, v0 = (np.asarray(a, np.float64) for a in (g, m0, v0))
-    em = U * (b1 * np.abs(m0) + (1 - b1) * np.abs(g) + np.abs(m)) + 3 * TINY
-    ev = U * (b2 * v0 + 2 * (1 - b2) * g * g + v) + 4 * TINY
-    s = np.sqrt(v / c2)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        dv_rel = np.where(v > 0, ev / (2 * v), 0.0)
-    ep = (1e-6 * lr * np.abs(u) + 0.5 * np.spacing(np.abs(p).astype(np.float32)).astype(np.float64)
-          + lr * em / (c1 * den) + lr * np.abs(u) * dv_rel * s / den)
-    return (p, m, v, u), (ep, em, ev)
 
 
 @pytest.mark.parametrize("cfg", OPT_CONFIGS)
