@@ -75,6 +75,22 @@ int isdqn_tree_swap_remove(double* nodes, int32_t depth, int32_t index, int32_t 
 int isdqn_tree_query(const double* nodes, int32_t depth, const double* targets, int32_t n, int32_t targets_are_unit,
                      int32_t* out_indices, uint32_t* dev_status, void* stream);
 
+/* isdqn_tree_query plus the importance-sampling weights of prioritized replay (Schaul et al. 2016, section 3.4; the
+ * reference has none), in the same launch.  THE definition: for the n sampled leaves with tree values p_i (already raised to
+ * the priority exponent alpha by the sampler) and root R, P(i) = p_i / R and, with N the number of stored keys,
+ *     w_i = (N P(i))^(-beta) / max_j (N P(j))^(-beta)  =  (p_min / p_i)^beta,     p_min = min_j p_j over the batch
+ * (N and R cancel under the batch-max normalisation -- Dopamine's and the paper's "normalise by 1 / max w" -- which is also why
+ * no min-tree is needed).  pow(p_min / p_i, (double)beta) is evaluated in float64 and rounded once to float32, so the largest
+ * weight is exactly 1.0f and beta = 0 gives exactly 1.0f everywhere.  A sampled leaf with p_i <= 0 (possible only by rounding
+ * at the right edge of the tree) is left out of the minimum and gets weight 1.0f; if no sampled leaf is positive all weights
+ * are 1.0f (the status word already reports the empty tree).
+ * `beta` is a DEVICE float, read by the kernel: a captured graph anneals it without a second capture.  n <=
+ * ISDQN_TREE_MAX_BATCH (one workgroup: the batch minimum is reduced through LDS); out_indices and the status bits are
+ * bit-identical to isdqn_tree_query on the same inputs; out_leaf (may be NULL) receives the n leaf values p_i. */
+int isdqn_tree_query_weighted(const double* nodes, int32_t depth, const double* targets, int32_t n, int32_t targets_are_unit,
+                              const float* beta, int32_t* out_indices, double* out_leaf, float* out_weights,
+                              uint32_t* dev_status, void* stream);
+
 /* ========================================================================== */
 /* Device-resident replay  (slimdqn/sample_collection/replay_buffer.py)        */
 /* ========================================================================== */
@@ -237,6 +253,13 @@ typedef struct isdqn_batch {
     void* priorities_ready;   /* hipEvent_t or NULL: recorded on `stream` once q_values / targets / priorities / losses of
                                * this call are final (long before the call's last kernel), so that a caller's second stream
                                * can write the priorities back (R6) and draw the next batch (S4, R5) under the backward pass */
+    const float* loss_weights; /* [B] device floats, finite and >= 0, or NULL (= weight 1 everywhere, same bits as before the
+                               * field existed): the importance-sampling weights of isdqn_tree_query_weighted.  With l the
+                               * configured per-element loss of d = q - target (squared, Huber, HL-Gauss cross-entropy):
+                               * losses[k] = (1 / B) sum_b w_b l_bk, dL/dq_bk = w_b l'(d_bk) / B (HL: dL/dlogit = w_b (softmax - p)
+                               * / B); losses_accum accumulates the weighted losses; q_values, targets and priorities stay
+                               * unweighted (the priorities are the raw TD error that goes back into the tree).  Honoured by
+                               * learn / loss / their _target forms / grad_on_batch */
 } isdqn_batch;
 
 /* The workspace keeps a pre-split (bf16 hi + lo) mirror of the weights that the MFMA stages copy from.  Every entry point

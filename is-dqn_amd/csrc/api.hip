@@ -13,5 +13,5 @@ void set_last_error(const char* fmt, ...) {
 }
 }  // namespace isdqn
 
-extern "C" const char* isdqn_version(void) { return "isdqn_hip 0.1 (gfx950)"; }
+extern "C" const char* isdqn_version(void) { return "isdqn_hip 0.2 (gfx950)"; }
 extern "C" const char* isdqn_last_error(void) { return isdqn::g_last_error; }

@@ -368,7 +368,8 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
     float* loss_part = ws + P.lpart_off;
     float* dbh_part = loss_part + (int64_t)n_blk * K;
     hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K, on0, tg0, P.n_actions, P.nha_p,
-                       batch->action, batch->reward, batch->terminal, cfg->gamma_n, cfg->huber_delta, learn ? ws + P.dout_off : nullptr, qv, tg, priorities,
+                       batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta, learn ? ws + P.dout_off : nullptr, qv, tg,
+                       priorities,
                        loss_part, dbh_part);
     ISDQN_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nha_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nha_p,

@@ -73,7 +73,8 @@ __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict_
 // (transition, k) pairs w, w + 4, ...: online head on0 + k at the taken action is regressed on head tg0 + k of the next-state rows.
 //   target = r + (1 - terminal) gamma^n max_a' Q_{tg0+k}(s', a');  y = clamp(target, v_min, v_max)
 //   u_i = erf((e_i - y) / (sqrt(2) sigma)),  p_j = (u_{j+1} - u_j) / (u_nb - u_0)   (the clamp keeps u_nb - u_0 away from 0/0)
-//   CE = logsumexp(l) - sum_j p_j l_j,  dL/dl_j = (softmax(l)_j - p_j) / B on the taken action's nb logits, 0 elsewhere.
+//   CE = w_b (logsumexp(l) - sum_j p_j l_j),  dL/dl_j = w_b (softmax(l)_j - p_j) / B on the taken action's nb logits, 0 elsewhere
+//   (w_b: isdqn_batch.loss_weights, 1 without).
 // Writes q_values / targets [B][K] (expectation, unclamped scalar target), priorities[B] = sqrt(mean_k (q - target)^2 + 1e-10) --
 // the expectations' TD error, not the CE (which never falls below the target histogram's entropy) -- per-workgroup partials of the
 // per-pair CE sums (loss_part [n_blk][K]) and, with `dout`, the dL/dlogits rows (zero-filled) and their column sums over the
@@ -82,13 +83,14 @@ __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ logits, int B, int R, int K, int on0, int tg0, int A,
                                                       int nb, int nlog_p, float vmin, float eta, float sigma,
                                                       const int* __restrict__ action, const float* __restrict__ reward,
-                                                      const uint8_t* __restrict__ terminal, float gamma_n, float* __restrict__ dout,
+                                                      const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
+                                                      float gamma_n, float* __restrict__ dout,
                                                       float* __restrict__ q_values, float* __restrict__ targets,
                                                       double* __restrict__ priorities, float* __restrict__ loss_part,
                                                       float* __restrict__ dbh_part) {
     extern __shared__ float s_dl[];  // [R][K][nb]
     __shared__ int s_action[HL_MAX_ROWS];
-    __shared__ float s_r[HL_MAX_ROWS], s_nt[HL_MAX_ROWS];
+    __shared__ float s_r[HL_MAX_ROWS], s_nt[HL_MAX_ROWS], s_w[HL_MAX_ROWS];  // s_w: importance-sampling weights (none: 1)
     __shared__ float s_ce[HL_MAX_ROWS * 64], s_td2[HL_MAX_ROWS * 64];  // [R][K], K <= 64 (checked by the host)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b0 = blockIdx.x * R;
@@ -102,6 +104,7 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ 
         s_action[tid] = on ? action[b0 + tid] : -1;
         s_r[tid] = on ? reward[b0 + tid] : 0.f;
         s_nt[tid] = on ? 1.f - (float)terminal[b0 + tid] : 0.f;
+        s_w[tid] = (on && loss_weights != nullptr) ? loss_weights[b0 + tid] : 1.f;
     }
     __syncthreads();
     const float inv_s = 1.f / (1.41421356237309515f * sigma);
@@ -130,12 +133,12 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ 
             if (j < nb) {
                 const float p = (erff((vmin + (float)(j + 1) * eta - y) * inv_s) - erff((vmin + (float)j * eta - y) * inv_s)) * inv_norm;
                 pl += p * v[t];
-                s_dl[(int64_t)pr * nb + j] = (e[t] * inv_sum - p) * inv_b;
+                s_dl[(int64_t)pr * nb + j] = (e[t] * inv_sum - p) * inv_b * s_w[bl];
             }
         }
         pl = hl_wave_sum(pl);
         if (lane == 0) {
-            s_ce[pr] = m + logf(s) - pl;
+            s_ce[pr] = (m + logf(s) - pl) * s_w[bl];  // (s_td2 stays unweighted: the priorities are the raw TD error)
             s_td2[pr] = (qv - tg) * (qv - tg);
             if (q_values) q_values[(int64_t)b * K + k] = qv;
             if (targets) targets[(int64_t)b * K + k] = tg;

@@ -345,8 +345,9 @@ __device__ __forceinline__ float td_dloss(float d, float huber_delta) {
 constexpr int TD_ROWS = 64;
 __global__ __launch_bounds__(256) void td_kernel(const float* __restrict__ q, int B, int K, int oh, int th, int A, int nha_p,
                                                  const int* __restrict__ action, const float* __restrict__ reward,
-                                                 const uint8_t* __restrict__ terminal, float gamma_n, float huber_delta,
-                                                 float* __restrict__ dout, float* __restrict__ q_values,
+                                                 const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
+                                                 float gamma_n, float huber_delta, float* __restrict__ dout,
+                                                 float* __restrict__ q_values,
                                                  float* __restrict__ targets, double* __restrict__ priorities,
                                                  float* __restrict__ loss_part, float* __restrict__ dbh_part) {
     extern __shared__ float s_d[];  // [TD_ROWS][K] : 2*(q-target)/B ; then [TD_ROWS][K] td
@@ -362,11 +363,12 @@ __global__ __launch_bounds__(256) void td_kernel(const float* __restrict__ q, in
         for (int i = tid; i < rows * nha_p; i += 256) dout[(int64_t)b0 * nha_p + i] = 0.f;
     }
     int a = 0;
-    float r = 0.f, nt = 0.f;
+    float r = 0.f, nt = 0.f, w = 1.f;  // w: importance-sampling weight of the transition (isdqn_batch.loss_weights; none: 1)
     if (on) {
         a = action[b];
         r = reward[b];
         nt = 1.f - (float)terminal[b];
+        if (loss_weights != nullptr) w = loss_weights[b];
     }
     if (wave == 0) s_action[lane] = on ? a : -1;
     for (int k = wave; k < K; k += 4) {
@@ -382,9 +384,9 @@ __global__ __launch_bounds__(256) void td_kernel(const float* __restrict__ q, in
             if (q_values) q_values[(int64_t)b * K + k] = qv;
             if (targets) targets[(int64_t)b * K + k] = tg;
         }
-        s_d[lane * K + k] = td_dloss(d, huber_delta) * inv_b;
-        s_td[lane * K + k] = td;
-        float sum = td;
+        s_d[lane * K + k] = td_dloss(d, huber_delta) * inv_b * w;
+        s_td[lane * K + k] = td;  // unweighted: the priorities are the raw TD error
+        float sum = td * w;
         for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
         if (lane == 0) loss_part[(int64_t)blockIdx.x * K + k] = sum;
     }
@@ -441,6 +443,7 @@ struct HeadChainParams {
     const int* action;
     const float* reward;
     const uint8_t* terminal;
+    const float* loss_weights;  // [B] importance-sampling weights, or null (weight 1)
     float gamma_n, huber_delta;
     float* dout;        // [B][Op]  dL/dq
     float* dz;          // [B][Fp]
@@ -470,7 +473,7 @@ constexpr int HC_KU = 16 / HC_WAVES;  // K-steps per wave and work item (an item
 __host__ __device__ inline int head_chain_pitch(int Fp) { return (Fp + 31) / 32 * 32 + 8; }
 static inline int head_chain_lds_bytes(int Fp, int Op, int K, int passes, int S) {
     const int PA = head_chain_pitch(Fp);
-    return (passes >= 2 ? 2 : 1) * 16 * PA * 2 + (HC_WAVES * 16 * Op + 16 * Op + S * Op + Op + 4 + 2 * S * Fp) * 4 + S * K * 8 +
+    return (passes >= 2 ? 2 : 1) * 16 * PA * 2 + (HC_WAVES * 16 * Op + 16 * Op + S * Op + Op + 4 + 2 * S * Fp) * 4 + S * K * 12 +
            HC_WAVES * 2 * S * 2 * 4 + 64;
 }
 
@@ -486,8 +489,9 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
     float* s_q = qpart + HC_WAVES * 16 * p.Op;                                  // [16][Op]
     float* s_dq = s_q + 16 * p.Op;                                       // [SMAX][Op]
     float* s_d = s_dq + SMAX * p.Op;                                 // [SMAX][K]
-    float* s_td = s_d + SMAX * p.K;
-    float* s_red = s_td + SMAX * p.K;                                // [HC_WAVES][2 * SMAX][2]
+    float* s_td = s_d + SMAX * p.K;                                  // TD loss per (transition, head): the priorities
+    float* s_wtd = s_td + SMAX * p.K;                                // the same times the transition's weight: the loss partials
+    float* s_red = s_wtd + SMAX * p.K;                               // [HC_WAVES][2 * SMAX][2]
     float* s_bias = s_red + HC_WAVES * 2 * SMAX * 2;                 // [Op]
     float* s_pre = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(s_bias + p.Op) + 15) & ~(uintptr_t)15);  // [2 * SMAX][Fp] hidden pre-activations, 16-B aligned
 
@@ -521,11 +525,14 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
         ISDQN_BOUNDS_CHECK((s < S && b0 + s < p.B) ? (const void*)(p.action + b0 + s) : zero_chunk(), 4, 20);
         act[s] = *(const ISDQN_GLOBAL int*)((s < S && b0 + s < p.B) ? (const void*)(p.action + b0 + s) : zero_chunk());
     }
-    float td_r;          // reward, terminal flag of this thread's (transition, head) pair
+    float td_r, td_w;    // reward, importance-sampling weight, terminal flag of this thread's (transition, head) pair
     uint8_t td_term;
     {
         const int s = tid / K;
         const bool ok = tid < S * K && b0 + s < p.B;
+        const bool okw = ok && p.loss_weights != nullptr;
+        ISDQN_BOUNDS_CHECK(okw ? (const void*)(p.loss_weights + b0 + s) : zero_chunk(), 4, 29);
+        td_w = *(const ISDQN_GLOBAL float*)(okw ? (const void*)(p.loss_weights + b0 + s) : zero_chunk());
         ISDQN_BOUNDS_CHECK(ok ? (const void*)(p.reward + b0 + s) : zero_chunk(), 4, 21);
         ISDQN_BOUNDS_CHECK(ok ? (const void*)(p.terminal + b0 + s) : zero_chunk(), 1, 22);
         td_r = *(const ISDQN_GLOBAL float*)(ok ? (const void*)(p.reward + b0 + s) : zero_chunk());
@@ -766,9 +773,11 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
             if (p.q_values) p.q_values[(int64_t)b * K + k] = qv;
             if (p.targets) p.targets[(int64_t)b * K + k] = tg;
         }
-        const float dd = td_dloss(d, p.huber_delta) * inv_b;
+        const float w = p.loss_weights != nullptr ? td_w : 1.f;
+        const float dd = td_dloss(d, p.huber_delta) * inv_b * w;
         s_d[tid] = dd;
         s_td[tid] = td;
+        s_wtd[tid] = td * w;
         s_dq[s * Op + (p.oh + k) * A + a] = dd;
     }
     __syncthreads();
@@ -783,7 +792,7 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
     }
     if (tid < K) {
         float sum = 0.f;
-        for (int s = 0; s < S; ++s) sum += s_td[s * K + tid];
+        for (int s = 0; s < S; ++s) sum += s_wtd[s * K + tid];
         p.loss_part[(int64_t)blockIdx.x * K + tid] = sum;
     }
     if (p.priorities != nullptr && tid < S && b0 + tid < p.B) {
@@ -1993,6 +2002,7 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
         hp.B = B; hp.S = hc_S; hp.F = hid.out_f; hp.Fp = hid.out_p; hp.O = P.nha; hp.Op = P.nha_p; hp.K = K; hp.oh = P.oh;
         hp.A = P.n_actions;
         hp.action = batch->action; hp.reward = batch->reward; hp.terminal = batch->terminal;
+        hp.loss_weights = batch->loss_weights;
         hp.gamma_n = cfg->gamma_n; hp.huber_delta = cfg->huber_delta;
         hp.dout = ws + P.dout_off; hp.dz = ws + hid.dz_off; hp.part = ws + hid.part_off;
         hp.q_values = qv; hp.targets = tg; hp.priorities = priorities;
@@ -2033,11 +2043,11 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
         if (hl_R)
             hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.hl_nb * sizeof(float), st, ws + P.logits_off, B, hl_R,
                                K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
-                               batch->action, batch->reward, batch->terminal, cfg->gamma_n, learn ? ws + P.dout_off : nullptr, qv, tg,
-                               priorities, loss_part, dbh_part);
+                               batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n,
+                               learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
         else
             hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K,
-                               on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, cfg->gamma_n, cfg->huber_delta,
+                               on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta,
                                learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
         ISDQN_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nlog_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nlog_p,

@@ -185,13 +185,10 @@ __global__ __launch_bounds__(64) void tree_swap_remove_kernel(double* __restrict
     (void)status;
 }
 
-__global__ __launch_bounds__(256) void tree_query_kernel(const double* __restrict__ nodes, int depth,
-                                                         const double* __restrict__ targets, int n, int unit,
-                                                         int* __restrict__ out, uint32_t* status) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double root = nodes[0];
-    double tgt = targets[i];
+// One draw of SumTree.query (sum_tree.py:58-102): the inverse-CDF descent shared by the two query kernels; returns the NODE
+// index of the leaf.
+__device__ __forceinline__ int tree_descend(const double* __restrict__ nodes, int depth, double root, double tgt, int unit,
+                                            uint32_t* status) {
     if (unit) tgt = 0.0 + root * tgt;  // numpy random_uniform: low + range * next_double
     if (!(tgt >= 0.0 && tgt < root)) atomicOr(status, root == 0.0 ? ISDQN_STATUS_EMPTY_TREE : ISDQN_STATUS_TARGET_RANGE);
     int node = 0;
@@ -202,7 +199,62 @@ __global__ __launch_bounds__(256) void tree_query_kernel(const double* __restric
         node = go_left ? left : left + 1;
         tgt = go_left ? tgt : tgt - ls;
     }
+    return node;
+}
+
+__global__ __launch_bounds__(256) void tree_query_kernel(const double* __restrict__ nodes, int depth,
+                                                         const double* __restrict__ targets, int n, int unit,
+                                                         int* __restrict__ out, uint32_t* status) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int node = tree_descend(nodes, depth, nodes[0], targets[i], unit, status);
     out[i] = node - ((1 << (depth - 1)) - 1);
+}
+
+// The query plus the importance-sampling weights w_i = (p_min / p_i)^beta of the drawn leaves (definition: include/isdqn_hip.h,
+// isdqn_tree_query_weighted).  One workgroup, thread t takes draws t, t + 1024, ...: descend, read the leaf, reduce the
+// batch minimum over the positive leaves (waves by shuffle, then the 16 wave minima through LDS in wave order), write the weights.
+// Fused because it sits on the sampling stream between the priority write-back of step s and the row gather of step s+1: a
+// weights launch of its own would add a launch and a dependent round trip to a chain that is pure latency.
+constexpr int TREE_QW_THREADS = 1024, TREE_QW_PER_THREAD = ISDQN_TREE_MAX_BATCH / TREE_QW_THREADS;
+__global__ __launch_bounds__(TREE_QW_THREADS) void tree_query_weighted_kernel(const double* __restrict__ nodes, int depth,
+                                                                              const double* __restrict__ targets, int n, int unit,
+                                                                              const float* __restrict__ beta, int* __restrict__ out,
+                                                                              double* __restrict__ out_leaf,
+                                                                              float* __restrict__ out_weights, uint32_t* status) {
+    __shared__ double s_wmin[TREE_QW_THREADS / 64];
+    const int t = threadIdx.x;
+    const double b = (double)*beta;
+    const double root = nodes[0];
+    const int first_leaf = (1 << (depth - 1)) - 1;
+    double leaf[TREE_QW_PER_THREAD];
+    double pmin = INFINITY;
+#pragma unroll
+    for (int k = 0; k < TREE_QW_PER_THREAD; ++k) {
+        const int i = t + k * TREE_QW_THREADS;
+        leaf[k] = 0.0;
+        if (i < n) {
+            const int node = tree_descend(nodes, depth, root, targets[i], unit, status);
+            out[i] = node - first_leaf;
+            leaf[k] = nodes[node];
+            if (out_leaf != nullptr) out_leaf[i] = leaf[k];
+            if (leaf[k] > 0.0) pmin = leaf[k] < pmin ? leaf[k] : pmin;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(pmin, off);
+        pmin = o < pmin ? o : pmin;
+    }
+    if ((t & 63) == 0) s_wmin[t >> 6] = pmin;
+    __syncthreads();
+    pmin = s_wmin[0];
+#pragma unroll
+    for (int w = 1; w < TREE_QW_THREADS / 64; ++w) pmin = s_wmin[w] < pmin ? s_wmin[w] : pmin;
+#pragma unroll
+    for (int k = 0; k < TREE_QW_PER_THREAD; ++k) {
+        const int i = t + k * TREE_QW_THREADS;
+        if (i < n) out_weights[i] = leaf[k] > 0.0 ? (float)pow(pmin / leaf[k], b) : 1.0f;
+    }
 }
 
 }  // namespace isdqn
@@ -254,6 +306,19 @@ extern "C" int isdqn_tree_query(const double* nodes, int32_t depth, const double
     if (n == 0) return ISDQN_OK;
     hipLaunchKernelGGL(tree_query_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, nodes, depth,
                        targets, n, targets_are_unit, out_indices, dev_status);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_tree_query_weighted(const double* nodes, int32_t depth, const double* targets, int32_t n,
+                                         int32_t targets_are_unit, const float* beta, int32_t* out_indices, double* out_leaf,
+                                         float* out_weights, uint32_t* dev_status, void* stream) {
+    ISDQN_REQUIRE(nodes && targets && beta && out_indices && out_weights && dev_status, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(depth >= 1 && depth <= 30, ISDQN_ERR_ARG, "bad depth");
+    ISDQN_REQUIRE(n >= 0 && n <= ISDQN_TREE_MAX_BATCH, ISDQN_ERR_SHAPE, "batch negative or larger than ISDQN_TREE_MAX_BATCH");
+    if (n == 0) return ISDQN_OK;
+    hipLaunchKernelGGL(tree_query_weighted_kernel, dim3(1), dim3(TREE_QW_THREADS), 0, (hipStream_t)stream, nodes, depth, targets,
+                       n, targets_are_unit, beta, out_indices, out_leaf, out_weights, dev_status);
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }

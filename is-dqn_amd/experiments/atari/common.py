@@ -30,7 +30,10 @@ def make_environment(p: dict):
 
 
 def make_replay(p: dict, prioritized: bool = False) -> ReplayBuffer:
-    sampler = PrioritizedSamplingDistribution(p["seed"], p["replay_buffer_capacity"]) if prioritized else UniformSamplingDistribution(p["seed"])
+    if prioritized:
+        sampler = PrioritizedSamplingDistribution(p["seed"], p["replay_buffer_capacity"], priority_exponent=p.get("priority_exponent", 1.0))
+    else:
+        sampler = UniformSamplingDistribution(p["seed"])
     return ReplayBuffer(
         sampling_distribution=sampler,
         max_capacity=p["replay_buffer_capacity"],

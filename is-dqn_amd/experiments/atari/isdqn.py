@@ -16,7 +16,7 @@ import numpy as np
 from experiments.base.dqn import train
 from experiments.atari.common import make_environment, make_replay, seeds
 from experiments.base.utils import prepare_logs
-from experiments.base.parser_argument import histogram_loss_kwargs
+from experiments.base.parser_argument import histogram_loss_kwargs, n_gradient_steps
 from slimdqn.networks.isdqn import iSDQN
 
 
@@ -49,7 +49,7 @@ def run(argvs=sys.argv[1:], root=None):
         huber_delta=p["huber_delta"],
     )
     if p["prioritized"]:
-        _wire_prioritized(agent, rb)
+        _wire_prioritized(agent, rb, p)
     try:
         out = train(np.random.default_rng(train_seed), p, agent, env, rb)
     finally:
@@ -59,15 +59,19 @@ def run(argvs=sys.argv[1:], root=None):
     return out
 
 
-def _wire_prioritized(agent, rb):
+def _wire_prioritized(agent, rb, p=None):
     """Trainer wiring the reference does not have: new elements enter with the
     largest priority seen so far (Dopamine's convention), sampled elements get sqrt(mean_k td) written back.
     Neither costs a read-back: the maximum is resolved on the device when the staged leaf writes are flushed
-    (samplers.py MAX_PRIORITY), the write-back is part of the captured step (networks/isdqn.py)."""
+    (samplers.py MAX_PRIORITY), the write-back is part of the captured step (networks/isdqn.py).
+    With -isb the loss of every sampled transition carries its importance-sampling weight, beta annealed from -isb to -isbe over
+    the run's gradient steps."""
     sampler = rb._sampling_distribution
     plain_add = rb.add
     rb.add = lambda transition, **kw: plain_add(transition, **{"priority": sampler.MAX_PRIORITY, **kw})
     agent.priority_writeback = True
+    if p is not None and p.get("is_beta", 0.0) != 0.0:
+        agent.set_importance_sampling(p["is_beta"], p.get("is_beta_end"), n_steps=n_gradient_steps(p))
 
 
 if __name__ == "__main__":

@@ -40,6 +40,9 @@ _TFDQN = [_ISDQN[1], _ISDQN[2], _ISDQN[3]]  # add_tfdqn_arguments: layer_norm, b
 _ENGINE = [
     ("-prec", "--precision", dict(type=str, default="bf16x3", choices=["bf16x3", "bf16"], help="MFMA precision of the HIP engine.")),
     ("-per", "--prioritized", dict(action="store_true", default=False, help="Prioritized replay (sum-tree on the GPU) with TD-error writeback.")),
+    ("-pe", "--priority_exponent", dict(type=float, default=1.0, help="alpha of prioritized replay: leaves hold priority ** alpha. Means nothing without -per.")),
+    ("-isb", "--is_beta", dict(type=float, default=0.0, help="Importance-sampling exponent beta at the first gradient step; 0 = no importance-sampling weights. Needs -per.")),
+    ("-isbe", "--is_beta_end", dict(type=float, default=None, help="beta at the last gradient step of the run (linear in between); default: constant -isb. Means nothing without -per and -isb.")),
     ("-hd", "--huber_delta", dict(type=float, default=0.0, help="0: squared TD error (the reference's loss); > 0: Huber loss with this delta.")),
     ("-hl", "--histogram_loss", dict(action="store_true", default=False, help="HL-Gauss histogram loss on the heads (the four flags below; off: scalar heads).")),
     # add_histogram_loss_parameters (reference parser_argument.py:199-228): names, types and defaults of the reference
@@ -85,6 +88,20 @@ def add_analysistfdqn_arguments(parser: argparse.ArgumentParser) -> List[str]:
 
 def add_engine_arguments(parser: argparse.ArgumentParser) -> List[str]:
     return _add(parser, _ENGINE)
+
+
+PRIORITIZED_FLAGS = ["priority_exponent", "is_beta", "is_beta_end"]  # stored in parameters.json with the algorithm's flags under -per
+
+
+def check_engine_arguments(p: dict) -> None:
+    if p["is_beta"] != 0.0 and not p["prioritized"]:
+        raise ValueError("-isb / --is_beta weighs prioritized samples: it needs -per / --prioritized")
+
+
+def n_gradient_steps(p: dict) -> int:
+    """Gradient steps of a whole run (the length of the beta schedule): one every data_to_update environment steps once
+    n_initial_samples are in the buffer."""
+    return max(1, int((p["n_epochs"] * p["n_training_steps_per_epoch"] - p["n_initial_samples"]) / p["data_to_update"]))
 
 
 def histogram_loss_kwargs(p) -> dict:

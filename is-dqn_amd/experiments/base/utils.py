@@ -33,6 +33,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     agent = getattr(parser_argument, f"add_{algo_name}_arguments")(parser)
     parser_argument.add_engine_arguments(parser)
     p = vars(parser.parse_args(argvs))
+    parser_argument.check_engine_arguments(p)
     p["env_name"] = env_name
     if env_name == "atari":
         p["game_name"] = p["experiment_name"].split("_")[-1]
@@ -40,7 +41,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     root = root or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     p["save_path"] = os.path.join(root, env_name, "exp_output", p["experiment_name"], algo_name)
     check_experiment(p)
-    store_params(p, shared, agent)
+    store_params(p, shared, agent + (parser_argument.PRIORITIZED_FLAGS if p["prioritized"] else []))
     p["wandb"] = _NullLogger()
     return p
 

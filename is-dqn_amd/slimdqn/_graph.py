@@ -10,17 +10,25 @@ pre-drawn dense indices (uniform) or unit draws (prioritized) are copied into th
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from slimdqn import _hip
 
 
 class GraphedUpdate:
-    def __init__(self, rb, eng, prioritized: bool, steps_per_graph: int = 8, writeback: bool | None = None, learn=None):
+    def __init__(self, rb, eng, prioritized: bool, steps_per_graph: int = 8, writeback: bool | None = None, learn=None,
+                 weighted: bool = False):
         """``prioritized``: the sampler is a sum tree (the query is part of the graph); ``writeback``: sqrt(mean_k td) of
         every step goes back into the tree (default: whenever prioritized); ``learn``: the learn call of one step on a C batch
-        (default ``eng.learn_on_batch``; DQN passes its target-parameter form, dqn.py:59-72)."""
+        (default ``eng.learn_on_batch``; DQN passes its target-parameter form, dqn.py:59-72); ``weighted``: the query also writes
+        the importance-sampling weights of its draws and the learn call applies them (prioritized only).  The betas are INPUT of
+        a replay, like the draws: ``run(betas)`` stages one per step, the query kernel reads its step's from device memory -- a
+        replay with other betas is the same executable graph."""
+        if weighted and not prioritized:
+            raise ValueError("importance-sampling weights need the prioritized sampling distribution")
         self.rb, self.eng, self.prioritized, self.S = rb, eng, prioritized, steps_per_graph
+        self.weighted = bool(weighted)
         self._learn = eng.learn_on_batch if learn is None else learn
         self.writeback = prioritized if writeback is None else (writeback and prioritized)
         dev, B, s2 = eng.device, eng.batch_size, 2 * rb._stack_size
@@ -41,6 +49,9 @@ class GraphedUpdate:
             self._prio_ready = [torch.cuda.Event() for _ in range(2)]
             for e in self._prio_ready:
                 e.record(self._sampling_stream)  # creates the handle the C ABI takes
+        # weights of the two batch slots (the query of slot 1 - slot writes them on the sampling stream) and the S betas
+        self.weights = torch.ones(2, B, dtype=torch.float32, device=dev) if self.weighted else None
+        self.betas = torch.zeros(self.S, dtype=torch.float32, device=dev) if self.weighted else None
         self.frame_ids = torch.zeros(n_b, B, s2, dtype=torch.int32, device=dev)
         self.action = torch.zeros(n_b, B, dtype=torch.int32, device=dev)
         self.reward = torch.zeros(n_b, B, dtype=torch.float32, device=dev)
@@ -79,18 +90,20 @@ class GraphedUpdate:
         # every step of a replay finds the weight mirror current: steps 2..S follow a learn step of the same graph, step 1 follows
         # run()'s check
         ev = lambda i: self._prio_ready[i] if self.prioritized else None
+        wt = lambda i: self.weights[i] if self.weighted else None
         if self.fc:
             B = self.B
             rows = lambda half, i: self.obs[half, i * B:(i + 1) * B].view(torch.float32)
             self.chained = [
                 eng.make_batch(state=rows(0, i), next_state=rows(1, i), action=self.action[i], reward=self.reward[i], terminal=self.terminal[i],
-                               mirror_current=True, priorities_ready=ev(i))
+                               mirror_current=True, priorities_ready=ev(i), loss_weights=wt(i))
                 for i in range(self.frame_ids.shape[0])
             ]
             return
         self.chained = [
             eng.make_batch(frames=rb._frames, frame_stride=rb._hw, frame_ids=self.frame_ids[i], action=self.action[i],
-                           reward=self.reward[i], terminal=self.terminal[i], mirror_current=True, priorities_ready=ev(i))
+                           reward=self.reward[i], terminal=self.terminal[i], mirror_current=True, priorities_ready=ev(i),
+                           loss_weights=wt(i))
             for i in range(self.frame_ids.shape[0])
         ]
 
@@ -117,6 +130,13 @@ class GraphedUpdate:
             "isdqn_replay_materialize",
         )
 
+    def _query(self, tree, s: int, slot: int) -> None:
+        """Draw of step ``s`` into batch slot ``slot`` (weighted: its importance-sampling weights with it, one launch)."""
+        if self.weighted:
+            tree.query_device(self.block[s], out=self.indices[slot], unit=True, beta=self.betas[s:s + 1], weights_out=self.weights[slot])
+        else:
+            tree.query_device(self.block[s], out=self.indices[slot], unit=True)
+
     def _steps(self) -> None:
         """The S steps of one replay, enqueued on the current stream.  The first node rebuilds the weight mirror from the parameters
         as they are when the replay starts (whoever wrote them, however: _engine.py "weight-mirror bookkeeping"); the steps behind
@@ -127,7 +147,7 @@ class GraphedUpdate:
         if self.prioritized:
             tree = rb._sampling_distribution._sum_tree
             main, sampling = torch.cuda.current_stream(eng.device), self._sampling_stream
-            tree.query_device(self.block[0], out=self.indices[0], unit=True)
+            self._query(tree, 0, 0)
             self._gather(self.indices[0], self.B, 0)
             for s in range(self.S):
                 slot = s & 1
@@ -141,7 +161,7 @@ class GraphedUpdate:
                     if self.writeback:
                         rb._sampling_distribution.update_device(self.indices[slot], eng.priorities)
                     if s + 1 < self.S:
-                        tree.query_device(self.block[s + 1], out=self.indices[1 - slot], unit=True)
+                        self._query(tree, s + 1, 1 - slot)
                         self._gather(self.indices[1 - slot], self.B, 1 - slot)
                 main.wait_stream(sampling)
         else:
@@ -178,9 +198,12 @@ class GraphedUpdate:
         self.eng.invalidate_mirror()
         self.graph = g
 
-    def run(self) -> None:
-        """S steps: draw S index rows on the host stream of the sampler, stage them, replay the graph."""
+    def run(self, betas=None) -> None:
+        """S steps: draw S index rows on the host stream of the sampler, stage them (weighted: and the S float32 ``betas`` of these
+        steps), replay the graph."""
         rb = self.rb
+        if self.weighted != (betas is not None):
+            raise ValueError("a weighted captured update takes the betas of its S steps, an unweighted one none")
         rb._flush()
         if rb._frames.data_ptr() != self._frames_ptr:  # the frame store was re-allocated: pointers in the graph are stale
             self._frames_ptr = rb._frames.data_ptr()
@@ -190,6 +213,10 @@ class GraphedUpdate:
         sampler = rb._sampling_distribution
         rows = sampler.draw_rows_device(self.S, self.B)
         self.block.copy_(rows, non_blocking=True)
+        if self.weighted:
+            betas = np.ascontiguousarray(betas, dtype=np.float32)
+            assert betas.shape == (self.S,)
+            self.betas.copy_(sampler._to_device(betas, torch.float32), non_blocking=True)
         if self.eng.trust_mirror:
             self.eng.refresh_mirror()  # (trusted engines only: one eager launch when the bookkeeping says the mirror is stale)
         self.graph.replay()

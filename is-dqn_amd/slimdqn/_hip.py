@@ -86,6 +86,7 @@ class Batch(ctypes.Structure):
         ("terminal", c_void_p),
         ("flags", c_int32),
         ("priorities_ready", c_void_p),
+        ("loss_weights", c_void_p),  # float32 [B] importance-sampling weights or NULL (include/isdqn_hip.h)
     ]
 
 
@@ -96,6 +97,10 @@ _SIGNATURES = {
     "isdqn_tree_set": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "isdqn_tree_swap_remove": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "isdqn_tree_query": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "isdqn_tree_query_weighted": (
+        c_int32,
+        [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "isdqn_replay_apply_staged": (
         c_int32,
         [c_void_p, POINTER(StagedUpdates), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -57,8 +57,50 @@ def _is_one_frame_shift(old: np.ndarray, new: np.ndarray) -> bool:
     return bool(np.array_equal(new[..., :-1], old[..., 1:]))
 
 
+def importance_beta(beta_start: float, beta_end, n_steps: int, step: int) -> np.float32:
+    """The importance-sampling exponent of gradient step ``step`` (0-based): linear from ``beta_start`` at step 0 to ``beta_end``
+    at step ``n_steps``, ``beta_end`` from there on; ``beta_start`` throughout when ``beta_end`` is None.  Host float64
+    arithmetic, stored as float32 -- the value the eager and the captured update both hand to the device."""
+    if beta_end is None:
+        return np.float32(beta_start)
+    if step >= n_steps:
+        return np.float32(beta_end)
+    b0, b1 = np.float64(beta_start), np.float64(beta_end)
+    return np.float32(b0 + (b1 - b0) * (np.float64(max(step, 0)) / np.float64(n_steps)))
+
+
 class EngineAgent:
     """Common state: ``n_heads`` network heads of ``n_actions`` outputs each on the HIP engine."""
+
+    _is_schedule = None  # (beta_start, beta_end, n_steps) once set_importance_sampling was called; None: no weights anywhere
+    _is_step = 0         # gradient steps taken under the schedule
+
+    # ------------------------------------------------------------------ importance sampling (prioritized replay)
+    def set_importance_sampling(self, beta_start: float, beta_end: float | None = None, n_steps: int = 0) -> None:
+        """Weigh the loss of every sampled transition with the importance-sampling weight of its draw (Schaul et al. 2016, 3.4;
+        computed by the sum-tree query: include/isdqn_hip.h, isdqn_tree_query_weighted).  beta is linear in gradient steps from
+        ``beta_start`` to ``beta_end`` over ``n_steps`` steps, constant when ``beta_end`` is None.  Needs a prioritized replay.
+        Until this is called no weight is computed and the learn calls get a NULL weights pointer."""
+        self._is_schedule = (float(beta_start), None if beta_end is None else float(beta_end), int(n_steps))
+        self._is_step = 0
+        self._drop_graph()  # (the captured step has the weighted query and the weights pointer, or not)
+
+    @property
+    def importance_sampling(self) -> bool:
+        return self._is_schedule is not None
+
+    def _next_betas(self, n: int = 1):
+        """float32 betas of the next ``n`` gradient steps (None when importance sampling is off); advances the step count."""
+        if self._is_schedule is None:
+            return None
+        t = self._is_step
+        self._is_step = t + n
+        return np.asarray([importance_beta(*self._is_schedule, t + i) for i in range(n)], dtype=np.float32)
+
+    def _sample(self, replay_buffer):
+        """The training batch of one eager gradient step: with importance sampling on, drawn with this step's beta."""
+        betas = self._next_betas()
+        return replay_buffer.sample() if betas is None else replay_buffer.sample(beta=float(betas[0]))
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
@@ -149,13 +191,17 @@ class EngineAgent:
         eng = self._engine_for(replay_buffer._batch_size)
         prioritized = hasattr(replay_buffer._sampling_distribution, "_tree")
         writeback = bool(getattr(self, "priority_writeback", False))
+        weighted = self.importance_sampling
+        if weighted and not prioritized:
+            raise ValueError("importance-sampling weights (set_importance_sampling) need the prioritized sampling distribution")
         g = self._graphed
         if (g is None or g.rb is not replay_buffer or g.eng is not eng or g.writeback != (writeback and prioritized)
-                or getattr(g, "key", None) != key or g.S != steps):
+                or g.weighted != weighted or getattr(g, "key", None) != key or g.S != steps):
             from slimdqn._graph import GraphedUpdate
 
             self._drop_graph()
-            g = self._graphed = GraphedUpdate(replay_buffer, eng, prioritized, steps_per_graph=steps, writeback=writeback, learn=learn)
+            g = self._graphed = GraphedUpdate(replay_buffer, eng, prioritized, steps_per_graph=steps, writeback=writeback, learn=learn,
+                                              weighted=weighted)
             g.key = key
             self._captures = getattr(self, "_captures", 0) + 1
         return g
@@ -188,24 +234,27 @@ class EngineAgent:
 
     # ------------------------------------------------------------------ batches
     def _c_batch(self, eng: QNetEngine, samples):
+        weights = getattr(samples, "weights", None)  # importance-sampling weights of the draw, when the batch carries them
         if hasattr(samples, "frame_ids") and self.architecture_type == "fc":
             # device replay of vector observations (LunarLander): the stored float32 bytes come back as (B, d) rows
             return eng.make_batch(state=samples.state, next_state=samples.next_state, action=samples.action, reward=samples.reward,
-                                  terminal=samples.is_terminal)
+                                  terminal=samples.is_terminal, loss_weights=weights)
         if hasattr(samples, "frame_ids"):  # DeviceBatch from the device replay
             return eng.make_batch(
                 frames=samples.frames, frame_stride=samples.frame_stride, frame_ids=samples.frame_ids,
-                action=samples.action, reward=samples.reward, terminal=samples.is_terminal,
+                action=samples.action, reward=samples.reward, terminal=samples.is_terminal, loss_weights=weights,
             )
         dev = eng.device
         as_t = lambda x, dt: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(dev).to(dt).contiguous()
+        if weights is not None:
+            weights = as_t(weights, torch.float32)
         action = as_t(samples.action, torch.int32)
         reward = as_t(samples.reward, torch.float32)
         terminal = as_t(samples.is_terminal, torch.uint8)
         if self.architecture_type == "fc":
             st = as_t(samples.state, torch.float32).reshape(len(action), -1)
             nx = as_t(samples.next_state, torch.float32).reshape(len(action), -1)
-            return eng.make_batch(state=st, next_state=nx, action=action, reward=reward, terminal=terminal)
+            return eng.make_batch(state=st, next_state=nx, action=action, reward=reward, terminal=terminal, loss_weights=weights)
         st = as_t(samples.state, torch.uint8)
         nx = as_t(samples.next_state, torch.uint8)
         B, h, w, stack = st.shape
@@ -214,7 +263,8 @@ class EngineAgent:
         _hip.check(
             eng.lib.isdqn_replay_deinterleave(_hip.ptr(st), _hip.ptr(nx), h, w, stack, B, _hip.ptr(planes), _hip.ptr(ids), _hip.stream_ptr(dev))
         )
-        return eng.make_batch(frames=planes, frame_stride=h * w, frame_ids=ids, action=action, reward=reward, terminal=terminal)
+        return eng.make_batch(frames=planes, frame_stride=h * w, frame_ids=ids, action=action, reward=reward, terminal=terminal,
+                              loss_weights=weights)
 
     @staticmethod
     def _batch_len(samples) -> int:

@@ -39,7 +39,7 @@ class AnalysisDQN(iSDQN):
     # ------------------------------------------------------------------ analysisdqn.py:63-121
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
-            batch_samples = replay_buffer.sample()
+            batch_samples = self._sample(replay_buffer)
             batch_samples_eval = replay_buffer.sample()
             (self.params, self.optimizer_state, losses, churn_train, churn_eval, cos_is_tb, cos_tf_tb) = self.learn_on_batch(
                 self.params, self.target_params, self.optimizer_state, batch_samples, batch_samples_eval)

@@ -61,10 +61,12 @@ class DQN(EngineAgent):
             eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
             g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target), key=target.data_ptr())
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
-                g.run()
+                g.run(self._next_betas(g.S))
                 return
-            batch_samples = replay_buffer.sample()
+            batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.target_params, self.optimizer_state, batch_samples)
+            if getattr(self, "priority_writeback", False) and hasattr(replay_buffer, "update_device"):  # (as the captured step does)
+                replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_loss += loss` (dqn.py:47) happens on the device inside the step
 
     def update_target_params(self, step: int):

@@ -92,7 +92,7 @@ class iSDQN(EngineAgent):
                 self.update_online_params(0, replay_buffer)
             return
         for _ in range(n_steps // g.S):
-            g.run()
+            g.run(self._next_betas(g.S))
 
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
@@ -102,9 +102,9 @@ class iSDQN(EngineAgent):
             else:
                 g = self._graphed_update(replay_buffer)
             if g is not None:
-                g.run()  # same draws, same kernels, same bits as the eager branch below (tests/test_gpu_graphed_update.py)
+                g.run(self._next_betas(g.S))  # same draws, same kernels, same bits as the eager branch below (tests/test_gpu_graphed_update.py)
                 return
-            batch_samples = replay_buffer.sample()
+            batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
             if self.priority_writeback and hasattr(replay_buffer, "update_device"):
                 replay_buffer.update_device(batch_samples, self._engine.priorities)

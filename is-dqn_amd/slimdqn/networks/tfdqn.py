@@ -52,9 +52,9 @@ class TFDQN(EngineAgent):
         if step % self.data_to_update == 0:
             g = self._graphed_update(replay_buffer)
             if g is not None:
-                g.run()  # same draws, same kernels, same bits as the eager branch below
+                g.run(self._next_betas(g.S))  # same draws, same kernels, same bits as the eager branch below
                 return
-            batch_samples = replay_buffer.sample()
+            batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
 
     def update_target_params(self, step: int):

@@ -61,8 +61,9 @@ class ReplayElement:
 class DeviceBatch:
     """A sampled batch (ReplayElement fields, replay_buffer.py:198-213) living on the GPU."""
 
-    def __init__(self, rb: "ReplayBuffer", indices, frame_ids, action, reward, is_terminal):
+    def __init__(self, rb: "ReplayBuffer", indices, frame_ids, action, reward, is_terminal, weights=None):
         self._rb = rb
+        self.weights = weights  # float32 [B] importance-sampling weights (prioritized sampling with a beta), else None
         self.indices = indices  # dense sampler indices (= sum-tree leaves), int32 [B]
         self.frame_ids = frame_ids  # int32 [B][2*stack]
         self.action = action  # int32 [B]
@@ -422,15 +423,22 @@ class ReplayBuffer:
                 for f in old_ids:
                     self._unref(int(f))
 
-    def sample(self, size=None) -> DeviceBatch:
+    def sample(self, size=None, beta=None) -> DeviceBatch:
+        """``beta`` (prioritized sampling only; python float or device float32 scalar): the batch also carries the
+        importance-sampling weights of its draws (``DeviceBatch.weights``)."""
         assert self.add_count, ValueError("No samples in replay buffer!")
         if size is None:
             size = self._batch_size
         self._flush()
+        if beta is not None:
+            if not hasattr(self._sampling_distribution, "sample_weighted_device"):
+                raise ValueError("importance-sampling weights (beta) need the prioritized sampling distribution")
+            indices, weights = self._sampling_distribution.sample_weighted_device(size, beta)
+            return self.gather(indices, weights=weights)
         indices = self._sampling_distribution.sample_device(size)
         return self.gather(indices)
 
-    def gather(self, indices: torch.Tensor) -> DeviceBatch:
+    def gather(self, indices: torch.Tensor, weights: torch.Tensor | None = None) -> DeviceBatch:
         """Rows of the element table for dense sampler indices (device int32)."""
         if self._lib is None:
             raise RuntimeError("ReplayBuffer.sample needs the HIP path (device='cuda:N'); there is no CPU fallback")
@@ -448,7 +456,7 @@ class ReplayBuffer:
             ),
             "isdqn_replay_gather_rows",
         )
-        return DeviceBatch(self, indices, ids, action, reward, terminal)
+        return DeviceBatch(self, indices, ids, action, reward, terminal, weights)
 
     def update(self, keys, **kwargs: Any) -> None:
         self._sampling_distribution.update(keys, **kwargs)

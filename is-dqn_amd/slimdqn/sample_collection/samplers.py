@@ -276,6 +276,16 @@ class PrioritizedSamplingDistribution(UniformSamplingDistribution):
         self.flush()
         return self._tree.query_device(pu["dev"][k], unit=True)
 
+    def sample_weighted_device(self, size: int, beta):
+        """``sample_device`` plus the importance-sampling weights (p_min / p_i)^beta of the drawn leaves (float32 [size]; the
+        definition lives in include/isdqn_hip.h), from the same launch.  ``beta``: a python float or a device float32 scalar.
+        Consumes the generator exactly as ``sample_device`` does."""
+        units = self._next_units(size)
+        self.flush()
+        weights = torch.empty(size, dtype=torch.float32, device=self._tree.device)
+        indices = self._tree.query_device(units, unit=True, beta=beta, weights_out=weights)
+        return indices, weights
+
     def _next_units(self, size: int) -> torch.Tensor:
         pu = getattr(self, "_pu", None)
         if pu is None or pu["size"] != size or pu["next"] >= self.PREFETCH:

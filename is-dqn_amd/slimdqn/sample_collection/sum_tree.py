@@ -51,12 +51,33 @@ class SumTree:
             "isdqn_tree_set",
         )
 
-    def query_device(self, targets: torch.Tensor, out: torch.Tensor | None = None, unit: bool = False) -> torch.Tensor:
-        """targets float64 [n] on the device (``unit``: draws in [0,1) scaled by the root on the device)."""
+    def query_device(self, targets: torch.Tensor, out: torch.Tensor | None = None, unit: bool = False, beta=None,
+                     weights_out: torch.Tensor | None = None, leaf_out: torch.Tensor | None = None) -> torch.Tensor:
+        """targets float64 [n] on the device (``unit``: draws in [0,1) scaled by the root on the device).
+        ``beta`` (a device float32 scalar tensor, or a python float): the same launch also writes the importance-sampling
+        weights (p_min / p_i)^beta of the drawn leaves (include/isdqn_hip.h: isdqn_tree_query_weighted) into ``weights_out``
+        (float32 [n], required) and the leaf values into ``leaf_out`` (float64
+        [n], optional); n is then limited to ISDQN_TREE_MAX_BATCH."""
         assert targets.dtype == torch.float64
         n = int(targets.numel())
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=self.device)
+        if beta is not None:
+            if not torch.is_tensor(beta):
+                beta = torch.tensor([float(beta)], dtype=torch.float32).to(self.device)
+            assert beta.dtype == torch.float32 and beta.numel() == 1
+            assert weights_out is not None, "beta needs weights_out"
+            assert weights_out.dtype == torch.float32 and weights_out.numel() == n
+            assert leaf_out is None or (leaf_out.dtype == torch.float64 and leaf_out.numel() == n)
+            _hip.check(
+                self._lib.isdqn_tree_query_weighted(
+                    _hip.ptr(self._nodes_dev), self._depth, _hip.ptr(targets), n, 1 if unit else 0, _hip.ptr(beta), _hip.ptr(out),
+                    _hip.ptr(leaf_out), _hip.ptr(weights_out), _hip.ptr(self._status), _hip.stream_ptr(self.device),
+                ),
+                "isdqn_tree_query_weighted",
+            )
+            return out
+        assert weights_out is None and leaf_out is None, "weights_out / leaf_out need beta"
         _hip.check(
             self._lib.isdqn_tree_query(
                 _hip.ptr(self._nodes_dev), self._depth, _hip.ptr(targets), n, 1 if unit else 0, _hip.ptr(out),

@@ -66,7 +66,8 @@ def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, g
     if arch == "fc":
         d = int(np.prod(obs))
         st, nx = dev(rng.normal(size=(B, d)).astype(np.float32)), dev(rng.normal(size=(B, d)).astype(np.float32))
-        batch = eng.make_batch(state=st, next_state=nx, action=action, reward=reward, terminal=terminal)
+        inputs = dict(state=st, next_state=nx)
+        batch = eng.make_batch(**inputs, action=action, reward=reward, terminal=terminal)
         fwd = dict(obs=torch.cat((st, nx)).contiguous(), n_rows=2 * B)
         one = dict(obs=st[:1].contiguous())
         extra += [st, nx, fwd["obs"], one["obs"]]
@@ -78,7 +79,8 @@ def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, g
         ids_np[rng.random(ids_np.shape) < 0.1] = -1
         ids = dev(ids_np)
         flat = dev(np.concatenate([ids_np[:, :stack], ids_np[:, stack:]], 0))
-        batch = eng.make_batch(frames=frames, frame_stride=h * w, frame_ids=ids, action=action, reward=reward, terminal=terminal)
+        inputs = dict(frames=frames, frame_stride=h * w, frame_ids=ids)
+        batch = eng.make_batch(**inputs, action=action, reward=reward, terminal=terminal)
         fwd = dict(frames=frames, frame_stride=h * w, frame_ids=flat, n_rows=2 * B)
         one = dict(frames=frames, frame_stride=h * w, frame_ids=flat[:1].contiguous())
         extra += [frames, ids, flat, one["frame_ids"]]
@@ -107,6 +109,15 @@ def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, g
     if target and not bn:
         eng.learn_on_batch_target(batch, tparams)
         eng.loss_on_batch_target(batch, tparams)
+    # importance-sampling weights (isdqn_batch.loss_weights: site 29 in the head chain), last so that a case's first violation stays
+    # what it was: the same batch with a registered weights tensor through learn / loss / gradient-only
+    weights = dev(np.random.default_rng(1).uniform(0.1, 1.0, B).astype(np.float32))
+    wbatch = eng.make_batch(**inputs, action=action, reward=reward, terminal=terminal, loss_weights=weights)
+    register(tensors + [q, weights], fresh=False)
+    eng.learn_on_batch(wbatch)
+    eng.loss_on_batch(wbatch)
+    if grad:
+        eng.grad_on_batch(wbatch, grad_out)
     report(name, omit)
     del eng
     torch.cuda.empty_cache()
