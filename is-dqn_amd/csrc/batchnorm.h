@@ -364,18 +364,9 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
     // ---- targets, loss, dL/dq (rows [0, B); the next-state rows of dL/dq are zero: stop_gradient, isdqn.py:99) ----
     float* qv = q_values ? q_values : ws + P.qv_off;
     float* tg = targets ? targets : ws + P.tg_off;
-    const int n_blk = ceil_div(B, TD_ROWS);
-    float* loss_part = ws + P.lpart_off;
-    float* dbh_part = loss_part + (int64_t)n_blk * K;
-    hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K, on0, tg0, P.n_actions, P.nha_p,
-                       batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta, learn ? ws + P.dout_off : nullptr, qv, tg,
-                       priorities,
-                       loss_part, dbh_part);
-    ISDQN_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nha_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nha_p,
-                       losses, loss_accum, learn ? ws + P.dbh_off : nullptr, (learn && update) ? adam_count : nullptr, cfg->adam_b1, cfg->adam_b2,
-                       ws + P.adam_tab_off);
-    ISDQN_HIP_CHECK(hipGetLastError());
+    // (BatchNorm networks never have histogram heads: the TD loss, and nlog_p == nha_p)
+    rc = loss_and_finalize(P, cfg, ws, batch, K, on0, tg0, learn, (learn && update) ? adam_count : nullptr, qv, tg, priorities, losses, loss_accum, st);
+    if (rc) return rc;
     if (batch->priorities_ready != nullptr) ISDQN_HIP_CHECK(hipEventRecord((hipEvent_t)batch->priorities_ready, st));
     if (!learn) return ISDQN_OK;
     if (Bb > B) {
@@ -385,12 +376,7 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
     }
 
     // ---- backward over all N2 rows ----
-    std::vector<AdamEntry> entries;
-    auto entry = [&](int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
-        AdamEntry e;
-        e.p_off = p_off; e.size = size; e.g = g; e.n_slabs = n_slabs; e.slab_stride = stride; e.block_start = 0;
-        entries.push_back(e);
-    };
+    AdamList adam;
     float* da = ws + P.da_off;
     const float* dz_cur = ws + P.dout_off;
     int dz_ld = P.nha_p;
@@ -403,17 +389,13 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
             const BnSite* site = bn_site_of(P, i);
             rc = bn_site_backward(*site, params, ws, da, Bb, true, st);
             if (rc) return rc;
-            entry(site->scale_off, site->G_p, ws + site->s2_off, 1, 0);
-            entry(site->bias_off, site->G_p, ws + site->s1_off, 1, 0);
+            adam.add(site->scale_off, site->G_p, ws + site->s2_off, 1, 0);
+            adam.add(site->bias_off, site->G_p, ws + site->s1_off, 1, 0);
             const int rows = l.kind != 1 ? Bb * l.npix : Bb;
             int nb = 0;
             rc = ln_bwd(l, params, da, ws + l.z_off, rows, ws + l.dz_off, ws + l.part_off, &nb, st);
             if (rc) return rc;
-            if (l.has_ln) {
-                entry(l.g_off, l.out_p, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
-                entry(l.be_off, l.out_p, ws + l.part_off + l.out_p, nb, 3 * (int64_t)l.out_p);
-            }
-            if (l.b_off >= 0) entry(l.b_off, l.out_p, ws + l.part_off + 2 * l.out_p, nb, 3 * (int64_t)l.out_p);  // (the impala torso has no bias of its own)
+            add_ln_bias_entries(adam, l, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
             dz_cur = ws + l.dz_off;
             dz_ld = l.out_p;
             if (l.kind == 2) {  // the impala torso: its own backward and optimizer launches over the 2B rows
@@ -422,69 +404,32 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
                 continue;
             }
         } else {
-            entry(l.b_off, l.out_p, ws + P.dbh_off, 1, 0);
+            adam.add(l.b_off, l.out_p, ws + P.dbh_off, 1, 0);
         }
         // data gradient w.r.t. this layer's input (the BatchNorm output below); the first convolution's feeds the input site
         if (i > 0 || (l.kind == 0 && below != nullptr)) {
-            if (l.kind == 0) {
-                const bool small = l.cin_p <= 32;
-                if (x3) rc = small ? launch_conv_dgrad<32, 3>(l, wmir, dz_cur, da, Bb, st) : launch_conv_dgrad<64, 3>(l, wmir, dz_cur, da, Bb, st);
-                else rc = small ? launch_conv_dgrad<32, 1>(l, wmir, dz_cur, da, Bb, st) : launch_conv_dgrad<64, 1>(l, wmir, dz_cur, da, Bb, st);
-            } else {
-                MatSrc A{dz_cur, dz_ld, Bb, l.out_p, 1};
-                MatSrc Bm{wmir + l.w_off, l.in_p, l.out_f, l.in_p, 1};
-                if (l.is_head) rc = plain_big<false, true, true, false, 2>(x3, A, nullptr, 0, Bm, da, l.in_p, Bb, l.in_p, l.out_p, 1, 0, st);
-                else rc = plain_big<false, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, da, l.in_p, Bb, l.in_p, l.out_p, 1, 0, st);
-            }
+            rc = l.kind == 0 ? conv_dgrad(l, x3, wmir, dz_cur, da, Bb, st) : dense_dgrad(l, x3, wmir, dz_cur, dz_ld, da, Bb, /*narrow=*/false, st);
             if (rc) return rc;
         }
         // weight gradient -> slabs, summed inside adam_kernel
         int w_slabs;
         if (l.kind == 0) {
-            int img_slabs = 0;
-            rc = conv_wgrad_img(l, x3, in, act_in, dz_cur, ws + l.gw_off, Bb, st, &img_slabs);
-            if (rc) return rc;
-            if (img_slabs) {
-                w_slabs = img_slabs;
-            } else {
-                rc = x3 ? launch_conv_wgrad<3, false>(l, in, act_in, dz_cur, ws + l.gw_off, Bb, st)
-                        : launch_conv_wgrad<1, false>(l, in, act_in, dz_cur, ws + l.gw_off, Bb, st);
-                w_slabs = conv_wgrad_slabs(l, Bb);
-            }
+            rc = conv_wgrad(l, x3, in, act_in, dz_cur, ws + l.gw_off, Bb, st, &w_slabs);
         } else {
-            MatSrc A{dz_cur, dz_ld, Bb, l.out_p, 1};
-            MatSrc Bm = l.in_unpadded_ld ? MatSrc{in.obs, l.in_unpadded_ld, Bb, l.in_f, 0} : MatSrc{act_in, l.in_p, Bb, l.in_p, 1};
             w_slabs = effective_splits(Bb, l.gw_slabs);
-            if (l.in_unpadded_ld)
-                rc = plain_big<true, true, false, false, DZ_S8>(x3, A, nullptr, 0, Bm, ws + l.gw_off, l.in_p, l.out_p, l.in_p, Bb, l.gw_slabs, l.w_size, st);
-            else if (l.is_head)
-                rc = plain_big<true, true, true, false, 2>(x3, A, nullptr, 0, Bm, ws + l.gw_off, l.in_p, l.out_p, l.in_p, Bb, l.gw_slabs, l.w_size, st);
-            else
-                rc = plain_big<true, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, ws + l.gw_off, l.in_p, l.out_p, l.in_p, Bb, l.gw_slabs, l.w_size, st);
+            rc = dense_wgrad(l, x3, in, act_in, dz_cur, dz_ld, ws + l.gw_off, Bb, st);
         }
         if (rc) return rc;
-        entry(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size);
+        adam.add(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size);
         if (i == 0 && below != nullptr) {  // scale / bias of the input site (dqn.py:52-53): sums only, nothing lies below it
             rc = bn_site_backward(*below, params, ws, da, Bb, false, st);
             if (rc) return rc;
-            entry(below->scale_off, below->G_p, ws + below->s2_off, 1, 0);
-            entry(below->bias_off, below->G_p, ws + below->s1_off, 1, 0);
+            adam.add(below->scale_off, below->G_p, ws + below->s2_off, 1, 0);
+            adam.add(below->bias_off, below->G_p, ws + below->s1_off, 1, 0);
         }
     }
-    for (size_t e0 = 0; e0 < entries.size(); e0 += ADAM_MAX_ENTRIES) {
-        AdamTable tab;
-        tab.n = 0;
-        tab.total_blocks = 0;
-        for (size_t e = e0; e < entries.size() && e < e0 + ADAM_MAX_ENTRIES; ++e) {
-            AdamEntry& t = tab.e[tab.n++];
-            t = entries[e];
-            t.block_start = tab.total_blocks;
-            tab.total_blocks += (int)((t.size + 63) / 64);
-        }
-        hipLaunchKernelGGL(adam_kernel, dim3(tab.total_blocks), dim3(256), 0, st, tab, params, adam_m, adam_v, ws + P.adam_tab_off, cfg->learning_rate,
-                           cfg->adam_b1, cfg->adam_b2, cfg->adam_eps, grad_out, ws + P.wsplit_off, update ? 1 : 0);
-        ISDQN_HIP_CHECK(hipGetLastError());
-    }
+    rc = adam.launch(st, P, cfg, params, adam_m, adam_v, ws, grad_out, update);
+    if (rc) return rc;
     if (update)  // params["batch_stats"] = batch_stats (isdqn.py:87-88): the running averages the forward's flax modules produced
         for (int s = 0; s < P.n_bn; ++s) {
             const BnSite& b = P.bns[s];

@@ -374,17 +374,12 @@ static int impala_forward(const Plan& P, bool x3, const float* params, const flo
 static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, float* params, float* adam_m, float* adam_v, const float* wmir,
                            float* ws, int B, float* grad_out, bool update, hipStream_t st, bool bn = false) {
     const Layer& L0 = P.L[0];
-    std::vector<AdamEntry> entries;
-    auto entry = [&](int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
-        AdamEntry e;
-        e.p_off = p_off; e.size = size; e.g = g; e.n_slabs = n_slabs; e.slab_stride = stride; e.block_start = 0;
-        entries.push_back(e);
-    };
+    AdamList adam;
     const NetInput none{nullptr, 0, nullptr, 0, nullptr, nullptr, 0};
     auto wgrad = [&](const Layer& c, const float* x_s8, const float* dz_s8) -> int {
         int rc = x3 ? launch_conv_wgrad<3, false>(c, none, x_s8, dz_s8, ws + c.gw_off, B, st)
                     : launch_conv_wgrad<1, false>(c, none, x_s8, dz_s8, ws + c.gw_off, B, st);
-        entry(c.w_off, c.w_size, ws + c.gw_off, conv_wgrad_slabs(c, B), c.w_size);
+        adam.add(c.w_off, c.w_size, ws + c.gw_off, conv_wgrad_slabs(c, B), c.w_size);
         return rc;
     };
     auto dgrad = [&](const Layer& c, const float* dz_s8, float* da) -> int {
@@ -396,7 +391,7 @@ static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, 
         const int nb = imp_blocks(rows);
         hipLaunchKernelGGL(imp_to_s8_kernel, dim3(nb), dim3(256), 0, st, d, mask, rows, Cp, out, part);
         ISDQN_HIP_CHECK(hipGetLastError());
-        entry(b_off, Cp, part, nb, Cp);
+        adam.add(b_off, Cp, part, nb, Cp);
         return ISDQN_OK;
     };
 
@@ -433,8 +428,8 @@ static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, 
             if (bs) {  // through the block's BatchNorm: da becomes the gradient w.r.t. relu([LN](r)) in place
                 rc = bn_site_backward(*bs, params, ws, da, B, true, st);
                 if (rc) return rc;
-                entry(bs->scale_off, bs->G_p, ws + bs->s2_off, 1, 0);
-                entry(bs->bias_off, bs->G_p, ws + bs->s1_off, 1, 0);
+                adam.add(bs->scale_off, bs->G_p, ws + bs->s2_off, 1, 0);
+                adam.add(bs->bias_off, bs->G_p, ws + bs->s1_off, 1, 0);
             }
             const float* g = S.ln_g[b] >= 0 ? params + S.ln_g[b] : nullptr;
             const float* be = S.ln_b[b] >= 0 ? params + S.ln_b[b] : nullptr;
@@ -443,8 +438,8 @@ static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, 
                                ws + S.lnpart_off[b]);
             ISDQN_HIP_CHECK(hipGetLastError());
             if (g != nullptr) {
-                entry(S.ln_g[b], S.C_p, ws + S.lnpart_off[b], nb, 2 * (int64_t)S.C_p);
-                entry(S.ln_b[b], S.C_p, ws + S.lnpart_off[b] + S.C_p, nb, 2 * (int64_t)S.C_p);
+                adam.add(S.ln_g[b], S.C_p, ws + S.lnpart_off[b], nb, 2 * (int64_t)S.C_p);
+                adam.add(S.ln_b[b], S.C_p, ws + S.lnpart_off[b] + S.C_p, nb, 2 * (int64_t)S.C_p);
             }
         }
         const int cq = S.C_p / 4;
@@ -464,24 +459,10 @@ static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, 
         if (b0) {  // scale / bias of the input site (sums only)
             rc = bn_site_backward(*b0, params, ws, da, B, false, st);
             if (rc) return rc;
-            entry(b0->scale_off, b0->G_p, ws + b0->s2_off, 1, 0);
-            entry(b0->bias_off, b0->G_p, ws + b0->s1_off, 1, 0);
+            adam.add(b0->scale_off, b0->G_p, ws + b0->s2_off, 1, 0);
+            adam.add(b0->bias_off, b0->G_p, ws + b0->s1_off, 1, 0);
         }
     }
-    // the optimizer over the torso's tensors (slab / partial sums inside the kernel), a table at a time
-    for (size_t e0 = 0; e0 < entries.size(); e0 += ADAM_MAX_ENTRIES) {
-        AdamTable tab;
-        tab.n = 0;
-        tab.total_blocks = 0;
-        for (size_t e = e0; e < entries.size() && e < e0 + ADAM_MAX_ENTRIES; ++e) {
-            AdamEntry& t = tab.e[tab.n++];
-            t = entries[e];
-            t.block_start = tab.total_blocks;
-            tab.total_blocks += (int)((t.size + 63) / 64);
-        }
-        hipLaunchKernelGGL(adam_kernel, dim3(tab.total_blocks), dim3(256), 0, st, tab, params, adam_m, adam_v, ws + P.adam_tab_off, cfg->learning_rate,
-                           cfg->adam_b1, cfg->adam_b2, cfg->adam_eps, grad_out, ws + P.wsplit_off, update ? 1 : 0);
-        ISDQN_HIP_CHECK(hipGetLastError());
-    }
-    return ISDQN_OK;
+    // the optimizer over the torso's tensors (slab / partial sums inside the kernel)
+    return adam.launch(st, P, cfg, params, adam_m, adam_v, ws, grad_out, update);
 }

@@ -9,7 +9,6 @@
 #include <type_traits>
 #include <vector>
 #include <atomic>
-#include <functional>
 
 #include "conv_img.h"
 #include "conv_u8_pair.h"
@@ -463,7 +462,7 @@ struct HeadChainParams {
 // is instruction-issue bound (a few thousand instructions executed once per wave), and the target / data-gradient /
 // LayerNorm phases scale with S, so few transitions on many workgroups win -- until every one of too many workgroups
 // streams the whole head matrix from L2: S = 1 at B = 256 (20 us; S = 2: 23 us; S = 4 on 256 threads: 22 us before the
-// dense_post fusion), S = 4 at B = 1024 (learn_or_loss picks about 256 workgroups).
+// dense_post fusion), S = 4 at B = 1024 (head_chain_plan picks about 256 workgroups).
 constexpr int HC_MAX_COLS = 4;  // hidden width up to HC_THREADS * 4 (columns per thread: template parameter COLS)
 // Eight waves: the kernel executes a few thousand instructions ONCE per wave, so it is bound by instruction issue and
 // its dependency stalls; two waves per SIMD interleave, and each owns half the K-steps / columns.
@@ -1327,6 +1326,16 @@ static int conv_fwd(const Layer& l, bool x3, const float* params, const float* w
                  : launch_conv_fwd<64, 1, false>(l, params, wmir, in, act_in, n_img, z_img, act, z, st);
 }
 
+// number of slabs launch_plain writes for (K, splits); *steps_per_split: the K steps of each
+static int effective_splits(int K, int splits, int* steps_per_split = nullptr) {
+    int ksteps = ceil_div(K, GEMM_BK);
+    if (splits < 1) splits = 1;
+    if (splits > ksteps) splits = ksteps;
+    int sps = ceil_div(ksteps, splits);
+    if (steps_per_split) *steps_per_split = sps;
+    return ceil_div(ksteps, sps);
+}
+
 // C[split][M][N] = A . B^T over row-major sources.  a_tr/b_tr: the operand is stored [K][rows].
 template <int BM, int BN, int WM, int WN, bool ATR, bool BTR, int PASSES, bool AL, bool A2PART, bool ADAM = false, int S8M = 0>
 static int launch_plain(const MatSrc& A, const float* A2, int a_split, const MatSrc& B, float* C, int ldc, int M,
@@ -1336,21 +1345,9 @@ static int launch_plain(const MatSrc& A, const float* A2, int a_split, const Mat
     if (adam) p.adam = *adam;
     p.A = A; p.B = B; p.A2 = A2; p.a_split = a_split; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
     p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
-    int ksteps = ceil_div(K, GEMM_BK);
-    if (splits < 1) splits = 1;
-    if (splits > ksteps) splits = ksteps;
-    p.steps_per_split = ceil_div(ksteps, splits);
-    p.splits = ceil_div(ksteps, p.steps_per_split);
+    p.splits = effective_splits(K, splits, &p.steps_per_split);
     p.slab_stride = slab_stride;
     return launch_gemm(p, p.tiles_m * p.tiles_n * p.splits, st);
-}
-// number of slabs launch_plain will actually write for (K, splits)
-static int effective_splits(int K, int splits) {
-    int ksteps = ceil_div(K, GEMM_BK);
-    if (splits < 1) splits = 1;
-    if (splits > ksteps) splits = ksteps;
-    int sps = ceil_div(ksteps, splits);
-    return ceil_div(ksteps, sps);
 }
 
 template <bool ATR, bool BTR, bool AL = true, bool A2PART = false, int S8M = 0>
@@ -1678,6 +1675,122 @@ struct HeadSel {
     int on0, tg0, K;
 };
 
+// ---- launch helpers shared by the three learn paths (plain / LayerNorm below, BatchNorm in batchnorm.h, the torso in impala.h) ----
+// `rows`: the rows the gradient flows through (B, or all 2B rows of a BatchNorm network)
+
+// The tensors one stream's optimizer launches update, in launch order: adam_kernel once per ADAM_MAX_ENTRIES of them.
+struct AdamList {
+    std::vector<AdamEntry> e;
+    AdamList() { e.reserve(ADAM_MAX_ENTRIES); }
+    void add(int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
+        e.push_back(AdamEntry{p_off, size, stride, g, n_slabs, 0});
+    }
+    int launch(hipStream_t st, const Plan& P, const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, float* ws, float* grad_out,
+               bool update) const {
+        for (size_t e0 = 0; e0 < e.size(); e0 += ADAM_MAX_ENTRIES) {
+            AdamTable tab;
+            tab.n = 0;
+            tab.total_blocks = 0;
+            for (size_t k = e0; k < e.size() && k < e0 + ADAM_MAX_ENTRIES; ++k) {
+                AdamEntry& t = tab.e[tab.n++];
+                t = e[k];
+                t.block_start = tab.total_blocks;
+                tab.total_blocks += (int)((t.size + 63) / 64);
+            }
+            hipLaunchKernelGGL(adam_kernel, dim3(tab.total_blocks), dim3(256), 0, st, tab, params, adam_m, adam_v, ws + P.adam_tab_off, cfg->learning_rate,
+                               cfg->adam_b1, cfg->adam_b2, cfg->adam_eps, grad_out, ws + P.wsplit_off, update ? 1 : 0);
+            ISDQN_HIP_CHECK(hipGetLastError());
+        }
+        return ISDQN_OK;
+    }
+};
+
+// per-head loss sums and the head-bias gradient (`width` columns) of the P.B transitions from the `n_blk` partial rows a loss kernel left
+// in the workspace; `adam_count` non-null: also the step count and Adam's bias corrections
+static int loss_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, int n_blk, int K, int width, float* losses, float* loss_accum,
+                         bool head_bias_grad, int32_t* adam_count, hipStream_t st) {
+    float* loss_part = ws + P.lpart_off;
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(width, 16)), dim3(256), 0, st, loss_part, loss_part + (int64_t)n_blk * K, n_blk,
+                       P.B, K, width, losses, loss_accum, head_bias_grad ? ws + P.dbh_off : nullptr, adam_count, cfg->adam_b1, cfg->adam_b2,
+                       ws + P.adam_tab_off);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
+// targets, per-transition loss and dL/d(head output) of rows [0, B) from the head outputs of a finished forward (TD loss on the Q rows, or
+// the HL-Gauss loss on the logit rows), then loss_finalize over the head layer's width (nlog_p: nha_p without histogram heads)
+static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, const isdqn_batch* batch, int K, int on0, int tg0, bool learn,
+                             int32_t* adam_count, float* qv, float* tg, double* priorities, float* losses, float* loss_accum, hipStream_t st) {
+    const int B = P.B;
+    const int hl_R = P.hl_nb > 0 ? hl_rows_per_wg(K, P.hl_nb) : 0;
+    const int n_blk = hl_R ? ceil_div(B, hl_R) : ceil_div(B, TD_ROWS);
+    float* loss_part = ws + P.lpart_off;
+    float* dbh_part = loss_part + (int64_t)n_blk * K;
+    if (hl_R)
+        hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.hl_nb * sizeof(float), st, ws + P.logits_off, B, hl_R,
+                           K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
+                           batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n,
+                           learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
+    else
+        hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K,
+                           on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta,
+                           learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return loss_finalize(P, cfg, ws, n_blk, K, P.nlog_p, losses, loss_accum, learn, adam_count, st);
+}
+
+// LayerNorm scale / bias and layer bias of `l` from `n_rows` partial rows of (dgamma, dbeta, dbias) at `part`
+static void add_ln_bias_entries(AdamList& adam, const Layer& l, const float* part, int n_rows, int64_t stride) {
+    if (l.has_ln) {
+        adam.add(l.g_off, l.out_p, part, n_rows, stride);
+        adam.add(l.be_off, l.out_p, part + l.out_p, n_rows, stride);
+    }
+    if (l.b_off >= 0) adam.add(l.b_off, l.out_p, part + 2 * l.out_p, n_rows, stride);  // (the impala torso has no bias of its own)
+}
+
+// generic data gradient of conv layer `l`: da [rows][hin][win][cin_p] fp32
+static int conv_dgrad(const Layer& l, bool x3, const float* wmir, const float* dz, float* da, int rows, hipStream_t st) {
+    const bool small = l.cin_p <= 32;
+    if (x3) return small ? launch_conv_dgrad<32, 3>(l, wmir, dz, da, rows, st) : launch_conv_dgrad<64, 3>(l, wmir, dz, da, rows, st);
+    return small ? launch_conv_dgrad<32, 1>(l, wmir, dz, da, rows, st) : launch_conv_dgrad<64, 1>(l, wmir, dz, da, rows, st);
+}
+
+// data gradient of dense layer `l`: da[b][in_p] = sum_o dz[b][o] * W[o][in_p]  (dz: the fp32 dL/dq of the head, S8 for a hidden layer)
+// `narrow`: 128 x 64 tiles
+static int dense_dgrad(const Layer& l, bool x3, const float* wmir, const float* dz, int dz_ld, float* da, int rows, bool narrow, hipStream_t st) {
+    MatSrc A{dz, dz_ld, rows, l.out_p, 1};
+    MatSrc Bm{wmir + l.w_off, l.in_p, l.out_f, l.in_p, 1};
+    if (l.is_head)
+        return narrow ? plain_narrow<false, true, 2>(x3, A, Bm, da, l.in_p, rows, l.in_p, l.out_p, 1, 0, st)
+                      : plain_big<false, true, true, false, 2>(x3, A, nullptr, 0, Bm, da, l.in_p, rows, l.in_p, l.out_p, 1, 0, st);
+    return narrow ? plain_narrow<false, true, DZ_S8 | 2>(x3, A, Bm, da, l.in_p, rows, l.in_p, l.out_p, 1, 0, st)
+                  : plain_big<false, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, da, l.in_p, rows, l.in_p, l.out_p, 1, 0, st);
+}
+
+// weight gradient of conv layer `l` into its slabs (image-resident kernel where the layer qualifies); *n_slabs: the slabs written
+// (l.is_u8 only on the first layer of a cnn without BatchNorm, net_plan.h)
+static int conv_wgrad(const Layer& l, bool x3, const NetInput& in, const float* act_in, const float* dz, float* slabs, int rows, hipStream_t st,
+                      int* n_slabs) {
+    int rc = conv_wgrad_img(l, x3, in, act_in, dz, slabs, rows, st, n_slabs);
+    if (rc || *n_slabs) return rc;
+    *n_slabs = conv_wgrad_slabs(l, rows);
+    if (l.is_u8) return x3 ? launch_conv_wgrad<2, true>(l, in, act_in, dz, slabs, rows, st) : launch_conv_wgrad<1, true>(l, in, act_in, dz, slabs, rows, st);
+    return x3 ? launch_conv_wgrad<3, false>(l, in, act_in, dz, slabs, rows, st) : launch_conv_wgrad<1, false>(l, in, act_in, dz, slabs, rows, st);
+}
+
+// weight gradient of dense layer `l` into its effective_splits(rows, l.gw_slabs) slabs:
+// dW[out][in_p] = sum_b dz[b][out] * a[b][in_p], both operands stored [K = b][rows]
+static int dense_wgrad(const Layer& l, bool x3, const NetInput& in, const float* act_in, const float* dz, int dz_ld, float* slabs, int rows,
+                       hipStream_t st) {
+    const MatSrc A{dz, dz_ld, rows, l.out_p, 1};
+    const MatSrc Bm = l.in_unpadded_ld ? MatSrc{in.obs, l.in_unpadded_ld, rows, l.in_f, 0} : MatSrc{act_in, l.in_p, rows, l.in_p, 1};
+    if (l.in_unpadded_ld)  // fc first layer: caller's fp32 observations
+        return plain_big<true, true, false, false, DZ_S8>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);
+    if (l.is_head)  // dL/dq is fp32, the hidden activations are S8
+        return plain_big<true, true, true, false, 2>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);
+    return plain_big<true, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);
+}
+
 #include "impala.h"
 #include "batchnorm.h"
 
@@ -1884,12 +1997,488 @@ static SideStream* side_stream() {
     while ((st = s.state.load(std::memory_order_acquire)) == 1) {}  // another thread is creating it
     return st == 2 ? &s : nullptr;
 }
+static hipEvent_t next_event(SideStream* ss) { return ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % (unsigned)ss->n_ev]; }
 // make `waiter` wait for everything enqueued so far on `signaller`
 static int chain(SideStream* ss, hipStream_t signaller, hipStream_t waiter) {
-    hipEvent_t e = ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % (unsigned)ss->n_ev];
+    hipEvent_t e = next_event(ss);
     ISDQN_HIP_CHECK(hipEventRecord(e, signaller));
     ISDQN_HIP_CHECK(hipStreamWaitEvent(waiter, e, 0));
     return ISDQN_OK;
+}
+
+// What a learn / loss / gradient-only call on a network without BatchNorm fixes before its first launch (learn_or_loss).
+struct LearnCtx {
+    const Plan& P;
+    const isdqn_net_config* cfg;
+    const isdqn_batch* batch;
+    float *params, *adam_m, *adam_v;
+    int32_t* adam_count;
+    const float* target_params;
+    float *losses, *loss_accum, *qv, *tg;  // qv / tg: the caller's q_values / targets, or their workspace regions
+    double* priorities;
+    float* ws;
+    float* grad_out;
+    hipStream_t st;  // the caller's stream
+    bool learn, update, x3;
+    int B, K, on0, tg0;
+    NetInput in;
+    SideStream* ss = nullptr;   // learn steps: the weight-gradient stream (nullptr: everything runs on the caller's stream)
+    hipStream_t wst = nullptr;  // stream of the weight gradients: ss->stream, or st
+    int hc_S = 0, hc_wg = 0;    // head chain (head_chain_plan): transitions per workgroup, workgroups; 0 = generic loss and head backward
+    const float* wmir() const { return ws + P.wsplit_off; }
+    const Layer& hid() const { return P.L[P.n_layers >= 2 ? P.n_layers - 2 : 0]; }
+    const Layer& head() const { return P.L[P.n_layers - 1]; }
+};
+
+// head chain eligibility (learn steps on the plan's own heads): last hidden layer dense + ReLU, widths within the kernel's limits
+static void head_chain_plan(LearnCtx& c, bool plan_heads) {
+    const Plan& P = c.P;
+    const Layer& hid = c.hid();
+    static const bool hc_disabled = ISDQN_DEV_ENV("ISDQN_NO_HEAD_CHAIN");
+    // (histogram heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
+    if (!(c.learn && c.update && plan_heads && !hc_disabled && c.target_params == nullptr && P.hl_nb == 0 && P.n_layers >= 2 && hid.kind == 1 &&
+          !hid.is_head && hid.has_relu && hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0))
+        return;
+    // transitions per workgroup: the per-transition phases scale with S (the kernel is instruction-issue bound) while
+    // every workgroup streams the whole head matrix from L2, so S follows the batch: about 256 workgroups
+    const int S = c.B >= 1024 ? 4 : c.B >= 512 ? 2 : 1;
+    const int n_wg = ceil_div(c.B, S);
+    if (n_wg <= hid.part_rows && S * c.K <= HC_THREADS && head_chain_lds_bytes(hid.out_p, P.nha_p, c.K, c.x3 ? 3 : 1, S) <= 150 * 1024) {
+        c.hc_S = S;
+        c.hc_wg = n_wg;
+    }
+}
+
+static int learn_forward(const LearnCtx& c) {
+    const Plan& P = c.P;
+    const isdqn_batch* batch = c.batch;
+    float* ws = c.ws;
+    const int B = c.B;
+    int rc;
+    if (c.target_params != nullptr) {
+        // DQN (dqn.py:74-88): the next states go through the TARGET parameters, the states through the online ones: two
+        // forwards of B images each over the same workspace, q rows [B, 2B) first, then rows [0, B) (+ z of every layer)
+        const int stack = c.cfg->arch != ISDQN_ARCH_FC ? c.cfg->obs_c : 0;
+        NetInput nx{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->next_state, nullptr, 0, 2 * stack, stack};
+        rc = refresh_mirror(P, c.target_params, ws, c.st);
+        if (rc) return rc;
+        rc = net_forward(P, c.x3, c.target_params, nx, B, 0, ws, ws + P.out_off + (int64_t)B * P.nlog_p, c.st);
+        if (rc) return rc;
+        rc = refresh_mirror(P, c.params, ws, c.st);
+        if (rc) return rc;
+        NetInput on{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->state, nullptr, 0, 2 * stack, 0};
+        return net_forward(P, c.x3, c.params, on, B, B, ws, ws + P.out_off, c.st);
+    }
+    // The optimizer writes the updated parameters in both forms, so a learn step leaves the mirror current; a caller
+    // that chains learn steps on one workspace with nothing else writing `params` in between says so
+    // (ISDQN_BATCH_MIRROR_CURRENT: the captured multi-step graphs) and the refresh is skipped.
+    if (!(batch->flags & ISDQN_BATCH_MIRROR_CURRENT)) {
+        rc = refresh_mirror(P, c.params, ws, c.st);
+        if (rc) return rc;
+    }
+    // forward on concat(state, next_state) (isdqn.py:95); the head chain takes over at the last hidden layer's split-K slabs
+    return net_forward(P, c.x3, c.params, c.in, P.N2, B, ws, ws + P.out_off, c.st, c.hc_S ? P.n_layers - 1 : -1, c.hc_S ? P.n_layers - 2 : -1);
+}
+
+static int launch_head_chain(const LearnCtx& c) {
+    const Plan& P = c.P;
+    const Layer &hid = c.hid(), &head = c.head();
+    float* ws = c.ws;
+    HeadChainParams hp;
+    hp.act = ws + hid.act_off; hp.z = ws + hid.z_off;
+    hp.slabs = ws + P.slab_off;
+    hp.n_slabs = effective_splits(hid.in_unpadded_ld ? hid.in_f : hid.K, hid.fwd_splits);
+    hp.slab_stride = hid.out_p;
+    hp.row_pitch = (int64_t)hp.n_slabs * hid.out_p;
+    hp.hbias = c.params + hid.b_off;
+    hp.W = c.params + head.w_off; hp.bias = c.params + head.b_off;
+    hp.gamma = hid.has_ln ? c.params + hid.g_off : nullptr;
+    hp.beta = hid.has_ln ? c.params + hid.be_off : nullptr;
+    hp.B = c.B; hp.S = c.hc_S; hp.F = hid.out_f; hp.Fp = hid.out_p; hp.O = P.nha; hp.Op = P.nha_p; hp.K = c.K; hp.oh = P.oh;
+    hp.A = P.n_actions;
+    hp.action = c.batch->action; hp.reward = c.batch->reward; hp.terminal = c.batch->terminal;
+    hp.loss_weights = c.batch->loss_weights;
+    hp.gamma_n = c.cfg->gamma_n; hp.huber_delta = c.cfg->huber_delta;
+    hp.dout = ws + P.dout_off; hp.dz = ws + hid.dz_off; hp.part = ws + hid.part_off;
+    hp.q_values = c.qv; hp.targets = c.tg; hp.priorities = c.priorities;
+    hp.loss_part = ws + P.lpart_off; hp.dbh_part = hp.loss_part + (int64_t)c.hc_wg * c.K;
+    hp.adam_count = c.adam_count; hp.b1 = c.cfg->adam_b1; hp.b2 = c.cfg->adam_b2; hp.adam_consts = ws + P.adam_tab_off;
+    hp.stamps = stamps_for("head_chain");
+    const int lds = head_chain_lds_bytes(hid.out_p, P.nha_p, c.K, c.x3 ? 3 : 1, c.hc_S);
+    const int cols = ceil_div(hid.out_p, HC_THREADS) <= 1 ? 1 : ceil_div(hid.out_p, HC_THREADS) <= 2 ? 2 : 4;
+    auto launch_hc = [&](auto kern, int slot) -> int {
+        static LdsConfigured configured[18];
+        if (int rc2 = ensure_dynamic_lds(kern, lds, configured[slot])) return rc2;
+        ISDQN_REPORT_OCCUPANCY(kern, HC_THREADS, lds, c.hc_wg);
+        hipLaunchKernelGGL(kern, dim3(c.hc_wg), dim3(HC_THREADS), lds, c.st, hp);
+        ISDQN_HIP_CHECK(hipGetLastError());
+        return ISDQN_OK;
+    };
+    auto by_cols = [&](auto passes_c, auto s_c, int base) -> int {
+        constexpr int PS = decltype(passes_c)::value, SS = decltype(s_c)::value;
+        return cols == 1 ? launch_hc(&head_chain_kernel<PS, 1, SS>, base) : cols == 2 ? launch_hc(&head_chain_kernel<PS, 2, SS>, base + 1)
+                                                                        : launch_hc(&head_chain_kernel<PS, 4, SS>, base + 2);
+    };
+    auto by_s = [&](auto passes_c, int base) -> int {
+        return c.hc_S == 1 ? by_cols(passes_c, std::integral_constant<int, 1>{}, base)
+             : c.hc_S == 2 ? by_cols(passes_c, std::integral_constant<int, 2>{}, base + 3)
+                           : by_cols(passes_c, std::integral_constant<int, 4>{}, base + 6);
+    };
+    return c.x3 ? by_s(std::integral_constant<int, 3>{}, 0) : by_s(std::integral_constant<int, 1>{}, 9);
+}
+
+// The two small kernels that only need the head chain's outputs: the loss / head-bias sums of its per-workgroup partials, and the
+// head's weight gradient (dL/dq fp32, hidden activations S8)
+static int head_chain_sums(const LearnCtx& c, hipStream_t s) {
+    return loss_finalize(c.P, c.cfg, c.ws, c.hc_wg, c.K, c.P.nha_p, c.losses, c.loss_accum, true, nullptr, s);
+}
+static int head_chain_tail(const LearnCtx& c, hipStream_t s) {
+    if (int rc = head_chain_sums(c, s)) return rc;
+    const Layer& head = c.head();
+    return dense_wgrad(head, c.x3, c.in, c.ws + c.hid().act_off, c.ws + c.P.dout_off, c.P.nlog_p, c.ws + head.gw_off, c.B, s);
+}
+
+// targets, loss, dL/dq: q_values / targets / priorities / per-head loss partials are final behind it
+static int learn_loss(const LearnCtx& c) {
+    if (!c.hc_S)
+        return loss_and_finalize(c.P, c.cfg, c.ws, c.batch, c.K, c.on0, c.tg0, c.learn, (c.learn && c.update) ? c.adam_count : nullptr, c.qv, c.tg,
+                                 c.priorities, c.losses, c.loss_accum, c.st);
+    if (int rc = launch_head_chain(c)) return rc;
+    // with a weight-gradient stream the sums leave the critical path: BackwardSchedule enqueues head_chain_tail() there
+    return c.ss ? ISDQN_OK : head_chain_sums(c, c.st);
+}
+
+// One layer's weight gradient as the schedule sees it (plain data: a deferred one waits in BackwardSchedule)
+struct WgradJob {
+    int layer = -1;  // -1: none
+    hipStream_t stream = nullptr;
+    hipEvent_t wait = nullptr;  // deferred: the fork recorded on the caller's stream behind the layer's data gradient
+    const float* dz = nullptr;  // gradient w.r.t. the layer's pre-activation output
+    int dz_ld = 0;
+};
+
+// dense weight gradient straight into Adam: one workgroup holds the whole contraction
+// (a gradient-only pass runs the same kernel with the stores of p / m / v switched off)
+static int dense_wgrad_fused_adam(const LearnCtx& c, const Layer& l, const float* act_in, const WgradJob& j) {
+    const MatSrc A{j.dz, j.dz_ld, c.B, l.out_p, 1};
+    const MatSrc Bm{act_in, l.in_p, c.B, l.in_p, 1};
+    AdamFuse af{c.params + l.w_off, c.adam_m + l.w_off, c.adam_v + l.w_off, c.ws + c.P.adam_tab_off,
+                c.cfg->learning_rate, c.cfg->adam_b1, c.cfg->adam_b2, c.cfg->adam_eps,
+                c.grad_out ? c.grad_out + l.w_off : nullptr, c.ws + c.P.wsplit_off + l.w_off, c.update ? 1 : 0};
+    // 64x64 tiles: the contraction is only B deep, the kernel lives off streaming p/m/v through the Adam
+    // epilogue, and 128x128 tiles would leave 100 workgroups for 256 CUs
+    // (operands: dz of a hidden layer -- or the fp32 dL/dq of the head -- and the S8 activations below it)
+    if (l.is_head)
+        return c.x3 ? launch_plain<64, 64, 2, 2, true, true, 3, true, false, true, 2>(A, nullptr, 0, Bm, nullptr, l.in_p, l.out_p, l.in_p, c.B, 1, 0,
+                                                                                      j.stream, &af)
+                    : launch_plain<64, 64, 2, 2, true, true, 1, true, false, true, 2>(A, nullptr, 0, Bm, nullptr, l.in_p, l.out_p, l.in_p, c.B, 1, 0,
+                                                                                      j.stream, &af);
+    return c.x3 ? launch_plain<64, 64, 2, 2, true, true, 3, true, false, true, DZ_S8 | 2>(A, nullptr, 0, Bm, nullptr, l.in_p, l.out_p, l.in_p, c.B, 1,
+                                                                                          0, j.stream, &af)
+                : launch_plain<64, 64, 2, 2, true, true, 1, true, false, true, DZ_S8 | 2>(A, nullptr, 0, Bm, nullptr, l.in_p, l.out_p, l.in_p, c.B, 1,
+                                                                                          0, j.stream, &af);
+}
+
+// weight gradient -> slabs and an entry in the optimizer list of its stream, or straight into Adam
+// `adam`: [0] caller's stream, [1] weight-gradient stream
+static int weight_gradient(const LearnCtx& c, const WgradJob& j, AdamList* adam) {
+    const Layer& l = c.P.L[j.layer];
+    float* ws = c.ws;
+    const float* act_in = j.layer > 0 ? ws + c.P.L[j.layer - 1].act_off : nullptr;
+    int w_slabs, rc;
+    if (l.is_head && c.hc_S && c.ss) {  // enqueued by head_chain_tail()
+        w_slabs = effective_splits(c.B, l.gw_slabs);
+    } else if (l.kind == 0) {
+        rc = conv_wgrad(l, c.x3, c.in, act_in, j.dz, ws + l.gw_off, c.B, j.stream, &w_slabs);
+        if (rc) return rc;
+    } else {
+        w_slabs = effective_splits(c.B, l.gw_slabs);
+        if (w_slabs == 1 && !l.in_unpadded_ld) return dense_wgrad_fused_adam(c, l, act_in, j);
+        rc = dense_wgrad(l, c.x3, c.in, act_in, j.dz, j.dz_ld, ws + l.gw_off, c.B, j.stream);
+        if (rc) return rc;
+    }
+    adam[c.ss && j.stream == c.wst ? 1 : 0].add(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size);
+    return ISDQN_OK;
+}
+
+#if !defined(ISDQN_FORK_LATE_MAX_B)
+#define ISDQN_FORK_LATE_MAX_B 768
+#endif
+// The side-stream policy of one learn step's backward pass: which stream a weight gradient runs on, where the caller's stream
+// forks, and in which order the kernels behind a fork are created.  Without a side stream (c.ss == nullptr) nothing forks and
+// every kernel is enqueued in line on the caller's stream.
+//
+//  * Streams.  Weight gradients of the middle layers go to the side stream.  Every fork costs the main stream an event record
+//    (a ~6 us bubble), so the head's tiny weight gradient and the first layer's (nothing is left to overlap with) stay on the
+//    main stream, and a dense layer (its Adam may be fused: an in-place update) forks once, AFTER its data gradient: dz is final
+//    and the data gradient, which reads W, is enqueued, so the update on the side stream cannot overtake it.
+//  * Tail swap.  With at least three layers the last two weight gradients swap streams: layer 1's follows its data gradient on
+//    the caller's stream, layer 0's (which only needs that data gradient's output) runs beside it.
+//  * Head chain.  Its loss / head-bias sums and the head's weight gradient (head_chain_tail) leave the critical path: they are
+//    enqueued on the side stream behind the first fork the backward pass makes anyway (no fork is spent on these two small
+//    kernels alone), or in line when no layer forked.
+//  * The caller's event (batch->priorities_ready: q_values / targets / priorities are final behind the loss) is likewise
+//    recorded at the first point that forks the caller's stream anyway, else at the end of the backward (no side stream: at once).
+//  * Which queue the replayed graph gives a kernel: a node's FIRST-created successor stays on its queue, the others move to
+//    another one and start ~12 us late.  Round 4's order (fork_late; c2 +1.2 %, c3 +7.5 %;
+//    -DISDQN_FORK_LATE_MAX_B=0 keeps round 3's):
+//      - the data-gradient chain is created first behind every fork, so it stays on the capturing queue all the way: a layer
+//        that forks after its data gradient records the fork there, but its side-stream kernels are created (`deferred`, flush)
+//        only after the NEXT layer's data gradient has been enqueued on the caller's stream;
+//      - the two head kernels become successors of the HEAD CHAIN on the side stream (head_event) -- created behind the dense
+//        data gradient, which therefore stays the head chain's first successor -- and run under the dense data gradient; the new
+//        queue's late start is hidden there, and it is what lets the first convolution data gradient become resident before the
+//        fused-Adam GEMM's 968 workgroups ask for the CUs.
+//    Large batches keep round 3's order: at B = 1024 every kernel is several rounds of workgroups, which queue gets the CUs first
+//    no longer matters and the new order measured 0.6 % slower (profiles/round4/ab_fork_c5.txt; ab_thresholds.txt: +2.0 % at
+//    B = 32, +1.7 % at 128, +1.5 % at 512, +2.0 % at 768).
+//  * Two optimizer lists: tensors whose gradient is produced on the side stream are updated there, the others on the caller's
+//    stream, so the step ends with two short Adam launches side by side instead of join -> reduce -> one Adam.  The side
+//    stream may update its own tensors only when every reader of the weights is behind it (adam_on_side): with the tail swap
+//    its last kernel (layer 0's weight gradient) waited for the last data gradient of the caller's stream.
+struct BackwardSchedule {
+    const LearnCtx& c;
+    AdamList* const adam;  // [0] caller's stream, [1] side stream
+    const bool tail_swap, fork_late;
+    bool prio_pending, head_pending;  // priorities_ready / head_chain_tail() still to be enqueued
+    hipEvent_t head_event = nullptr;  // fork_late: the head chain's end on the caller's stream
+    bool forked = false, layer0_chained = false;
+    WgradJob deferred;  // the side-stream work of the layer above, held back until this layer's data gradient is enqueued
+
+    BackwardSchedule(const LearnCtx& ctx, AdamList* lists)
+        : c(ctx), adam(lists), tail_swap(ctx.ss && ctx.P.n_layers >= 3 && !ctx.P.L[1].is_head),
+          fork_late(ctx.ss != nullptr && ctx.P.L[0].kind != 2 && ctx.B <= ISDQN_FORK_LATE_MAX_B),
+          prio_pending(ctx.batch->priorities_ready != nullptr), head_pending(ctx.hc_S && ctx.ss) {}
+
+    bool wgrad_on_side(int i) const { return c.ss && !c.P.L[i].is_head && (tail_swap ? i != 1 : i > 0); }
+    // (the head's weight gradient behind a head chain: head_chain_tail() on the side stream)
+    hipStream_t wgrad_stream(int i) const { return wgrad_on_side(i) || (c.P.L[i].is_head && c.hc_S) ? c.wst : c.st; }
+    bool forks_after_dgrad(int i) const { return wgrad_on_side(i) && c.P.L[i].kind == 1 && i > 0; }
+    // dz of the layer is final on the main stream (layer 0 with the tail swap: chain_layer0() already forked)
+    bool forks_before_dgrad(int i) const { return wgrad_on_side(i) && !forks_after_dgrad(i) && !(i == 0 && layer0_chained); }
+    bool adam_on_side() const { return c.ss && forked && tail_swap; }
+
+    int signal_priorities() {
+        if (prio_pending) {
+            prio_pending = false;
+            ISDQN_HIP_CHECK(hipEventRecord((hipEvent_t)c.batch->priorities_ready, c.st));
+        }
+        return ISDQN_OK;
+    }
+    int run_head_tail(hipStream_t s) {
+        if (!head_pending) return ISDQN_OK;
+        head_pending = false;
+        return head_chain_tail(c, s);
+    }
+    // behind the loss, in front of the first layer
+    int begin() {
+        if (!c.ss)
+            if (int rc = signal_priorities()) return rc;
+        if (fork_late && head_pending) {
+            head_event = next_event(c.ss);
+            ISDQN_HIP_CHECK(hipEventRecord(head_event, c.st));
+        }
+        return ISDQN_OK;
+    }
+    // fork in front of a layer's data gradient
+    int fork(hipStream_t side) {
+        if (int rc = chain(c.ss, c.st, side)) return rc;
+        if (int rc = signal_priorities()) return rc;
+        forked = true;
+        // (held-back side work of the layer above enqueues the two head kernels itself, behind this layer's data gradient)
+        return deferred.layer < 0 ? run_head_tail(side) : ISDQN_OK;
+    }
+    // fork behind a layer's data gradient; *defer: the job's kernels wait (as `deferred`) for the next layer's data gradient
+    int fork_after_dgrad(WgradJob& job, bool* defer) {
+        if (!fork_late) {
+            if (int rc = chain(c.ss, c.st, job.stream)) return rc;
+            if (int rc = signal_priorities()) return rc;
+            forked = true;
+            return run_head_tail(job.stream);
+        }
+        if (head_event != nullptr && head_pending) {  // (the dense data gradient is enqueued: the head chain keeps it as first successor)
+            ISDQN_HIP_CHECK(hipStreamWaitEvent(job.stream, head_event, 0));
+            if (int rc = run_head_tail(job.stream)) return rc;
+        }
+        job.wait = next_event(c.ss);
+        ISDQN_HIP_CHECK(hipEventRecord(job.wait, c.st));
+        *defer = true;
+        forked = true;
+        return signal_priorities();
+    }
+    // tail swap, behind layer 1's fused data gradient: layer 0's dz is final, its weight gradient may start beside layer 1's
+    int chain_layer0() {
+        if (int rc = chain(c.ss, c.st, c.wst)) return rc;
+        forked = layer0_chained = true;
+        return run_head_tail(c.wst);
+    }
+    // the held-back side-stream work, now that the data gradient it yields to is enqueued
+    int flush() {
+        if (deferred.layer < 0) return ISDQN_OK;
+        const WgradJob j = deferred;
+        deferred.layer = -1;
+        ISDQN_HIP_CHECK(hipStreamWaitEvent(j.stream, j.wait, 0));
+        if (int rc = run_head_tail(j.stream)) return rc;
+        return weight_gradient(c, j, adam);
+    }
+    // behind the last layer
+    int finish() {
+        if (int rc = flush()) return rc;
+        if (int rc = run_head_tail(c.st)) return rc;  // no layer forked: keep the two kernels in line
+        return signal_priorities();
+    }
+};
+
+// first dense layer over a 64-channel conv output: data gradient + LN/ReLU backward of the layer below in one kernel
+static bool dense_dgrad_ln_applies(const Layer& l, const Layer& below, int B) {
+    return l.kind == 1 && below.kind != 1 && below.cout_p == 64 && !l.in_unpadded_ld && below.part_rows >= ceil_div(B, 128) * below.npix;
+}
+static int dense_dgrad_ln(const LearnCtx& c, const Layer& l, const Layer& below, const float* dz, int dz_ld, ReduceJobs* red) {
+    float* ws = c.ws;
+    const int B = c.B;
+    auto launch = [&](auto prob) {
+        prob.A = MatSrc{dz, dz_ld, B, l.out_p, 1};
+        prob.B = MatSrc{c.wmir() + l.w_off, l.in_p, l.out_f, l.in_p, 1};
+        prob.z = ws + below.z_off;
+        prob.gamma = below.has_ln ? c.params + below.g_off : nullptr;
+        prob.beta = below.has_ln ? c.params + below.be_off : nullptr;
+        prob.dz_out = ws + below.dz_off;
+        prob.part = ws + below.part_off;
+        prob.ldc = l.in_p; prob.M = B; prob.N = l.in_p; prob.K = l.out_p; prob.c_in = below.out_f;
+        prob.tiles_m = ceil_div(B, decltype(prob)::BM); prob.tiles_n = l.in_p / 64;
+        return launch_gemm(prob, prob.tiles_m * prob.tiles_n, c.st);
+    };
+    // 128-row tiles (8 accumulators per wave).  64-row tiles fill the chip better (196 workgroups, -3 us)
+    // but are a four-accumulator kernel, and those are not run-to-run stable on gfx950
+    // at most one workgroup per CU (242 at the headline size): two K groups of four waves (gemm_core.h)
+    static const bool no_kg = ISDQN_DEV_ENV("ISDQN_NO_KGROUPS");
+    const bool kg2 = !no_kg && ceil_div(B, 128) * (l.in_p / 64) <= 256 && l.out_p % 64 == 0;
+    int rc;
+    // ISDQN_DGRAD64 (development): 64-row tiles, one K group
+#if defined(ISDQN_DGRAD64)
+    (void)kg2;
+    rc = c.x3 ? launch(DenseDgradLN<3, 64>{}) : launch(DenseDgradLN<1, 64>{});
+    constexpr int DG_BM = 64;
+#else
+    if (kg2) rc = c.x3 ? launch(DenseDgradLN<3, 128, 2>{}) : launch(DenseDgradLN<1, 128, 2>{});
+    else rc = c.x3 ? launch(DenseDgradLN<3, 128>{}) : launch(DenseDgradLN<1, 128>{});
+    constexpr int DG_BM = 128;
+#endif
+    if (rc) return rc;
+    add_reduce_job(*red, ws + below.part_off, ceil_div(B, DG_BM) * (l.in_p / 64), 3 * below.out_p, ws + below.red_off);
+    return ISDQN_OK;
+}
+
+// data gradient of layer i > 0 for the layer below.  *dz_fused: a fused kernel also ran the LN/ReLU backward of the layer below (its dz
+// is written, the partial rows of its parameter gradients are a job in `red`); otherwise da (w.r.t. that layer's activation) is in ws+da_off
+static int data_gradient(const LearnCtx& c, int i, const float* dz, int dz_ld, bool* dz_fused, ReduceJobs* red) {
+    const Layer &l = c.P.L[i], &below = c.P.L[i - 1];
+    float* da = c.ws + c.P.da_off;
+    *dz_fused = false;
+    if (l.is_head && c.hc_S) return ISDQN_OK;  // dz of the hidden layer came from the head chain
+    if (l.kind == 0) {
+        int rc = conv_dgrad_img(l, below, c.x3, c.params, c.wmir(), dz, c.ws, c.B, c.st, dz_fused, red);
+        if (rc || *dz_fused) return rc;
+        return conv_dgrad(l, c.x3, c.wmir(), dz, da, c.B, c.st);
+    }
+    if (dense_dgrad_ln_applies(l, below, c.B)) {
+        *dz_fused = true;
+        return dense_dgrad_ln(c, l, below, dz, dz_ld, red);
+    }
+    const bool narrow = ceil_div(c.B, 128) * ceil_div(l.in_p, 128) < 200;
+    return dense_dgrad(l, c.x3, c.wmir(), dz, dz_ld, da, c.B, narrow, c.st);
+}
+
+// backward (online rows only: the next-state half has a zero cotangent, isdqn.py:99), top layer first.  Per layer: parameter-gradient
+// entries -> maybe fork -> data gradient for the layer below -> what the layer above deferred -> fork after the data gradient, or
+// defer -> weight gradient
+static int learn_backward(const LearnCtx& c, BackwardSchedule& sched, AdamList* adam, ReduceJobs* red) {
+    const Plan& P = c.P;
+    float* ws = c.ws;
+    const int B = c.B;
+    int rc;
+    const float* dz_cur = ws + P.dout_off;  // gradient w.r.t. the current layer's pre-activation output
+    int dz_ld = P.nlog_p;
+    bool dz_fused = false;  // dz of layer i was already produced by the fused data gradient of layer i+1
+    for (int i = P.n_layers - 1; i >= 0; --i) {
+        const Layer& l = P.L[i];
+        if (l.is_head) {
+            adam[c.hc_S && c.ss ? 1 : 0].add(l.b_off, l.out_p, ws + P.dbh_off, 1, 0);  // loss_finalize_kernel's stream
+        } else {
+            dz_cur = ws + l.dz_off;
+            dz_ld = l.out_p;
+            if (c.hc_S && i == P.n_layers - 2) {  // dz and the partial sums came from the head chain
+                add_ln_bias_entries(adam[0], l, ws + l.part_off, c.hc_wg, 3 * (int64_t)l.out_p);
+            } else if (dz_fused) {  // (reduce_rows_kernel, in front of Adam)
+                add_ln_bias_entries(adam[0], l, ws + l.red_off, 1, 0);
+            } else {
+                // da (w.r.t. this layer's activation) was left in ws+da_off by layer i+1's data-gradient
+                int nb = 0;
+                rc = ln_bwd(l, c.params, ws + P.da_off, ws + l.z_off, l.kind != 1 ? B * l.npix : B, ws + l.dz_off, ws + l.part_off, &nb, c.st);
+                if (rc) return rc;
+                add_ln_bias_entries(adam[0], l, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
+            }
+        }
+        if (l.kind == 2) {  // the impala torso: its own backward (generic engine + row-wise kernels) and optimizer launches, on the caller's stream
+            rc = impala_backward(P, c.cfg, c.x3, c.params, c.adam_m, c.adam_v, c.wmir(), ws, B, c.grad_out, c.update, c.st);
+            if (rc) return rc;
+            continue;
+        }
+        WgradJob job;
+        job.layer = i; job.stream = sched.wgrad_stream(i); job.dz = dz_cur; job.dz_ld = dz_ld;
+        if (sched.forks_before_dgrad(i)) {
+            rc = sched.fork(job.stream);
+            if (rc) return rc;
+        }
+        // data gradient for the layer below first: it reads this layer's weights, which the fused-Adam
+        // weight-gradient epilogue below updates in place
+        dz_fused = false;
+        if (i > 0) {
+            rc = data_gradient(c, i, dz_cur, dz_ld, &dz_fused, red);
+            if (rc) return rc;
+        }
+        rc = sched.flush();
+        if (rc) return rc;
+        bool defer = false;
+        if (sched.forks_after_dgrad(i)) {
+            rc = sched.fork_after_dgrad(job, &defer);
+            if (rc) return rc;
+        }
+        if (sched.tail_swap && i == 1 && dz_fused) {
+            rc = sched.chain_layer0();
+            if (rc) return rc;
+        }
+        if (defer) {
+            sched.deferred = job;
+        } else {
+            rc = weight_gradient(c, job, adam);
+            if (rc) return rc;
+        }
+    }
+    return sched.finish();
+}
+
+// the partial-row reductions the fused data gradients left, and the optimizer launches of both streams; the call is complete on
+// the caller's stream behind it (and the next call may touch the workspace)
+static int learn_optimizer(const LearnCtx& c, const BackwardSchedule& sched, const AdamList* adam, const ReduceJobs& red) {
+    auto run_adam = [&](const AdamList& list, hipStream_t s) {
+        return list.launch(s, c.P, c.cfg, c.params, c.adam_m, c.adam_v, c.ws, c.grad_out, c.update);
+    };
+    int rc;
+    if (sched.adam_on_side()) {
+        rc = run_adam(adam[1], c.wst);
+        if (rc) return rc;
+    } else if (c.ss) {  // all weight gradients done before Adam
+        rc = chain(c.ss, c.wst, c.st);
+        if (rc) return rc;
+    }
+    if (red.n > 0) {
+        hipLaunchKernelGGL(reduce_rows_kernel, dim3(red.block_start[red.n]), dim3(256), 0, c.st, red);
+        ISDQN_HIP_CHECK(hipGetLastError());
+    }
+    rc = run_adam(adam[0], c.st);
+    if (rc) return rc;
+    return sched.adam_on_side() ? chain(c.ss, c.wst, c.st) : run_adam(adam[1], c.st);
 }
 
 static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, int32_t* adam_count,
@@ -1921,499 +2510,37 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
         return bn_learn_or_loss(cfg, P, params, adam_m, adam_v, adam_count, batch, losses, loss_accum, q_values, targets, priorities,
                                 (float*)workspace, (hipStream_t)stream, learn, grad_out, update, target_params, sel);
     }
-    const bool x3 = cfg->precision == ISDQN_PRECISION_BF16X3;
     const int B = P.B, K = sel ? sel->K : P.K;
     const int on0 = sel ? sel->on0 : P.oh, tg0 = sel ? sel->tg0 : 0;
     if (sel) ISDQN_REQUIRE(sel->K >= 1 && on0 >= 0 && tg0 >= 0 && on0 + K <= P.n_heads && tg0 + K <= P.n_heads && K <= P.K, ISDQN_ERR_ARG,
                            "head selection outside the network's heads");
     float* ws = (float*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    NetInput in{batch->frames, batch->frame_stride, batch->frame_ids, B, batch->state, batch->next_state, B};
+    LearnCtx c{P, cfg, batch, params, adam_m, adam_v, adam_count, target_params, losses, loss_accum,
+               q_values ? q_values : ws + P.qv_off, targets ? targets : ws + P.tg_off, priorities, ws, grad_out, (hipStream_t)stream,
+               learn, update, cfg->precision == ISDQN_PRECISION_BF16X3, B, K, on0, tg0,
+               NetInput{batch->frames, batch->frame_stride, batch->frame_ids, B, batch->state, batch->next_state, B}};
+    head_chain_plan(c, sel == nullptr);
+    c.ss = learn ? side_stream() : nullptr;
+    c.wst = c.ss ? c.ss->stream : c.st;
 
-    // ---- head chain eligibility (learn path): last hidden layer dense + ReLU, widths within the kernel's limits ----
-    const Layer& hid = P.L[P.n_layers >= 2 ? P.n_layers - 2 : 0];
-    const Layer& head = P.L[P.n_layers - 1];
-    int hc_S = 0, hc_wg = 0;
-    static const bool hc_disabled = ISDQN_DEV_ENV("ISDQN_NO_HEAD_CHAIN");
-    // (histogram heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
-    if (learn && update && sel == nullptr && !hc_disabled && target_params == nullptr && P.hl_nb == 0 && P.n_layers >= 2 && hid.kind == 1 && !hid.is_head && hid.has_relu &&
-        hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0) {
-        // transitions per workgroup: the per-transition phases scale with S (the kernel is instruction-issue bound) while
-        // every workgroup streams the whole head matrix from L2, so S follows the batch: about 256 workgroups
-        const int S = B >= 1024 ? 4 : B >= 512 ? 2 : 1;
-        const int n_wg = ceil_div(B, S);
-        if (n_wg <= hid.part_rows && S * K <= HC_THREADS &&
-            head_chain_lds_bytes(hid.out_p, P.nha_p, K, x3 ? 3 : 1, S) <= 150 * 1024) {
-            hc_S = S;
-            hc_wg = n_wg;
-        }
-    }
-    SideStream* ss = learn ? side_stream() : nullptr;
-    hipStream_t wst = ss ? ss->stream : st;  // stream of the weight gradients
-    const float* wmir = ws + P.wsplit_off;
-
-    if (target_params != nullptr) {
-        // DQN (dqn.py:74-88): the next states go through the TARGET parameters, the states through the online ones: two
-        // forwards of B images each over the same workspace, q rows [B, 2B) first, then rows [0, B) (+ z of every layer)
-        const int stack = cfg->arch != ISDQN_ARCH_FC ? cfg->obs_c : 0;
-        NetInput nx{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->next_state, nullptr, 0, 2 * stack, stack};
-        rc = refresh_mirror(P, target_params, ws, st);
-        if (rc) return rc;
-        rc = net_forward(P, x3, target_params, nx, B, 0, ws, ws + P.out_off + (int64_t)B * P.nlog_p, st);
-        if (rc) return rc;
-        rc = refresh_mirror(P, params, ws, st);
-        if (rc) return rc;
-        NetInput on{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->state, nullptr, 0, 2 * stack, 0};
-        rc = net_forward(P, x3, params, on, B, B, ws, ws + P.out_off, st);
-        if (rc) return rc;
-    } else {
-        // The optimizer writes the updated parameters in both forms, so a learn step leaves the mirror current; a caller
-        // that chains learn steps on one workspace with nothing else writing `params` in between says so
-        // (ISDQN_BATCH_MIRROR_CURRENT: the captured multi-step graphs) and the refresh is skipped.
-        if (!(batch->flags & ISDQN_BATCH_MIRROR_CURRENT)) {
-            rc = refresh_mirror(P, params, ws, st);
-            if (rc) return rc;
-        }
-        // ---- forward on concat(state, next_state) (isdqn.py:95) ----
-        rc = net_forward(P, x3, params, in, P.N2, B, ws, ws + P.out_off, st, hc_S ? P.n_layers - 1 : -1,
-                         hc_S ? P.n_layers - 2 : -1);
-        if (rc) return rc;
-    }
-
-    // ---- targets, loss, dL/dq ----
-    float* qv = q_values ? q_values : ws + P.qv_off;
-    float* tg = targets ? targets : ws + P.tg_off;
-    const int hl_R = P.hl_nb > 0 ? hl_rows_per_wg(K, P.hl_nb) : 0;
-    const int n_blk = hc_S ? hc_wg : hl_R ? ceil_div(B, hl_R) : ceil_div(B, TD_ROWS);
-    float* loss_part = ws + P.lpart_off;
-    float* dbh_part = loss_part + (int64_t)n_blk * K;
-    float* adam_consts = ws + P.adam_tab_off;
-    if (hc_S) {
-        HeadChainParams hp;
-        hp.act = ws + hid.act_off; hp.z = ws + hid.z_off;
-        hp.slabs = ws + P.slab_off;
-        hp.n_slabs = effective_splits(hid.in_unpadded_ld ? hid.in_f : hid.K, hid.fwd_splits);
-        hp.slab_stride = hid.out_p;
-        hp.row_pitch = (int64_t)hp.n_slabs * hid.out_p;
-        hp.hbias = params + hid.b_off;
-        hp.W = params + head.w_off; hp.bias = params + head.b_off;
-        hp.gamma = hid.has_ln ? params + hid.g_off : nullptr;
-        hp.beta = hid.has_ln ? params + hid.be_off : nullptr;
-        hp.B = B; hp.S = hc_S; hp.F = hid.out_f; hp.Fp = hid.out_p; hp.O = P.nha; hp.Op = P.nha_p; hp.K = K; hp.oh = P.oh;
-        hp.A = P.n_actions;
-        hp.action = batch->action; hp.reward = batch->reward; hp.terminal = batch->terminal;
-        hp.loss_weights = batch->loss_weights;
-        hp.gamma_n = cfg->gamma_n; hp.huber_delta = cfg->huber_delta;
-        hp.dout = ws + P.dout_off; hp.dz = ws + hid.dz_off; hp.part = ws + hid.part_off;
-        hp.q_values = qv; hp.targets = tg; hp.priorities = priorities;
-        hp.loss_part = loss_part; hp.dbh_part = dbh_part;
-        hp.adam_count = adam_count; hp.b1 = cfg->adam_b1; hp.b2 = cfg->adam_b2; hp.adam_consts = adam_consts;
-        hp.stamps = stamps_for("head_chain");
-        const int lds = head_chain_lds_bytes(hid.out_p, P.nha_p, K, x3 ? 3 : 1, hc_S);
-        const int cols = ceil_div(hid.out_p, HC_THREADS) <= 1 ? 1 : ceil_div(hid.out_p, HC_THREADS) <= 2 ? 2 : 4;
-        auto launch_hc = [&](auto kern, int slot) -> int {
-            static LdsConfigured configured[18];
-            if (int rc2 = ensure_dynamic_lds(kern, lds, configured[slot])) return rc2;
-            ISDQN_REPORT_OCCUPANCY(kern, HC_THREADS, lds, hc_wg);
-            hipLaunchKernelGGL(kern, dim3(hc_wg), dim3(HC_THREADS), lds, st, hp);
-            ISDQN_HIP_CHECK(hipGetLastError());
-            return ISDQN_OK;
-        };
-        auto by_cols = [&](auto passes_c, auto s_c, int base) -> int {
-            constexpr int PS = decltype(passes_c)::value, SS = decltype(s_c)::value;
-            return cols == 1 ? launch_hc(&head_chain_kernel<PS, 1, SS>, base) : cols == 2 ? launch_hc(&head_chain_kernel<PS, 2, SS>, base + 1)
-                                                                            : launch_hc(&head_chain_kernel<PS, 4, SS>, base + 2);
-        };
-        auto by_s = [&](auto passes_c, int base) -> int {
-            return hc_S == 1 ? by_cols(passes_c, std::integral_constant<int, 1>{}, base)
-                 : hc_S == 2 ? by_cols(passes_c, std::integral_constant<int, 2>{}, base + 3)
-                             : by_cols(passes_c, std::integral_constant<int, 4>{}, base + 6);
-        };
-        rc = x3 ? by_s(std::integral_constant<int, 3>{}, 0) : by_s(std::integral_constant<int, 1>{}, 9);
-        if (rc) return rc;
-        // The loss / head-bias reductions and the head's weight gradient leave the critical path: with a weight-
-        // gradient stream they are enqueued there behind the first fork the backward pass makes anyway (every fork
-        // costs the main stream a dependency bubble, so none is spent on these two small kernels alone).
-        if (!ss) {
-            hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nha_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nha_p,
-                               losses, loss_accum, ws + P.dbh_off, (int*)nullptr, cfg->adam_b1, cfg->adam_b2, adam_consts);
-            ISDQN_HIP_CHECK(hipGetLastError());
-        }
-    } else {
-        if (hl_R)
-            hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.hl_nb * sizeof(float), st, ws + P.logits_off, B, hl_R,
-                               K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
-                               batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n,
-                               learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
-        else
-            hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, B, K,
-                               on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta,
-                               learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
-        ISDQN_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nlog_p, 16)), dim3(256), 0, st, loss_part, dbh_part, n_blk, B, K, P.nlog_p,
-                           losses, loss_accum, learn ? ws + P.dbh_off : nullptr, (learn && update) ? adam_count : nullptr,
-                           cfg->adam_b1, cfg->adam_b2, adam_consts);
-        ISDQN_HIP_CHECK(hipGetLastError());
-    }
-    // q_values / targets / priorities / per-head loss partials are final here.  The caller's event (batch->priorities_ready) is
-    // recorded at the first point that forks the caller's stream anyway (every fork costs it a dependency bubble), else now.
-    bool prio_pending = batch->priorities_ready != nullptr;
-    auto signal_priorities = [&]() -> int {
-        if (prio_pending) {
-            prio_pending = false;
-            ISDQN_HIP_CHECK(hipEventRecord((hipEvent_t)batch->priorities_ready, st));
-        }
-        return ISDQN_OK;
-    };
-    if (!learn || !ss) {
-        rc = signal_priorities();
-        if (rc) return rc;
-    }
-    if (!learn) return ISDQN_OK;
-
-    // ---- backward (online rows only: the next-state half has a zero cotangent, isdqn.py:99) ----
-    // Two optimizer tables: tensors whose gradient is produced on the weight-gradient stream are updated there, the others on
-    // the caller's stream, so the step ends with two short Adam launches side by side instead of join -> reduce -> one Adam.
-    AdamTable tabs[2];  // [0] caller's stream, [1] weight-gradient stream
-    tabs[0].n = tabs[1].n = 0;
-    tabs[0].total_blocks = tabs[1].total_blocks = 0;
-    auto add_entry_on = [&](int which, int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
-        AdamTable& tab = tabs[which];
-        AdamEntry& e = tab.e[tab.n++];
-        e.p_off = p_off; e.size = size; e.g = g; e.n_slabs = n_slabs; e.slab_stride = stride;
-        e.block_start = tab.total_blocks;
-        tab.total_blocks += (int)((size + 63) / 64);
-    };
-    auto add_entry = [&](int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
-        add_entry_on(0, p_off, size, g, n_slabs, stride);
-    };
-    // With a weight-gradient stream and at least three layers, the last two weight gradients swap streams: layer 1's follows
-    // its data gradient on the caller's stream, layer 0's (which only needs that data gradient's output) runs beside it.
-    const bool tail_swap = ss && P.n_layers >= 3 && !P.L[1].is_head;
-    bool forked = false, layer0_chained = false;
-    const float* dz_cur = ws + P.dout_off;  // gradient w.r.t. the current layer's pre-activation output
-    int dz_ld = P.nlog_p;
-    bool dz_fused = false;  // dz of layer i was already produced by the fused data gradient of layer i+1
-    ReduceJobs red_jobs;    // partial-row reductions left by the fused data gradients (one launch before Adam)
-    red_jobs.n = 0;
-    red_jobs.block_start[0] = 0;
-    bool head_deferred = hc_S && ss;  // loss_finalize + head weight gradient still to be enqueued on the side stream
-    auto run_head_deferred = [&](hipStream_t s2) -> int {
-        if (!head_deferred) return ISDQN_OK;
-        head_deferred = false;
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(ceil_div(K, 16) + ceil_div(P.nha_p, 16)), dim3(256), 0, s2, loss_part, dbh_part, n_blk, B, K, P.nha_p, losses,
-                           loss_accum, ws + P.dbh_off, (int*)nullptr, cfg->adam_b1, cfg->adam_b2, adam_consts);
-        ISDQN_HIP_CHECK(hipGetLastError());
-        MatSrc A{ws + P.dout_off, P.nlog_p, B, head.out_p, 1};
-        MatSrc Bm{ws + hid.act_off, head.in_p, B, head.in_p, 1};
-        return plain_big<true, true, true, false, 2>(x3, A, nullptr, 0, Bm, ws + head.gw_off, head.in_p, head.out_p, head.in_p, B,
-                                                     head.gw_slabs, head.w_size, s2);  // dL/dq fp32, hidden activations S8
-    };
-    std::function<int()> deferred;  // side-stream launches of the layer above, held back until this layer's data gradient is enqueued
-    // Which queue the replayed graph gives a kernel: a node's FIRST-created successor stays on its queue, the others move to
-    // another one and start ~12 us late.  Round 4's order (c2 +1.2 %, c3 +7.5 %; -DISDQN_FORK_LATE_MAX_B=0 keeps round 3's):
-    //   * the data-gradient chain is created first behind every fork, so it stays on the capturing queue all the way;
-    //   * the two small kernels that only need the head chain's outputs (loss sums, head weight gradient) become successors of the
-    //     HEAD CHAIN on the side stream -- created behind the dense data gradient, which therefore stays the head chain's first
-    //     successor -- and run under the dense data gradient; the new queue's late start is hidden there, and it is what lets the
-    //     first convolution data gradient become resident before the fused-Adam GEMM's 968 workgroups ask for the CUs.
-    // Large batches keep round 3's order: at B = 1024 every kernel is several rounds of workgroups, which queue gets the CUs first
-    // no longer matters and the new order measured 0.6 % slower (profiles/round4/ab_fork_c5.txt; ab_thresholds.txt: +2.0 % at
-    // B = 32, +1.7 % at 128, +1.5 % at 512, +2.0 % at 768).
-    hipEvent_t head_event = nullptr;
-#if !defined(ISDQN_FORK_LATE_MAX_B)
-#define ISDQN_FORK_LATE_MAX_B 768
-#endif
-    const bool fork_late = ss != nullptr && P.L[0].kind != 2 && B <= ISDQN_FORK_LATE_MAX_B;
-    if (fork_late && head_deferred) {
-        head_event = ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % (unsigned)ss->n_ev];
-        ISDQN_HIP_CHECK(hipEventRecord(head_event, st));
-    }
-    for (int i = P.n_layers - 1; i >= 0; --i) {
-        const Layer& l = P.L[i];
-        const float* act_in = i > 0 ? ws + P.L[i - 1].act_off : nullptr;
-        if (!l.is_head) {
-            dz_cur = ws + l.dz_off;
-            dz_ld = l.out_p;
-            if (hc_S && i == P.n_layers - 2) {  // dz and the partial sums came from the head chain
-                if (l.has_ln) {
-                    add_entry(l.g_off, l.out_p, ws + l.part_off, hc_wg, 3 * (int64_t)l.out_p);
-                    add_entry(l.be_off, l.out_p, ws + l.part_off + l.out_p, hc_wg, 3 * (int64_t)l.out_p);
-                }
-                add_entry(l.b_off, l.out_p, ws + l.part_off + 2 * l.out_p, hc_wg, 3 * (int64_t)l.out_p);
-            } else if (dz_fused) {
-                if (l.has_ln) {
-                    add_entry(l.g_off, l.out_p, ws + l.red_off, 1, 0);
-                    add_entry(l.be_off, l.out_p, ws + l.red_off + l.out_p, 1, 0);
-                }
-                if (l.b_off >= 0) add_entry(l.b_off, l.out_p, ws + l.red_off + 2 * l.out_p, 1, 0);  // (the impala torso has no bias of its own)
-            } else {
-                // da (w.r.t. this layer's activation) was left in ws+da_off by layer i+1's data-gradient
-                int rows = l.kind != 1 ? B * l.npix : B;
-                int nb = 0;
-                rc = ln_bwd(l, params, ws + P.da_off, ws + l.z_off, rows, ws + l.dz_off, ws + l.part_off, &nb, st);
-                if (rc) return rc;
-                if (l.has_ln) {
-                    add_entry(l.g_off, l.out_p, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
-                    add_entry(l.be_off, l.out_p, ws + l.part_off + l.out_p, nb, 3 * (int64_t)l.out_p);
-                }
-                if (l.b_off >= 0) add_entry(l.b_off, l.out_p, ws + l.part_off + 2 * l.out_p, nb, 3 * (int64_t)l.out_p);
-            }
-        } else {
-            add_entry_on(hc_S && ss ? 1 : 0, l.b_off, l.out_p, ws + P.dbh_off, 1, 0);  // loss_finalize_kernel's stream
-        }
-        if (l.kind == 2) {  // the impala torso: its own backward (generic engine + row-wise kernels) and optimizer launches, on the caller's stream
-            rc = impala_backward(P, cfg, x3, params, adam_m, adam_v, wmir, ws, B, grad_out, update, st);
-            if (rc) return rc;
-            continue;
-        }
-        // Weight gradients of the middle layers go to the side stream.  Every fork costs the main stream an event
-        // record (a ~6 us bubble), so the head's tiny weight gradient and the first layer's (nothing is left to
-        // overlap with) stay on the main stream, and a layer whose Adam is fused forks once, after its data gradient.
-        const bool head_chained = l.is_head && hc_S;  // the fork happened right after the head chain
-        const bool wg_on_side = ss && !l.is_head && (tail_swap ? i != 1 : i > 0);
-        hipStream_t lws = (wg_on_side || head_chained) ? wst : st;
-        const bool fork_after_dgrad = wg_on_side && l.kind == 1 && i > 0;
-        if (wg_on_side && !fork_after_dgrad && !(i == 0 && layer0_chained)) {  // dz of this layer is final on the main stream
-            rc = chain(ss, st, lws);
-            if (rc) return rc;
-            rc = signal_priorities();
-            if (rc) return rc;
-            forked = true;
-            if (!deferred) {  // (held-back side work of the layer above enqueues the two head kernels itself, behind this layer's data gradient)
-                rc = run_head_deferred(lws);
-                if (rc) return rc;
-            }
-        }
-        // data gradient for the layer below first: it reads this layer's weights, which the fused-Adam
-        // weight-gradient epilogue below updates in place
-        dz_fused = false;
-        if (i > 0) {
-            if (l.kind == 0) {
-                rc = conv_dgrad_img(l, P.L[i - 1], x3, params, wmir, dz_cur, ws, B, st, &dz_fused, &red_jobs);
-                if (rc) return rc;
-            }
-            if (l.kind == 1 && P.L[i - 1].kind != 1 && P.L[i - 1].cout_p == 64 && !l.in_unpadded_ld &&
-                P.L[i - 1].part_rows >= ceil_div(B, 128) * P.L[i - 1].npix) {
-                // first dense layer over a 64-channel conv output: data gradient + LN/ReLU backward in one kernel
-                const Layer& below = P.L[i - 1];
-                auto launch = [&](auto prob) {
-                    prob.A = MatSrc{dz_cur, dz_ld, B, l.out_p, 1};
-                    prob.B = MatSrc{wmir + l.w_off, l.in_p, l.out_f, l.in_p, 1};
-                    prob.z = ws + below.z_off;
-                    prob.gamma = below.has_ln ? params + below.g_off : nullptr;
-                    prob.beta = below.has_ln ? params + below.be_off : nullptr;
-                    prob.dz_out = ws + below.dz_off;
-                    prob.part = ws + below.part_off;
-                    prob.ldc = l.in_p; prob.M = B; prob.N = l.in_p; prob.K = l.out_p; prob.c_in = below.out_f;
-                    prob.tiles_m = ceil_div(B, decltype(prob)::BM); prob.tiles_n = l.in_p / 64;
-                    return launch_gemm(prob, prob.tiles_m * prob.tiles_n, st);
-                };
-                // 128-row tiles (8 accumulators per wave).  64-row tiles fill the chip better (196 workgroups, -3 us)
-                // but are a four-accumulator kernel, and those are not run-to-run stable on gfx950
-                // at most one workgroup per CU (242 at the headline size): two K groups of four waves (gemm_core.h)
-                static const bool no_kg = ISDQN_DEV_ENV("ISDQN_NO_KGROUPS");
-                const bool kg2 = !no_kg && ceil_div(B, 128) * (l.in_p / 64) <= 256 && l.out_p % 64 == 0;
-                // ISDQN_DGRAD64 (development): 64-row tiles, one K group
-#if defined(ISDQN_DGRAD64)
-                (void)kg2;
-                rc = x3 ? launch(DenseDgradLN<3, 64>{}) : launch(DenseDgradLN<1, 64>{});
-                constexpr int DG_BM = 64;
-#else
-                if (kg2) rc = x3 ? launch(DenseDgradLN<3, 128, 2>{}) : launch(DenseDgradLN<1, 128, 2>{});
-                else rc = x3 ? launch(DenseDgradLN<3, 128>{}) : launch(DenseDgradLN<1, 128>{});
-                constexpr int DG_BM = 128;
-#endif
-                if (rc) return rc;
-                add_reduce_job(red_jobs, ws + below.part_off, ceil_div(B, DG_BM) * (l.in_p / 64), 3 * below.out_p,
-                               ws + below.red_off);
-                dz_fused = true;
-            }
-            if (dz_fused || head_chained) {
-            } else if (l.kind == 0) {
-                const bool small = l.cin_p <= 32;
-                if (x3) rc = small ? launch_conv_dgrad<32, 3>(l, wmir, dz_cur, ws + P.da_off, B, st)
-                                   : launch_conv_dgrad<64, 3>(l, wmir, dz_cur, ws + P.da_off, B, st);
-                else rc = small ? launch_conv_dgrad<32, 1>(l, wmir, dz_cur, ws + P.da_off, B, st)
-                                : launch_conv_dgrad<64, 1>(l, wmir, dz_cur, ws + P.da_off, B, st);
-            } else {
-                // da[b][in_p] = sum_o dz[b][o] * W[o][in_p]
-                MatSrc A{dz_cur, dz_ld, B, l.out_p, 1};
-                MatSrc Bm{wmir + l.w_off, l.in_p, l.out_f, l.in_p, 1};
-                const bool narrow = ceil_div(B, 128) * ceil_div(l.in_p, 128) < 200;
-                if (l.is_head)  // dL/dq: fp32
-                    rc = narrow ? plain_narrow<false, true, 2>(x3, A, Bm, ws + P.da_off, l.in_p, B, l.in_p, l.out_p, 1, 0, st)
-                                : plain_big<false, true, true, false, 2>(x3, A, nullptr, 0, Bm, ws + P.da_off, l.in_p, B, l.in_p, l.out_p, 1, 0, st);
-                else
-                    rc = narrow ? plain_narrow<false, true, DZ_S8 | 2>(x3, A, Bm, ws + P.da_off, l.in_p, B, l.in_p, l.out_p, 1, 0, st)
-                                : plain_big<false, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, ws + P.da_off, l.in_p, B, l.in_p, l.out_p, 1, 0, st);
-            }
-            if (rc) return rc;
-        }
-        if (deferred) {  // the side-stream work of the layer above, now that this layer's data gradient is enqueued
-            auto f = std::move(deferred);
-            deferred = nullptr;
-            rc = f();
-            if (rc) return rc;
-        }
-        // weight gradient -> slabs (or straight into Adam when one workgroup holds the whole contraction)
-        bool defer_side = false;
-        hipEvent_t defer_event = nullptr;
-        if (fork_after_dgrad) {  // dz is final AND the data gradient (which reads W) is enqueued: an in-place
-                                 // fused-Adam update on the side stream cannot overtake it
-            if (fork_late && i > 0) {
-                // Graph replay keeps the FIRST successor of a node on its queue and moves the others to another queue, where they
-                // start ~12 us late.  The successor that matters is the next data gradient: record the fork here,
-                // but create the side stream's kernels (loss_finalize, head weight gradient, this layer's weight gradient) only
-                // after that data gradient has been enqueued on the caller's stream.
-                if (head_event != nullptr && head_deferred) {  // (the dense data gradient is enqueued: the head chain keeps it as first successor)
-                    ISDQN_HIP_CHECK(hipStreamWaitEvent(lws, head_event, 0));
-                    rc = run_head_deferred(lws);
-                    if (rc) return rc;
-                }
-                defer_event = ss->ev[ss->next.fetch_add(1, std::memory_order_relaxed) % (unsigned)ss->n_ev];
-                ISDQN_HIP_CHECK(hipEventRecord(defer_event, st));
-                defer_side = true;
-                rc = signal_priorities();
-                if (rc) return rc;
-                forked = true;
-            } else {
-                rc = chain(ss, st, lws);
-                if (rc) return rc;
-                rc = signal_priorities();
-                if (rc) return rc;
-                forked = true;
-                rc = run_head_deferred(lws);
-                if (rc) return rc;
-            }
-        }
-        if (tail_swap && i == 1 && dz_fused) {  // layer 0's dz is final: its weight gradient may start beside this layer's
-            rc = chain(ss, st, wst);
-            if (rc) return rc;
-            forked = layer0_chained = true;
-            rc = run_head_deferred(wst);
-            if (rc) return rc;
-        }
-        // (the weight-gradient part of this layer as a closure: with ISDQN_FORK_LATE a layer that forks the side stream behind its
-        // own data gradient enqueues it only after the NEXT layer's data gradient is on the caller's stream -- see `deferred`)
-        const Layer* lp = &l;
-        auto wgrad_part = [&, lp, lws, head_chained, dz_cur, dz_ld, act_in]() -> int {
-            const Layer& l = *lp;
-            int rc = ISDQN_OK;
-            int w_slabs;
-            bool fused_adam = false;
-            if (head_chained && ss) {  // enqueued by run_head_deferred()
-                add_entry_on(1, l.w_off, l.w_size, ws + l.gw_off, effective_splits(B, l.gw_slabs), l.w_size);
-                return ISDQN_OK;
-            }
-            if (l.kind == 0) {
-                int img_slabs = 0;
-                rc = conv_wgrad_img(l, x3, in, act_in, dz_cur, ws + l.gw_off, B, lws, &img_slabs);
-                if (rc) return rc;
-                if (img_slabs) {
-                    w_slabs = img_slabs;
-                } else {
-                if (l.is_u8) rc = x3 ? launch_conv_wgrad<2, true>(l, in, act_in, dz_cur, ws + l.gw_off, B, lws)
-                                     : launch_conv_wgrad<1, true>(l, in, act_in, dz_cur, ws + l.gw_off, B, lws);
-                else rc = x3 ? launch_conv_wgrad<3, false>(l, in, act_in, dz_cur, ws + l.gw_off, B, lws)
-                             : launch_conv_wgrad<1, false>(l, in, act_in, dz_cur, ws + l.gw_off, B, lws);
-                w_slabs = conv_wgrad_slabs(l, B);
-                }
-            } else {
-                // dW[out][in_p] = sum_b dz[b][out] * a[b][in_p] : both operands stored [K = b][rows]
-                MatSrc A{dz_cur, dz_ld, B, l.out_p, 1};
-                MatSrc Bm = l.in_unpadded_ld ? MatSrc{in.obs, l.in_unpadded_ld, B, l.in_f, 0}
-                                             : MatSrc{act_in, l.in_p, B, l.in_p, 1};
-                w_slabs = effective_splits(B, l.gw_slabs);
-                if (w_slabs == 1 && !l.in_unpadded_ld) {
-                    fused_adam = true;  // (a gradient-only pass runs the same kernel with the stores of p / m / v switched off)
-
-                    AdamFuse af{params + l.w_off, adam_m + l.w_off, adam_v + l.w_off, ws + P.adam_tab_off,
-                                cfg->learning_rate, cfg->adam_b1, cfg->adam_b2, cfg->adam_eps,
-                                grad_out ? grad_out + l.w_off : nullptr, ws + P.wsplit_off + l.w_off, update ? 1 : 0};
-                    // 64x64 tiles: the contraction is only B deep, the kernel lives off streaming p/m/v through the Adam
-                    // epilogue, and 128x128 tiles would leave 100 workgroups for 256 CUs
-                    // (operands: dz of a hidden layer -- or the fp32 dL/dq of the head -- and the S8 activations below it)
-                    if (l.is_head)
-                        rc = x3 ? launch_plain<64, 64, 2, 2, true, true, 3, true, false, true, 2>(A, nullptr, 0, Bm, nullptr, l.in_p,
-                                                                                                 l.out_p, l.in_p, B, 1, 0, lws, &af)
-                                : launch_plain<64, 64, 2, 2, true, true, 1, true, false, true, 2>(A, nullptr, 0, Bm, nullptr, l.in_p,
-                                                                                                 l.out_p, l.in_p, B, 1, 0, lws, &af);
-                    else
-                        rc = x3 ? launch_plain<64, 64, 2, 2, true, true, 3, true, false, true, DZ_S8 | 2>(A, nullptr, 0, Bm, nullptr, l.in_p,
-                                                                                                         l.out_p, l.in_p, B, 1, 0, lws, &af)
-                                : launch_plain<64, 64, 2, 2, true, true, 1, true, false, true, DZ_S8 | 2>(A, nullptr, 0, Bm, nullptr, l.in_p,
-                                                                                                         l.out_p, l.in_p, B, 1, 0, lws, &af);
-                } else if (l.in_unpadded_ld) {  // fc first layer: caller's fp32 observations
-                    rc = plain_big<true, true, false, false, DZ_S8>(x3, A, nullptr, 0, Bm, ws + l.gw_off, l.in_p, l.out_p, l.in_p, B,
-                                                                    l.gw_slabs, l.w_size, lws);
-                } else if (l.is_head) {         // dL/dq is fp32, the hidden activations are S8
-                    rc = plain_big<true, true, true, false, 2>(x3, A, nullptr, 0, Bm, ws + l.gw_off, l.in_p, l.out_p, l.in_p, B,
-                                                               l.gw_slabs, l.w_size, lws);
-                } else {
-                    rc = plain_big<true, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, ws + l.gw_off, l.in_p, l.out_p, l.in_p, B,
-                                                                       l.gw_slabs, l.w_size, lws);
-                }
-            }
-            if (rc) return rc;
-            if (!fused_adam) add_entry_on(lws == wst && ss ? 1 : 0, l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size);
-            return ISDQN_OK;
-        };
-        if (defer_side) {
-            hipEvent_t e = defer_event;
-            deferred = [&, e, lws, wgrad_part]() -> int {
-                ISDQN_HIP_CHECK(hipStreamWaitEvent(lws, e, 0));
-                if (int r = run_head_deferred(lws)) return r;
-                return wgrad_part();
-            };
-        } else {
-            rc = wgrad_part();
-            if (rc) return rc;
-        }
-    }
-    if (deferred) {
-        auto f = std::move(deferred);
-        deferred = nullptr;
-        rc = f();
-        if (rc) return rc;
-    }
-    if (head_deferred) {  // no layer forked: keep the two kernels in line
-        rc = run_head_deferred(st);
-        if (rc) return rc;
-    }
-    rc = signal_priorities();
+    rc = learn_forward(c);
     if (rc) return rc;
-    auto run_adam = [&](const AdamTable& tab, hipStream_t s2) -> int {
-        if (tab.n == 0) return ISDQN_OK;
-        hipLaunchKernelGGL(adam_kernel, dim3(tab.total_blocks), dim3(256), 0, s2, tab, params, adam_m, adam_v, ws + P.adam_tab_off,
-                           cfg->learning_rate, cfg->adam_b1, cfg->adam_b2, cfg->adam_eps, grad_out, ws + P.wsplit_off, update ? 1 : 0);
-        ISDQN_HIP_CHECK(hipGetLastError());
-        return ISDQN_OK;
-    };
-    // The weight-gradient stream may update its own tensors only when every reader of the weights is behind it: with the
-    // tail swap its last kernel (layer 0's weight gradient) waited for the last data gradient of the caller's stream.
-    const bool adam_on_side = ss && forked && tail_swap;
-    if (adam_on_side) {
-        rc = run_adam(tabs[1], wst);
-        if (rc) return rc;
-    } else if (ss) {  // all weight gradients done before Adam
-        rc = chain(ss, wst, st);
-        if (rc) return rc;
-    }
-    if (red_jobs.n > 0) {
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3(red_jobs.block_start[red_jobs.n]), dim3(256), 0, st, red_jobs);
-        ISDQN_HIP_CHECK(hipGetLastError());
-    }
-    rc = run_adam(tabs[0], st);
+    rc = learn_loss(c);
     if (rc) return rc;
-    if (adam_on_side) {  // the call is complete on the caller's stream (and the next call may touch the workspace)
-        rc = chain(ss, wst, st);
-        if (rc) return rc;
-    } else {
-        rc = run_adam(tabs[1], st);
-        if (rc) return rc;
+    if (!learn) {
+        if (batch->priorities_ready != nullptr) ISDQN_HIP_CHECK(hipEventRecord((hipEvent_t)batch->priorities_ready, c.st));
+        return ISDQN_OK;
     }
-    return ISDQN_OK;
+    AdamList adam[2];  // [0] caller's stream, [1] weight-gradient stream
+    ReduceJobs red;    // partial-row reductions left by the fused data gradients (one launch before Adam)
+    red.n = 0;
+    red.block_start[0] = 0;
+    BackwardSchedule sched(c, adam);
+    rc = sched.begin();
+    if (rc) return rc;
+    rc = learn_backward(c, sched, adam, &red);
+    if (rc) return rc;
+    return learn_optimizer(c, sched, adam, red);
 }
 
 extern "C" int isdqn_net_learn_on_batch(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v,

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # Which kernel updates which tensor (net_plan.h: dense weight-gradient slabs s = 1 from 128 output tiles of 128 x 128, else 256 / tiles
-# capped at ceil(B / 32) K steps; net_kernels.hip learn_or_loss: fused Adam when effective_splits(B, s) == 1 and the input is not the
+# capped at ceil(B / 32) K steps; net_kernels.hip weight_gradient: fused Adam when effective_splits(B, s) == 1 and the input is not the
 # caller's fp32 observations; the head takes the head chain in every learn step with a ReLU hidden layer up to 2048 wide):
 #   headline, B = 32 and B = 64: Dense_0 (512 x 7744 after SAME padding: 4 x 61 = 244 tiles, s = 1) -> FUSED epilogue at both sizes
 #     (one and two K steps of the contraction inside the one slab); the head (Dense_1) -> head chain, slabs + adam_kernel at both;
