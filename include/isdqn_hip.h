@@ -203,6 +203,32 @@ typedef struct isdqn_net_config {
                                            * would flatten prioritized replay).  Not with huber_delta > 0 (ISDQN_ERR_ARG) nor with
                                            * batch_norm (ISDQN_ERR_UNSUPPORTED).                                                    */
     float hl_min, hl_max, hl_sigma;       /* n_bins > 0: support [hl_min, hl_max] (hl_max > hl_min) and sigma > 0; ignored at 0 */
+    int32_t double_q;                     /* 0: the bootstrap value is max_a' Q(s', a') of the value head (the reference; every result
+                                           * keeps the bits it had before the field existed).  1: Double Q-learning (van Hasselt et al.
+                                           * 2016).  Anything else: ISDQN_ERR_ARG.  THE definition: for every regressed pair k < K with
+                                           * value head v = target_head + k and selector head s = online_head + k (iS-DQN: v = k,
+                                           * s = 1 + k; grad_on_batch with n_pairs > 0: the heads the caller names),
+                                           *     a*_bk     = the FIRST index attaining max_a Q^sel_s(s'_b, a)
+                                           *     target_bk = r_b + (1 - terminal_b) * gamma^n * Q^val_v(s'_b, a*_bk)
+                                           * Q^val is the network that supplies the next-state value with double_q = 0: the same
+                                           * parameters, or `target_params` in the *_target forms and in grad_on_batch.  Q^sel is always
+                                           * the ONLINE parameters applied to the next states (iS-DQN: the head being learned selects, the
+                                           * head it is regressed on evaluates, both in the rows of the one forward; DQN: the textbook
+                                           * Double DQN, which costs one more forward -- the target parameters over the B next states into
+                                           * the workspace region "q_target", then the online parameters over concat(state, next_state)).
+                                           * No gradient flows through either.  The tie rule is isdqn_net_best_action's: strict >, the
+                                           * lowest index wins.  Everything behind the target is unchanged: q_values, the squared / Huber
+                                           * / HL-Gauss loss, loss_weights, dL/dq, the priorities (the raw TD error on these targets),
+                                           * losses_accum, priorities_ready.  With n_bins > 0 selector and value are the expectations
+                                           * sum_j softmax(l)_j c_j; `targets` stays the unclamped scalar.  Where selector and value are
+                                           * the same head of the same rows (a single head without target_params: TF-DQN) Q[argmax Q] ==
+                                           * max Q and the result has the bits of double_q = 0.  batch_norm: supported without
+                                           * target_params (both heads lie in the rows of the training-mode forward); with target_params
+                                           * ISDQN_ERR_UNSUPPORTED (the reference defines no statistics for an online forward of the next
+                                           * states alone).  The workspace regions "q_target" ([B][n_heads * A padded to 8]; histogram
+                                           * heads: also "logits_target") exist only with double_q = 1, behind every other region.  With
+                                           * histogram heads the loss takes the value expectation from "logits_target" itself;
+                                           * "q_target" then holds the same expectations for the caller to read (informational).     */
 } isdqn_net_config;
 
 /* One parameter tensor inside the flat fp32 parameter buffer.  `name` is the Flax

@@ -365,7 +365,8 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
     float* qv = q_values ? q_values : ws + P.qv_off;
     float* tg = targets ? targets : ws + P.tg_off;
     // (BatchNorm networks never have histogram heads: the TD loss, and nlog_p == nha_p)
-    rc = loss_and_finalize(P, cfg, ws, batch, K, on0, tg0, learn, (learn && update) ? adam_count : nullptr, qv, tg, priorities, losses, loss_accum, st);
+    rc = loss_and_finalize(P, cfg, ws, batch, K, on0, tg0, learn, (learn && update) ? adam_count : nullptr, qv, tg, priorities, losses, loss_accum, st,
+                           /*double_q=*/cfg->double_q != 0 && target_params == nullptr && on0 != tg0);  // (with target_params: refused by the caller)
     if (rc) return rc;
     if (batch->priorities_ready != nullptr) ISDQN_HIP_CHECK(hipEventRecord((hipEvent_t)batch->priorities_ready, st));
     if (!learn) return ISDQN_OK;

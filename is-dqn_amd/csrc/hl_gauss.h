@@ -75,12 +75,15 @@ __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict_
 //   u_i = erf((e_i - y) / (sqrt(2) sigma)),  p_j = (u_{j+1} - u_j) / (u_nb - u_0)   (the clamp keeps u_nb - u_0 away from 0/0)
 //   CE = w_b (logsumexp(l) - sum_j p_j l_j),  dL/dl_j = w_b (softmax(l)_j - p_j) / B on the taken action's nb logits, 0 elsewhere
 //   (w_b: isdqn_batch.loss_weights, 1 without).
+// `vlogits`: the value rows of the B next states (pitch nlog_p).  `slogits` != null (isdqn_net_config::double_q): max_a' becomes the
+// value head's expectation at the first argmax of the expectations of head sh + k of the selector rows (pitch s_pitch).
 // Writes q_values / targets [B][K] (expectation, unclamped scalar target), priorities[B] = sqrt(mean_k (q - target)^2 + 1e-10) --
 // the expectations' TD error, not the CE (which never falls below the target histogram's entropy) -- per-workgroup partials of the
 // per-pair CE sums (loss_part [n_blk][K]) and, with `dout`, the dL/dlogits rows (zero-filled) and their column sums over the
 // workgroup's rows (dbh_part [n_blk][nlog_p], the head-bias gradient); loss_finalize_kernel reduces both in a fixed order.
 // Dynamic LDS: R * K * nb floats of dL/dl.
-__global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ logits, int B, int R, int K, int on0, int tg0, int A,
+__global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ logits, const float* __restrict__ vlogits,
+                                                      const float* __restrict__ slogits, int s_pitch, int sh, int B, int R, int K, int on0, int tg0, int A,
                                                       int nb, int nlog_p, float vmin, float eta, float sigma,
                                                       const int* __restrict__ action, const float* __restrict__ reward,
                                                       const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
@@ -115,9 +118,22 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ 
             continue;
         }
         const int b = b0 + bl;
-        const float* nrow = logits + (int64_t)(B + b) * nlog_p + (int64_t)(tg0 + k) * ldk;
+        const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(tg0 + k) * ldk;
         float mx = -INFINITY;
-        for (int a2 = 0; a2 < A; ++a2) mx = fmaxf(mx, hl_expectation(nrow + (int64_t)a2 * nb, nb, lane, vmin, eta));
+        if (slogits != nullptr) {  // Double Q-learning: first argmax of the selector head's expectations, valued by the value head
+            const float* srow = slogits + (int64_t)b * s_pitch + (int64_t)(sh + k) * ldk;
+            ISDQN_BOUNDS_CHECK(srow + min(lane, ldk - 1), 4, 30);
+            ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 30);
+            int best = 0;
+            float bv = hl_expectation(srow, nb, lane, vmin, eta);
+            for (int a2 = 1; a2 < A; ++a2) {
+                const float x = hl_expectation(srow + (int64_t)a2 * nb, nb, lane, vmin, eta);
+                if (x > bv) { bv = x; best = a2; }
+            }
+            mx = hl_expectation(nrow + (int64_t)best * nb, nb, lane, vmin, eta);
+        } else {
+            for (int a2 = 0; a2 < A; ++a2) mx = fmaxf(mx, hl_expectation(nrow + (int64_t)a2 * nb, nb, lane, vmin, eta));
+        }
         const float tg = s_r[bl] + s_nt[bl] * gamma_n * mx;
         float v[HL_PER_LANE], e[HL_PER_LANE], s, w;
         const float m = hl_softmax_parts(logits + (int64_t)b * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * nb, nb, lane,

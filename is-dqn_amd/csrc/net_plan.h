@@ -98,6 +98,10 @@ struct Plan {
     int64_t n_params;
     // workspace (float offsets unless noted)
     int64_t q_off, logits_off, out_off, dout_off, da_off, slab_off, qv_off, tg_off, dbh_off, adam_tab_off, lpart_off;
+    // Double Q-learning (cfg->double_q), forms with separate target parameters: head output of the target network on the B next
+    // states (q_target: Q rows [B][nha_p]; histogram heads: logits_target [B][nlog_p], q_target their expectations).  -1 without
+    int double_q;
+    int64_t qt_off, logits_t_off, out_t_off;
     int64_t wsplit_off;  // S8 mirror of the parameter buffer (same offsets as the fp32 master; weights only are read from it)
     int64_t slab_floats, da_floats;
     int64_t ws_bytes;
@@ -123,6 +127,7 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
                   "bad precision");
     ISDQN_REQUIRE(cfg->huber_delta >= 0.f, ISDQN_ERR_ARG, "huber_delta must be >= 0 (0 = squared error)");
     ISDQN_REQUIRE(cfg->batch_norm == 0 || cfg->batch_norm == 1, ISDQN_ERR_ARG, "batch_norm must be 0 or 1");
+    ISDQN_REQUIRE(cfg->double_q == 0 || cfg->double_q == 1, ISDQN_ERR_ARG, "double_q must be 0 or 1");
     ISDQN_REQUIRE(cfg->n_bins == 0 || (cfg->n_bins >= 2 && cfg->n_bins <= 256), ISDQN_ERR_ARG, "n_bins must be 0 (off) or in [2, 256]");
     if (cfg->n_bins > 0) {
         ISDQN_REQUIRE(cfg->hl_max > cfg->hl_min, ISDQN_ERR_ARG, "histogram loss: hl_max must be > hl_min");
@@ -531,6 +536,11 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.adam_tab_off = region("adam_consts", 64);
     P.lpart_off = region("loss_partials", (int64_t)P.B * (P.K + P.nlog_p));
     P.wsplit_off = region("wsplit", P.n_params);
+    // (appended: a configuration without the option keeps every offset and the total it had)
+    P.double_q = cfg->double_q;
+    P.qt_off = P.double_q ? region("q_target", (int64_t)P.B * P.nha_p) : -1;
+    P.logits_t_off = (P.double_q && P.hl_nb > 0) ? region("logits_target", (int64_t)P.B * P.nlog_p) : -1;
+    P.out_t_off = P.hl_nb > 0 ? P.logits_t_off : P.qt_off;
     P.ws_bytes = off * 4;
     return ISDQN_OK;
 }

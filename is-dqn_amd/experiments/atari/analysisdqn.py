@@ -47,6 +47,7 @@ def run(argvs=sys.argv[1:], root=None):
         batch_size=p["batch_size"],
         precision=p["precision"],
         **histogram_loss_kwargs(p),
+        double_q=p["double_q"],
         huber_delta=p["huber_delta"],
     )
     if p["prioritized"]:

@@ -50,6 +50,7 @@ _ENGINE = [
     ("-minn", "--min_value", dict(type=float, default=-100, help="Value of the lowest learnable value of the target.")),
     ("-maxn", "--max_value", dict(type=float, default=100, help="Value of the highest learnable value of the target.")),
     ("-sigma", "--sigma", dict(type=float, default=3, help="Standard deviation of each target sample. If sigma / eta = 0.75, then sigma = 0.75 * (max_value - min_value) / n_bins")),
+    ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
     ("-nenvs", "--n_envs", dict(type=int, default=1, help="Host environments stepped in lockstep with one batched best_actions forward (1 = the reference's loop).")),
     ("-nworkers", "--n_env_workers", dict(type=int, default=0, help="Host worker processes stepping the -nenvs environments in parallel (0 = in this process).")),
     ("-env", "--env_backend", dict(type=str, default="ale", choices=["ale", "synthetic"], help="'synthetic' replaces ALE by random frames (no ROMs needed).")),
@@ -91,6 +92,18 @@ def add_engine_arguments(parser: argparse.ArgumentParser) -> List[str]:
 
 
 PRIORITIZED_FLAGS = ["priority_exponent", "is_beta", "is_beta_end"]  # stored in parameters.json with the algorithm's flags under -per
+
+
+DOUBLE_Q_FLAGS = ["double_q"]  # stored with the algorithm's flags under -dq
+TARGET_FREE_ALGOS = ("tfdqn", "analysistfdqn")
+
+
+def check_double_q(p: dict, algo_name: str) -> None:
+    """-dq on a target-free agent fails before anything is written, with the agent's own message."""
+    if p.get("double_q") and algo_name in TARGET_FREE_ALGOS:
+        from slimdqn.networks.tfdqn import DOUBLE_Q_REFUSED
+
+        raise ValueError(DOUBLE_Q_REFUSED)
 
 
 def check_engine_arguments(p: dict) -> None:

@@ -45,6 +45,7 @@ def run(argvs=sys.argv[1:], root=None):
         batch_size=p["batch_size"],
         precision=p["precision"],
         **histogram_loss_kwargs(p),
+        double_q=p["double_q"],
     )
     out = train(np.random.default_rng(train_seed), p, agent, env, rb)
     replicas.finalize()

@@ -42,6 +42,7 @@ class QNetEngine:
         min_value: float = -100.0,
         max_value: float = 100.0,
         sigma: float = 3.0,
+        double_q: bool = False,
     ):
         _hip.require_gpu()
         self.lib = _hip.lib()
@@ -82,6 +83,10 @@ class QNetEngine:
         cfg.n_bins = int(n_bins)
         cfg.hl_min, cfg.hl_max, cfg.hl_sigma = (float(min_value), float(max_value), float(sigma)) if n_bins else (0.0, 0.0, 0.0)
         self.n_bins = int(n_bins)
+        # Double Q-learning targets (include/isdqn_hip.h, isdqn_net_config::double_q); the *_target forms then keep the target
+        # network's rows in region "q_target"
+        cfg.double_q = 1 if double_q else 0
+        self.double_q = bool(double_q)
         self.cfg = cfg
         self.features = feats
         self.architecture_type = architecture_type

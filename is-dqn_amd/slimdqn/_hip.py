@@ -48,6 +48,7 @@ class NetConfig(ctypes.Structure):
         ("hl_min", c_float),
         ("hl_max", c_float),
         ("hl_sigma", c_float),
+        ("double_q", c_int32),  # 0: max_a' Q(s', a'); 1: Double Q-learning targets (include/isdqn_hip.h)
     ]
 
 

@@ -104,8 +104,9 @@ class EngineAgent:
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
-                           n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0):
+                           n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0, double_q=False):
         self.n_actions = n_actions
+        self.double_q = bool(double_q)
         self.batch_norm = bool(batch_norm)
         self._n_heads = int(n_heads)
         self.features = [int(f) for f in features]
@@ -135,6 +136,7 @@ class EngineAgent:
             self.layer_norm, batch_size, gamma_n=self.gamma**self.update_horizon, learning_rate=self.learning_rate,
             adam_eps=self.adam_eps, precision=self.precision, device=self.device, huber_delta=self.huber_delta, batch_norm=self.batch_norm,
             n_bins=self.n_bins, min_value=self.min_value, max_value=self.max_value, sigma=self.sigma,
+            double_q=self.double_q,
         )
         if init:
             eng.init_params(self._seed)

@@ -22,6 +22,11 @@ from slimdqn.networks.isdqn import iSDQN
 class AnalysisDQN(iSDQN):
     def __init__(self, *args, **kwargs):
         kwargs["use_graph"] = False  # every update reads diagnostics back: nothing to capture
+        # its target-based gradient takes separate target parameters, which BatchNorm networks refuse with double_q
+        # (include/isdqn_hip.h): said here, before an engine is built
+        batch_norm = kwargs["batch_norm"] if "batch_norm" in kwargs else (args[6] if len(args) > 6 else False)
+        if kwargs.get("double_q", False) and batch_norm:
+            raise NotImplementedError("AnalysisDQN: double_q with batch_norm is not built (ISDQN_ERR_UNSUPPORTED with target parameters)")
         super().__init__(*args, **kwargs)
         self.target_params = self.params.clone()  # analysisdqn.py:49
         K = self.n_bellman_iterations

@@ -37,8 +37,11 @@ class DQN(EngineAgent):
         min_value: float = -100.0,
         max_value: float = 100.0,
         sigma: float = 3.0,
+        double_q: bool = False,
     ):
-        """``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
+        """``double_q``: Double DQN (van Hasselt et al. 2016) -- the online parameters pick the next action, the target parameters
+        value it (include/isdqn_hip.h, isdqn_net_config::double_q): one more forward per step.
+        ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, n_actions * max(int(n_bins), 1), layer_norm, False)
         self.data_to_update = data_to_update
@@ -46,7 +49,7 @@ class DQN(EngineAgent):
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
-                                max_value=max_value, sigma=sigma)
+                                max_value=max_value, sigma=sigma, double_q=double_q)
         self.target_params = self.params.copy()  # dqn.py:34
         self.cumulated_loss = 0
 

@@ -51,8 +51,11 @@ class iSDQN(EngineAgent):
         min_value: float = -100.0,
         max_value: float = 100.0,
         sigma: float = 3.0,
+        double_q: bool = False,
     ):
-        """``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss.
+        """``double_q``: Double Q-learning targets -- online head 1 + k picks the next action that head k values
+        (include/isdqn_hip.h, isdqn_net_config::double_q); off keeps the reference's max.
+        ``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss.
         ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
         cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
         self.n_bellman_iterations = n_bellman_iterations
@@ -67,7 +70,7 @@ class iSDQN(EngineAgent):
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
-                                n_bins, min_value, max_value, sigma)
+                                n_bins, min_value, max_value, sigma, double_q)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 

@@ -12,6 +12,12 @@ from slimdqn.networks._agent import EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
+DOUBLE_Q_REFUSED = (
+    "double_q has no effect on target-free DQN: its single head both selects and values the next action through the same "
+    "parameters, so Q[argmax Q] == max Q and the update would be the one without the option; use DQN or iSDQN for Double "
+    "Q-learning targets")
+
+
 class TFDQN(EngineAgent):
     def __init__(
         self,
@@ -36,8 +42,12 @@ class TFDQN(EngineAgent):
         min_value: float = -100.0,
         max_value: float = 100.0,
         sigma: float = 3.0,
+        double_q: bool = False,
     ):
-        """``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
+        """``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h).
+        ``double_q`` is refused: see DOUBLE_Q_REFUSED."""
+        if double_q:
+            raise ValueError(DOUBLE_Q_REFUSED)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, n_actions * max(int(n_bins), 1), layer_norm, batch_norm)
         self.data_to_update = data_to_update
