@@ -172,6 +172,43 @@ typedef struct isdqn_net_config {
     float huber_delta;                    /* 0: squared TD error, the reference's loss (isdqn.py:102); > 0: Huber loss with
                                            * this delta (0.5 d^2 for |d| <= delta, delta (|d| - delta/2) beyond; the north
                                            * star's wording), gradient clip(d, -delta, delta)                */
+    float munchausen_tau, munchausen_alpha, munchausen_clip;
+                                          /* (behind huber_delta, with the other options of the target and the loss: the
+                                           * struct still ends in double_q.)  Munchausen targets (Vieillard, Pietquin, Geist,
+                                           * "Munchausen Reinforcement Learning", NeurIPS 2020).  munchausen_tau == 0: off -- the other two fields are ignored and every result keeps
+                                           * the bits it had before the fields existed.  munchausen_tau > 0: on.  tau < 0 or non-finite,
+                                           * alpha outside [0, 1], clip > 0 or non-finite: ISDQN_ERR_ARG; double_q = 1 together with
+                                           * tau > 0: ISDQN_ERR_ARG (the soft value has no argmax to decouple).  THE definition, with
+                                           * tau = munchausen_tau, alpha = munchausen_alpha, l0 = munchausen_clip: for every regressed
+                                           * pair k < K with value head v = target_head + k (iS-DQN: v = k; grad_on_batch with
+                                           * n_pairs > 0: the heads the caller names),
+                                           *     V(x)      = m + tau * log( sum_a exp((Q^val_v(x, a) - m) / tau) ),  m = max_a Q^val_v(x, a)
+                                           *     bonus_bk  = alpha * clip( Q^val_v(s_b, a_b) - V(s_b), l0, 0 )
+                                           *                                             ( = alpha * clip(tau ln pi(a_b|s_b), l0, 0) )
+                                           *     target_bk = r_b + bonus_bk + (1 - terminal_b) * gamma^n * V(s'_b)
+                                           *                                             ( V(s') = sum_a' pi(a'|s') (Q - tau ln pi)(s', a') )
+                                           * with pi = softmax(Q^val_v / tau).  Q^val is the network that supplies the next-state value
+                                           * with the option off: the same parameters, or `target_params` in the *_target forms and in
+                                           * grad_on_batch -- on the STATE rows (the bonus) as well as on the next-state rows.  With the
+                                           * same parameters both are rows of the one forward over concat(state, next_state); with
+                                           * target_params the target parameters run over all 2B rows into the workspace region
+                                           * "q_target" ([2B][n_heads * A padded to 8]; histogram heads: "logits_target", "q_target" its
+                                           * expectations), then the online parameters over the B states.  `terminal` does not mask the
+                                           * bonus.  With update_horizon > 1 r_b is the n-step return the replay delivers and the bonus
+                                           * is that of the FIRST action only: the batch carries no other action.  No gradient flows
+                                           * through any Q^val term, the state-row term included, even where that head is itself being
+                                           * learned in another pair: dL/dq keeps exactly one non-zero per (transition, pair), at
+                                           * (online_head + k, a_b).  Everything behind the target is unchanged: q_values, the squared /
+                                           * Huber / HL-Gauss loss, loss_weights, the priorities (the raw TD error on these targets),
+                                           * losses_accum, priorities_ready.  alpha = 0 gives soft-DQN targets.  Acting (best_action[s])
+                                           * is unchanged: greedy on Q, as the paper's M-DQN.  With n_bins > 0 Q means the expectations
+                                           * sum_j softmax(l)_j c_j; `targets` stays the unclamped scalar.  A single head without
+                                           * target_params (TF-DQN) is regularised by its own stop-gradient policy: supported.
+                                           * batch_norm: supported without target_params (both halves are rows of the training-mode
+                                           * forward); with target_params ISDQN_ERR_UNSUPPORTED.  The regions "q_target" /
+                                           * "logits_target" hold [2B] rows with tau > 0 ([B] with double_q = 1) and exist only with one
+                                           * of the two options, behind every other region: an off configuration's workspace keeps its
+                                           * size and offsets.                                                                          */
     int32_t batch_norm;                   /* 0/1 (dqn.py:52-53, 59-60, 66-67, 73-74, 100-101): flax.linen.BatchNorm behind the
                                            * input scaling and behind every hidden layer's ReLU -- `axis=(1, 2)` on image
                                            * tensors (statistics per pixel position over batch AND channels), per feature on

@@ -58,6 +58,26 @@ __device__ __forceinline__ float hl_expectation(const float* __restrict__ l, int
     return w / s;
 }
 
+// Soft value tau log(sum_a exp(Q_a / tau)) of the A expectations of one head's logits at `row` (munchausen.h: the maximum is
+// subtracted first); *picked = the expectation of action a_pick.  One pass over the actions, every expectation computed once: the
+// running sum is rescaled whenever the running maximum moves (exponents stay <= 0, so tau = 0.03 with |Q| in the hundreds neither
+// overflows nor returns -inf; the first action finds s = 0, m = -inf and leaves s = 1).
+__device__ __forceinline__ float hl_soft_value(const float* __restrict__ row, int A, int nb, int lane, float vmin, float eta, float tau,
+                                               int a_pick, float* picked) {
+    float m = -INFINITY, s = 0.f;
+    for (int a2 = 0; a2 < A; ++a2) {
+        const float x = hl_expectation(row + (int64_t)a2 * nb, nb, lane, vmin, eta);
+        if (a2 == a_pick) *picked = x;
+        if (x > m) {
+            s = s * expf((m - x) / tau) + 1.f;
+            m = x;
+        } else {
+            s += expf((x - m) / tau);
+        }
+    }
+    return m + tau * logf(s);
+}
+
 // q[row][c] = Q of column c = h * A + a (c < nha) from logits[row][c * nb .. c * nb + nb); the padding columns of q are not written.
 __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict__ logits, int n_rows, int nha, int nb, int nlog_p,
                                                         int nha_p, float vmin, float eta, float* __restrict__ q) {
@@ -77,13 +97,16 @@ __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict_
 //   (w_b: isdqn_batch.loss_weights, 1 without).
 // `vlogits`: the value rows of the B next states (pitch nlog_p).  `slogits` != null (isdqn_net_config::double_q): max_a' becomes the
 // value head's expectation at the first argmax of the expectations of head sh + k of the selector rows (pitch s_pitch).
+// `mlogits` != null (isdqn_net_config::munchausen_tau > 0, munchausen.h): the target is the Munchausen one on the expectations of
+// the value head -- head mh + k of the STATE rows `mlogits` (pitch m_pitch) for the bonus, the soft value of the value rows.
 // Writes q_values / targets [B][K] (expectation, unclamped scalar target), priorities[B] = sqrt(mean_k (q - target)^2 + 1e-10) --
 // the expectations' TD error, not the CE (which never falls below the target histogram's entropy) -- per-workgroup partials of the
 // per-pair CE sums (loss_part [n_blk][K]) and, with `dout`, the dL/dlogits rows (zero-filled) and their column sums over the
 // workgroup's rows (dbh_part [n_blk][nlog_p], the head-bias gradient); loss_finalize_kernel reduces both in a fixed order.
 // Dynamic LDS: R * K * nb floats of dL/dl.
 __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ logits, const float* __restrict__ vlogits,
-                                                      const float* __restrict__ slogits, int s_pitch, int sh, int B, int R, int K, int on0, int tg0, int A,
+                                                      const float* __restrict__ slogits, int s_pitch, int sh, const float* mlogits, int m_pitch,
+                                                      int mh, Munchausen mu, int B, int R, int K, int on0, int tg0, int A,
                                                       int nb, int nlog_p, float vmin, float eta, float sigma,
                                                       const int* __restrict__ action, const float* __restrict__ reward,
                                                       const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
@@ -120,7 +143,17 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ 
         const int b = b0 + bl;
         const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(tg0 + k) * ldk;
         float mx = -INFINITY;
-        if (slogits != nullptr) {  // Double Q-learning: first argmax of the selector head's expectations, valued by the value head
+        float tg_m = 0.f;
+        if (mlogits != nullptr) {  // Munchausen: bonus from the value head's state row, soft value of its next-state row
+            const float* srow = mlogits + (int64_t)b * m_pitch + (int64_t)(mh + k) * ldk;
+            ISDQN_BOUNDS_CHECK(srow + min(lane, ldk - 1), 4, 31);
+            ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 31);
+            float qa = 0.f, unused;
+            const float vs = hl_soft_value(srow, A, nb, lane, vmin, eta, mu.tau, s_action[bl], &qa);
+            const float vn = hl_soft_value(nrow, A, nb, lane, vmin, eta, mu.tau, -1, &unused);
+            tg_m = munchausen_target(s_r[bl], s_nt[bl], gamma_n, qa, vs, vn, mu);
+            mx = 0.f;
+        } else if (slogits != nullptr) {  // Double Q-learning: first argmax of the selector head's expectations, valued by the value head
             const float* srow = slogits + (int64_t)b * s_pitch + (int64_t)(sh + k) * ldk;
             ISDQN_BOUNDS_CHECK(srow + min(lane, ldk - 1), 4, 30);
             ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 30);
@@ -134,7 +167,7 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ 
         } else {
             for (int a2 = 0; a2 < A; ++a2) mx = fmaxf(mx, hl_expectation(nrow + (int64_t)a2 * nb, nb, lane, vmin, eta));
         }
-        const float tg = s_r[bl] + s_nt[bl] * gamma_n * mx;
+        const float tg = mlogits != nullptr ? tg_m : s_r[bl] + s_nt[bl] * gamma_n * mx;
         float v[HL_PER_LANE], e[HL_PER_LANE], s, w;
         const float m = hl_softmax_parts(logits + (int64_t)b * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * nb, nb, lane,
                                          vmin, eta, v, e, &s, &w);

@@ -13,6 +13,7 @@
 #include "conv_img.h"
 #include "conv_u8_pair.h"
 #include "conv_s8_pair.h"
+#include "munchausen.h"
 #include "hl_gauss.h"
 #include "net_plan.h"
 #include "net_problems.h"
@@ -334,7 +335,9 @@ __global__ __launch_bounds__(256) void ln_bwd_wide_kernel(const float* __restric
 // bias gradient (column sums of dout); loss_finalize_kernel reduces them in a fixed order.
 // `vq`: the value rows of the B next states (pitch nha_p; rows [B, 2B) of `q`, or the target network's own rows).  `sq` != null:
 // Double Q-learning (isdqn_net_config::double_q) -- the value is taken at the first argmax of head sh + k of the selector rows
-// (pitch sq_pitch; they may come from another forward than the value rows); null: the max form.
+// (pitch sq_pitch; they may come from another forward than the value rows); null: the max form.  `mq` != null: Munchausen targets
+// (munchausen.h) -- the value head th + k (mh + k in `mq`) of the STATE rows `mq` (pitch mq_pitch; rows [0, B) of `q`, or the target
+// network's own rows) supplies the bonus, and the bootstrap value is the soft value of the value rows; null: off.
 // Per-element loss and its derivative w.r.t. q for d = q - target: squared error (the reference, isdqn.py:102) or, with
 // huber_delta > 0, the Huber loss (0.5 d^2 inside, delta (|d| - delta / 2) outside; derivative clip(d, -delta, delta)).
 __device__ __forceinline__ float td_loss(float d, float huber_delta) {
@@ -356,7 +359,8 @@ __device__ __forceinline__ int argmax_first(const float* v, int n) {
 }
 constexpr int TD_ROWS = 64;
 __global__ __launch_bounds__(256) void td_kernel(const float* __restrict__ q, const float* __restrict__ vq,
-                                                 const float* __restrict__ sq, int sq_pitch, int sh, int B, int K, int oh, int th, int A, int nha_p,
+                                                 const float* __restrict__ sq, int sq_pitch, int sh, const float* mq, int mq_pitch, int mh,
+                                                 Munchausen mu, int B, int K, int oh, int th, int A, int nha_p,
                                                  const int* __restrict__ action, const float* __restrict__ reward,
                                                  const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
                                                  float gamma_n, float huber_delta, float* __restrict__ dout,
@@ -399,6 +403,12 @@ __global__ __launch_bounds__(256) void td_kernel(const float* __restrict__ q, co
                 for (int j = 1; j < A; ++j) mx = fmaxf(mx, nq[j]);
             }
             float tg = r + nt * gamma_n * mx;
+            if (mq != nullptr) {
+                const float* sv = mq + (int64_t)b * mq_pitch + (mh + k) * A;
+                ISDQN_BOUNDS_CHECK(sv, 4 * A, 31);
+                ISDQN_BOUNDS_CHECK(nq, 4 * A, 31);
+                tg = munchausen_target(r, nt, gamma_n, sv[a], soft_value(sv, A, mu.tau), soft_value(nq, A, mu.tau), mu);
+            }
             d = qv - tg;
             td = td_loss(d, huber_delta);
             if (q_values) q_values[(int64_t)b * K + k] = qv;
@@ -466,6 +476,7 @@ struct HeadChainParams {
     const float* loss_weights;  // [B] importance-sampling weights, or null (weight 1)
     float gamma_n, huber_delta;
     int double_q;       // isdqn_net_config::double_q: head oh + k of the next-state row selects, head k values
+    Munchausen mu;      // isdqn_net_config::munchausen_*: head k of the state row gives the bonus, of the next-state row the soft value
     float* dout;        // [B][Op]  dL/dq
     float* dz;          // [B][Fp]
     float* part;        // [n_wg][3][Fp]
@@ -792,7 +803,11 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
             } else {
                 for (int j = 1; j < A; ++j) mx = fmaxf(mx, nq[j]);
             }
-            const float tg = td_r + (1.f - (float)td_term) * p.gamma_n * mx;
+            float tg = td_r + (1.f - (float)td_term) * p.gamma_n * mx;
+            if (p.mu.tau > 0.f) {  // the value head's own row of the state: head k, not oh + k
+                const float* sv = s_q + s * Op + k * A;
+                tg = munchausen_target(td_r, 1.f - (float)td_term, p.gamma_n, sv[a], soft_value(sv, A, p.mu.tau), soft_value(nq, A, p.mu.tau), p.mu);
+            }
             d = qv - tg;
             td = td_loss(d, p.huber_delta);
             if (p.q_values) p.q_values[(int64_t)b * K + k] = qv;
@@ -1746,11 +1761,16 @@ static int loss_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, 
 // targets, per-transition loss and dL/d(head output) of rows [0, B) from the head outputs of a finished forward (TD loss on the Q rows, or
 // the HL-Gauss loss on the logit rows), then loss_finalize over the head layer's width (nlog_p: nha_p without histogram heads).
 // `val_rows`: head-output rows [B][nlog_p] of the next states that supply the bootstrap value (null: rows [B, 2B) of the forward);
-// `double_q`: selector head on0 + k of rows [B, 2B) of the forward -- the online parameters on the next states -- picks the action
+// `double_q`: selector head on0 + k of rows [B, 2B) of the forward -- the online parameters on the next states -- picks the action;
+// Munchausen targets (cfg->munchausen_tau > 0): `state_val_rows`, head-output rows [B][nlog_p] of the states from the network that
+// supplies the value (null: rows [0, B) of the forward)
 static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, const isdqn_batch* batch, int K, int on0, int tg0, bool learn,
                              int32_t* adam_count, float* qv, float* tg, double* priorities, float* losses, float* loss_accum, hipStream_t st,
-                             bool double_q = false, const float* val_rows = nullptr) {
+                             bool double_q = false, const float* val_rows = nullptr, const float* state_val_rows = nullptr) {
     const int B = P.B;
+    const Munchausen mu{cfg->munchausen_tau, cfg->munchausen_alpha, cfg->munchausen_clip};
+    if (state_val_rows == nullptr) state_val_rows = ws + P.out_off;
+    const float* mun_rows = mu.tau > 0.f ? state_val_rows : nullptr;
     const float* next_rows = ws + P.out_off + (int64_t)B * P.nlog_p;
     if (val_rows == nullptr) val_rows = next_rows;
     const float* sel_rows = double_q ? next_rows : nullptr;
@@ -1760,12 +1780,12 @@ static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* 
     float* dbh_part = loss_part + (int64_t)n_blk * K;
     if (hl_R)
         hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.hl_nb * sizeof(float), st, ws + P.logits_off, val_rows,
-                           sel_rows, P.nlog_p, on0, B, hl_R, K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
+                           sel_rows, P.nlog_p, on0, mun_rows, P.nlog_p, tg0, mu, B, hl_R, K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
                            batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n,
                            learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
     else
         hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, val_rows, sel_rows,
-                           P.nha_p, on0, B, K, on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta,
+                           P.nha_p, on0, mun_rows, P.nha_p, tg0, mu, B, K, on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta,
                            learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
     ISDQN_HIP_CHECK(hipGetLastError());
     return loss_finalize(P, cfg, ws, n_blk, K, P.nlog_p, losses, loss_accum, learn, adam_count, st);
@@ -2057,6 +2077,7 @@ struct LearnCtx {
     SideStream* ss = nullptr;   // learn steps: the weight-gradient stream (nullptr: everything runs on the caller's stream)
     hipStream_t wst = nullptr;  // stream of the weight gradients: ss->stream, or st
     bool double_q = false;      // Double Q-learning targets (cfg->double_q, unless selector and value are the same head of the same rows)
+    bool munchausen = false;    // Munchausen targets (cfg->munchausen_tau > 0); excludes double_q (build_plan)
     int hc_S = 0, hc_wg = 0;    // head chain (head_chain_plan): transitions per workgroup, workgroups; 0 = generic loss and head backward
     const float* wmir() const { return ws + P.wsplit_off; }
     const Layer& hid() const { return P.L[P.n_layers >= 2 ? P.n_layers - 2 : 0]; }
@@ -2088,6 +2109,24 @@ static int learn_forward(const LearnCtx& c) {
     float* ws = c.ws;
     const int B = c.B;
     int rc;
+    if (c.target_params != nullptr && c.munchausen) {
+        // Munchausen DQN: the target parameters value the states too, so they run over concat(state, next_state) (2B rows of head
+        // output -> "q_target" / "logits_target", states first); then the online parameters over the B states, as the DQN form below
+        const int stack = c.cfg->arch != ISDQN_ARCH_FC ? c.cfg->obs_c : 0;
+        rc = refresh_mirror(P, c.target_params, ws, c.st);
+        if (rc) return rc;
+        rc = net_forward(P, c.x3, c.target_params, c.in, P.N2, 0, ws, ws + P.out_t_off, c.st);
+        if (rc) return rc;
+        if (P.hl_nb > 0) {
+            hipLaunchKernelGGL(hl_expect_kernel, dim3((unsigned)(((int64_t)P.N2 * P.nha + 3) / 4)), dim3(256), 0, c.st, ws + P.logits_t_off, P.N2,
+                               P.nha, P.hl_nb, P.nlog_p, P.nha_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, ws + P.qt_off);
+            ISDQN_HIP_CHECK(hipGetLastError());
+        }
+        rc = refresh_mirror(P, c.params, ws, c.st);
+        if (rc) return rc;
+        NetInput on{batch->frames, batch->frame_stride, batch->frame_ids, 0, batch->state, nullptr, 0, 2 * stack, 0};
+        return net_forward(P, c.x3, c.params, on, B, B, ws, ws + P.out_off, c.st);
+    }
     if (c.target_params != nullptr && c.double_q) {
         // Double DQN: the target parameters value the B next states (head output -> "q_target" / "logits_target"), then ONE forward
         // of the online parameters over concat(state, next_state) as the iS-DQN path runs it: its next-state rows select
@@ -2151,6 +2190,7 @@ static int launch_head_chain(const LearnCtx& c) {
     hp.loss_weights = c.batch->loss_weights;
     hp.gamma_n = c.cfg->gamma_n; hp.huber_delta = c.cfg->huber_delta;
     hp.double_q = c.double_q ? 1 : 0;
+    hp.mu = Munchausen{c.cfg->munchausen_tau, c.cfg->munchausen_alpha, c.cfg->munchausen_clip};
     hp.dout = ws + P.dout_off; hp.dz = ws + hid.dz_off; hp.part = ws + hid.part_off;
     hp.q_values = c.qv; hp.targets = c.tg; hp.priorities = c.priorities;
     hp.loss_part = ws + P.lpart_off; hp.dbh_part = hp.loss_part + (int64_t)c.hc_wg * c.K;
@@ -2192,10 +2232,13 @@ static int head_chain_tail(const LearnCtx& c, hipStream_t s) {
 
 // targets, loss, dL/dq: q_values / targets / priorities / per-head loss partials are final behind it
 static int learn_loss(const LearnCtx& c) {
+    // the target network's own head output ("q_target" / "logits_target": next states; Munchausen: states, then next states)
+    const bool tnet = (c.double_q || c.munchausen) && c.target_params != nullptr;
     if (!c.hc_S)
         return loss_and_finalize(c.P, c.cfg, c.ws, c.batch, c.K, c.on0, c.tg0, c.learn, (c.learn && c.update) ? c.adam_count : nullptr, c.qv, c.tg,
                                  c.priorities, c.losses, c.loss_accum, c.st, c.double_q,
-                                 (c.double_q && c.target_params != nullptr) ? c.ws + c.P.out_t_off : nullptr);
+                                 tnet ? c.ws + c.P.out_t_off + (c.munchausen ? (int64_t)c.B * c.P.nlog_p : 0) : nullptr,
+                                 (tnet && c.munchausen) ? c.ws + c.P.out_t_off : nullptr);
     if (int rc = launch_head_chain(c)) return rc;
     // with a weight-gradient stream the sums leave the critical path: BackwardSchedule enqueues head_chain_tail() there
     return c.ss ? ISDQN_OK : head_chain_sums(c, c.st);
@@ -2563,6 +2606,9 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
         ISDQN_REQUIRE(target_params == nullptr || cfg->double_q == 0, ISDQN_ERR_UNSUPPORTED,
                       "BatchNorm networks: double_q with separate target parameters is not defined (no statistics for an online forward "
                       "of the next states)");
+        ISDQN_REQUIRE(target_params == nullptr || !P.munchausen, ISDQN_ERR_UNSUPPORTED,
+                      "BatchNorm networks: Munchausen targets with separate target parameters are not defined (no statistics for a target "
+                      "forward of the states)");
         return bn_learn_or_loss(cfg, P, params, adam_m, adam_v, adam_count, batch, losses, loss_accum, q_values, targets, priorities,
                                 (float*)workspace, (hipStream_t)stream, learn, grad_out, update, target_params, sel);
     }
@@ -2577,6 +2623,7 @@ static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam
                NetInput{batch->frames, batch->frame_stride, batch->frame_ids, B, batch->state, batch->next_state, B}};
     // (same head of the same rows selecting and valuing -- TF-DQN -- is the max form: Q[argmax Q] == max Q)
     c.double_q = cfg->double_q != 0 && !(target_params == nullptr && on0 == tg0);
+    c.munchausen = P.munchausen;
     head_chain_plan(c, sel == nullptr);
     c.ss = learn ? side_stream() : nullptr;
     c.wst = c.ss ? c.ss->stream : c.st;

@@ -2,6 +2,7 @@
 // Mirrors slimdqn/networks/architectures/dqn.py:47-103 (cnn / fc branches) and the
 // (1+K)*A head view of slimdqn/networks/isdqn.py:34-41.
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include <string.h>
 
@@ -100,7 +101,10 @@ struct Plan {
     int64_t q_off, logits_off, out_off, dout_off, da_off, slab_off, qv_off, tg_off, dbh_off, adam_tab_off, lpart_off;
     // Double Q-learning (cfg->double_q), forms with separate target parameters: head output of the target network on the B next
     // states (q_target: Q rows [B][nha_p]; histogram heads: logits_target [B][nlog_p], q_target their expectations).  -1 without
-    int double_q;
+    // Munchausen targets (cfg->munchausen_tau > 0) with separate target parameters: the same regions hold the target network's head
+    // output on all 2B rows, states first (qt_rows = 2B; B with double_q; 0 without either option)
+    int double_q, qt_rows;
+    bool munchausen;
     int64_t qt_off, logits_t_off, out_t_off;
     int64_t wsplit_off;  // S8 mirror of the parameter buffer (same offsets as the fp32 master; weights only are read from it)
     int64_t slab_floats, da_floats;
@@ -128,6 +132,12 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     ISDQN_REQUIRE(cfg->huber_delta >= 0.f, ISDQN_ERR_ARG, "huber_delta must be >= 0 (0 = squared error)");
     ISDQN_REQUIRE(cfg->batch_norm == 0 || cfg->batch_norm == 1, ISDQN_ERR_ARG, "batch_norm must be 0 or 1");
     ISDQN_REQUIRE(cfg->double_q == 0 || cfg->double_q == 1, ISDQN_ERR_ARG, "double_q must be 0 or 1");
+    ISDQN_REQUIRE(std::isfinite(cfg->munchausen_tau) && cfg->munchausen_tau >= 0.f, ISDQN_ERR_ARG, "munchausen_tau must be finite and >= 0 (0 = off)");
+    if (cfg->munchausen_tau > 0.f) {
+        ISDQN_REQUIRE(cfg->munchausen_alpha >= 0.f && cfg->munchausen_alpha <= 1.f, ISDQN_ERR_ARG, "munchausen_alpha must be in [0, 1]");
+        ISDQN_REQUIRE(std::isfinite(cfg->munchausen_clip) && cfg->munchausen_clip <= 0.f, ISDQN_ERR_ARG, "munchausen_clip must be finite and <= 0");
+        ISDQN_REQUIRE(cfg->double_q == 0, ISDQN_ERR_ARG, "double_q and munchausen_tau > 0 exclude each other (the soft value has no argmax to decouple)");
+    }
     ISDQN_REQUIRE(cfg->n_bins == 0 || (cfg->n_bins >= 2 && cfg->n_bins <= 256), ISDQN_ERR_ARG, "n_bins must be 0 (off) or in [2, 256]");
     if (cfg->n_bins > 0) {
         ISDQN_REQUIRE(cfg->hl_max > cfg->hl_min, ISDQN_ERR_ARG, "histogram loss: hl_max must be > hl_min");
@@ -536,10 +546,14 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.adam_tab_off = region("adam_consts", 64);
     P.lpart_off = region("loss_partials", (int64_t)P.B * (P.K + P.nlog_p));
     P.wsplit_off = region("wsplit", P.n_params);
-    // (appended: a configuration without the option keeps every offset and the total it had)
+    // (appended: a configuration without the option keeps every offset and the total it had.  The plan does not know whether the
+    // caller will pass target parameters, so the regions exist with the option whatever the form: only the *_target entry points
+    // and grad_on_batch with target_params read them, iS-DQN / TF-DQN learn steps leave them untouched)
     P.double_q = cfg->double_q;
-    P.qt_off = P.double_q ? region("q_target", (int64_t)P.B * P.nha_p) : -1;
-    P.logits_t_off = (P.double_q && P.hl_nb > 0) ? region("logits_target", (int64_t)P.B * P.nlog_p) : -1;
+    P.munchausen = cfg->munchausen_tau > 0.f;
+    P.qt_rows = P.munchausen ? P.N2 : P.double_q ? P.B : 0;
+    P.qt_off = P.qt_rows ? region("q_target", (int64_t)P.qt_rows * P.nha_p) : -1;
+    P.logits_t_off = (P.qt_rows && P.hl_nb > 0) ? region("logits_target", (int64_t)P.qt_rows * P.nlog_p) : -1;
     P.out_t_off = P.hl_nb > 0 ? P.logits_t_off : P.qt_off;
     P.ws_bytes = off * 4;
     return ISDQN_OK;

@@ -51,6 +51,10 @@ _ENGINE = [
     ("-maxn", "--max_value", dict(type=float, default=100, help="Value of the highest learnable value of the target.")),
     ("-sigma", "--sigma", dict(type=float, default=3, help="Standard deviation of each target sample. If sigma / eta = 0.75, then sigma = 0.75 * (max_value - min_value) / n_bins")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
+    ("-mq", "--munchausen", dict(action="store_true", default=False, help="Munchausen targets (Vieillard et al. 2020): soft-value bootstrap plus the scaled, clipped log-policy of the taken action (the three flags below). Not with -dq.")),
+    ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
+    ("-mqa", "--munchausen_alpha", dict(type=float, default=0.9, help="Scale alpha in [0, 1] of the log-policy bonus (0: soft-DQN targets). Means nothing without -mq.")),
+    ("-mqc", "--munchausen_clip", dict(type=float, default=-1.0, help="Lower clip l0 <= 0 of tau * ln pi(a|s). Means nothing without -mq.")),
     ("-nenvs", "--n_envs", dict(type=int, default=1, help="Host environments stepped in lockstep with one batched best_actions forward (1 = the reference's loop).")),
     ("-nworkers", "--n_env_workers", dict(type=int, default=0, help="Host worker processes stepping the -nenvs environments in parallel (0 = in this process).")),
     ("-env", "--env_backend", dict(type=str, default="ale", choices=["ale", "synthetic"], help="'synthetic' replaces ALE by random frames (no ROMs needed).")),
@@ -104,6 +108,23 @@ def check_double_q(p: dict, algo_name: str) -> None:
         from slimdqn.networks.tfdqn import DOUBLE_Q_REFUSED
 
         raise ValueError(DOUBLE_Q_REFUSED)
+
+
+MUNCHAUSEN_FLAGS = ["munchausen", "munchausen_tau", "munchausen_alpha", "munchausen_clip"]  # stored with the algorithm's flags under -mq
+
+
+def check_munchausen(p: dict) -> None:
+    """-mq together with -dq fails before anything is written, with the agents' own message."""
+    if p.get("munchausen") and p.get("double_q"):
+        from slimdqn._engine import MUNCHAUSEN_DOUBLE_Q_REFUSED
+
+        raise ValueError(MUNCHAUSEN_DOUBLE_Q_REFUSED)
+
+
+def munchausen_kwargs(p) -> dict:
+    """The agents' Munchausen keywords from parsed parameters: tau = 0 (off) unless -mq is given."""
+    return dict(munchausen_tau=p["munchausen_tau"] if p["munchausen"] else 0.0, munchausen_alpha=p["munchausen_alpha"],
+                munchausen_clip=p["munchausen_clip"])
 
 
 def check_engine_arguments(p: dict) -> None:

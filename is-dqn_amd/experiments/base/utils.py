@@ -35,6 +35,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     p = vars(parser.parse_args(argvs))
     parser_argument.check_engine_arguments(p)
     parser_argument.check_double_q(p, algo_name)
+    parser_argument.check_munchausen(p)
     p["env_name"] = env_name
     if env_name == "atari":
         p["game_name"] = p["experiment_name"].split("_")[-1]
@@ -43,7 +44,8 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     p["save_path"] = os.path.join(root, env_name, "exp_output", p["experiment_name"], algo_name)
     check_experiment(p)
     store_params(p, shared, agent + (parser_argument.PRIORITIZED_FLAGS if p["prioritized"] else [])
-                 + (parser_argument.DOUBLE_Q_FLAGS if p["double_q"] else []))
+                 + (parser_argument.DOUBLE_Q_FLAGS if p["double_q"] else [])
+                 + (parser_argument.MUNCHAUSEN_FLAGS if p["munchausen"] else []))
     p["wandb"] = _NullLogger()
     return p
 

@@ -19,6 +19,17 @@ def _round_up(a, b):
     return (a + b - 1) // b * b
 
 
+MUNCHAUSEN_DOUBLE_Q_REFUSED = (
+    "double_q and munchausen_tau > 0 exclude each other: the Munchausen target bootstraps from the soft value "
+    "tau * logsumexp(Q / tau), which has no argmax to decouple")
+
+
+def check_munchausen(double_q, munchausen_tau) -> None:
+    """The one combination the library refuses (ISDQN_ERR_ARG), said before anything is allocated."""
+    if double_q and float(munchausen_tau) > 0.0:
+        raise ValueError(MUNCHAUSEN_DOUBLE_Q_REFUSED)
+
+
 class QNetEngine:
     """One Q-network (slimdqn/networks/architectures/dqn.py DQNNet + isdqn.py head view) on one GPU."""
 
@@ -43,7 +54,11 @@ class QNetEngine:
         max_value: float = 100.0,
         sigma: float = 3.0,
         double_q: bool = False,
+        munchausen_tau: float = 0.0,
+        munchausen_alpha: float = 0.9,
+        munchausen_clip: float = -1.0,
     ):
+        check_munchausen(double_q, munchausen_tau)
         _hip.require_gpu()
         self.lib = _hip.lib()
         self.device = _hip.resolve_device(device)
@@ -87,6 +102,10 @@ class QNetEngine:
         # network's rows in region "q_target"
         cfg.double_q = 1 if double_q else 0
         self.double_q = bool(double_q)
+        # Munchausen targets (include/isdqn_hip.h, isdqn_net_config::munchausen_tau): tau = 0 is off; the *_target forms then keep
+        # the target network's rows of concat(state, next_state) in region "q_target"
+        cfg.munchausen_tau, cfg.munchausen_alpha, cfg.munchausen_clip = float(munchausen_tau), float(munchausen_alpha), float(munchausen_clip)
+        self.munchausen_tau, self.munchausen_alpha, self.munchausen_clip = float(munchausen_tau), float(munchausen_alpha), float(munchausen_clip)
         self.cfg = cfg
         self.features = feats
         self.architecture_type = architecture_type

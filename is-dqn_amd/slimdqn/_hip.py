@@ -43,6 +43,9 @@ class NetConfig(ctypes.Structure):
         ("adam_b2", c_float),
         ("adam_eps", c_float),
         ("huber_delta", c_float),
+        ("munchausen_tau", c_float),  # 0: off; > 0: Munchausen targets at this temperature (include/isdqn_hip.h)
+        ("munchausen_alpha", c_float),
+        ("munchausen_clip", c_float),
         ("batch_norm", c_int32),
         ("n_bins", c_int32),  # 0: scalar heads; > 0: HL-Gauss histogram loss over [hl_min, hl_max] (include/isdqn_hip.h)
         ("hl_min", c_float),

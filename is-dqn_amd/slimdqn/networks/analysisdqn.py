@@ -27,6 +27,8 @@ class AnalysisDQN(iSDQN):
         batch_norm = kwargs["batch_norm"] if "batch_norm" in kwargs else (args[6] if len(args) > 6 else False)
         if kwargs.get("double_q", False) and batch_norm:
             raise NotImplementedError("AnalysisDQN: double_q with batch_norm is not built (ISDQN_ERR_UNSUPPORTED with target parameters)")
+        if float(kwargs.get("munchausen_tau", 0.0)) > 0.0 and batch_norm and not kwargs.get("double_q", False):
+            raise NotImplementedError("AnalysisDQN: munchausen_tau > 0 with batch_norm is not built (ISDQN_ERR_UNSUPPORTED with target parameters)")
         super().__init__(*args, **kwargs)
         self.target_params = self.params.clone()  # analysisdqn.py:49
         K = self.n_bellman_iterations

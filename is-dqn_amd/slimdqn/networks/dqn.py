@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from slimdqn._engine import check_munchausen
 from slimdqn.networks._agent import DeviceParams, EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -38,10 +39,18 @@ class DQN(EngineAgent):
         max_value: float = 100.0,
         sigma: float = 3.0,
         double_q: bool = False,
+        munchausen_tau: float = 0.0,
+        munchausen_alpha: float = 0.9,
+        munchausen_clip: float = -1.0,
     ):
-        """``double_q``: Double DQN (van Hasselt et al. 2016) -- the online parameters pick the next action, the target parameters
+        """``munchausen_tau`` > 0: Munchausen targets (Vieillard et al. 2020) -- the bootstrap value is the soft value
+        tau * logsumexp(Q / tau) of the value head and alpha * clip(tau ln pi(a|s), munchausen_clip, 0) is added to the reward
+        (include/isdqn_hip.h, isdqn_net_config::munchausen_tau); 0 is off.  Here the
+        target parameters then run over the states as well as the next states: about one more forward of B images per step.  Not together with ``double_q`` (ValueError).
+        ``double_q``: Double DQN (van Hasselt et al. 2016) -- the online parameters pick the next action, the target parameters
         value it (include/isdqn_hip.h, isdqn_net_config::double_q): one more forward per step.
         ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
+        check_munchausen(double_q, munchausen_tau)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, n_actions * max(int(n_bins), 1), layer_norm, False)
         self.data_to_update = data_to_update
@@ -49,7 +58,8 @@ class DQN(EngineAgent):
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
-                                max_value=max_value, sigma=sigma, double_q=double_q)
+                                max_value=max_value, sigma=sigma, double_q=double_q, munchausen_tau=munchausen_tau,
+                                munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip)
         self.target_params = self.params.copy()  # dqn.py:34
         self.cumulated_loss = 0
 

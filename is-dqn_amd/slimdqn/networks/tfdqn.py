@@ -43,8 +43,13 @@ class TFDQN(EngineAgent):
         max_value: float = 100.0,
         sigma: float = 3.0,
         double_q: bool = False,
+        munchausen_tau: float = 0.0,
+        munchausen_alpha: float = 0.9,
+        munchausen_clip: float = -1.0,
     ):
-        """``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h).
+        """``munchausen_tau`` > 0: Munchausen targets (include/isdqn_hip.h, isdqn_net_config::munchausen_tau) -- unlike ``double_q``
+        well defined here: the single head is regularised by its own stop-gradient policy.
+        ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h).
         ``double_q`` is refused: see DOUBLE_Q_REFUSED."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
@@ -54,7 +59,8 @@ class TFDQN(EngineAgent):
         self.target_update_frequency = target_update_frequency
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, batch_norm=batch_norm,
-                                n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma)
+                                n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma, munchausen_tau=munchausen_tau,
+                                munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54

@@ -53,9 +53,10 @@ def report(case, omit=None):
     print(json.dumps({"case": case, "bad": bad, "site": site, "addr": hex(addr), "omitted": omit}), flush=True)
 
 
-def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0):
+def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False):
     n_heads = 1 + K if K > 0 else 1
-    eng = QNetEngine(obs, A, n_heads, feats, arch, ln, B, batch_norm=bn, double_q=double_q, n_bins=n_bins, min_value=-10.0, max_value=10.0, sigma=0.3)
+    eng = QNetEngine(obs, A, n_heads, feats, arch, ln, B, batch_norm=bn, double_q=double_q, n_bins=n_bins, min_value=-10.0, max_value=10.0, sigma=0.3,
+                     munchausen_tau=0.03 if munchausen else 0.0)
     eng.init_params(0)
     rng = np.random.default_rng(0)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -104,7 +105,7 @@ def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, g
         eng.best_actions(frames=fwd["frames"], frame_stride=fwd["frame_stride"], frame_ids=fwd["frame_ids"], idx_networks=heads)
     if grad:  # (BatchNorm networks too: the analysis agents' gradient-only passes, with and without separate target parameters)
         eng.grad_on_batch(batch, grad_out)
-        if K >= 1 and n_heads >= 2 and not (bn and double_q):  # (BatchNorm + double_q + target parameters: refused)
+        if K >= 1 and n_heads >= 2 and not (bn and (double_q or munchausen)):  # (BatchNorm + either option + target parameters: refused)
             eng.grad_on_batch(batch, grad_out, target_params=tparams, online_head=1, target_head=1, n_pairs=1)
     if target and not bn:
         eng.learn_on_batch_target(batch, tparams)
@@ -154,6 +155,16 @@ if __name__ == "__main__":
         dict(name="dq-hist-cnn-tiny-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, double_q=True, n_bins=51),
         dict(name="dq-hist-cnn-one-head-dqn-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=0, A=5, B=6, target=True, double_q=True, n_bins=51),
         dict(name="dq-bn-cnn-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, bn=True, double_q=True),
+        # Munchausen targets (site 31: the value head's state / next-state rows of td_kernel; the DQN form reads both halves from the
+        # [2B] region "q_target"); the head chain reads them from LDS
+        dict(name="mq-cnn-tiny-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, munchausen=True),
+        dict(name="mq-cnn-headline-B7-ragged", arch="cnn", obs=(84, 84, 4), feats=HL, K=9, A=9, B=7, munchausen=True),
+        dict(name="mq-cnn-one-head-dqn-B8", arch="cnn", obs=(84, 84, 4), feats=HL, K=0, A=6, B=8, target=True, munchausen=True),
+        dict(name="mq-fc-one-head-dqn-B32", arch="fc", obs=(8,), feats=(100, 100), K=0, A=4, B=32, target=True, munchausen=True),
+        # histogram heads: the value head's logit rows of hl_loss_kernel (site 31), the DQN form's from the [2B] region "logits_target"
+        dict(name="mq-hist-cnn-tiny-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, munchausen=True, n_bins=51),
+        dict(name="mq-hist-cnn-one-head-dqn-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=0, A=5, B=6, target=True, munchausen=True, n_bins=51),
+        dict(name="mq-bn-cnn-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, bn=True, munchausen=True),
         # negative control: the checker must notice a tensor that was not registered
         dict(name="control-action-not-registered", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, omit="action"),
     ]
