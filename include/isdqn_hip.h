@@ -239,7 +239,42 @@ typedef struct isdqn_net_config {
                                            * never falls below the target histogram's entropy, ~1.1 nats at sigma / eta = 0.75, and
                                            * would flatten prioritized replay).  Not with huber_delta > 0 (ISDQN_ERR_ARG) nor with
                                            * batch_norm (ISDQN_ERR_UNSUPPORTED).                                                    */
-    float hl_min, hl_max, hl_sigma;       /* n_bins > 0: support [hl_min, hl_max] (hl_max > hl_min) and sigma > 0; ignored at 0 */
+    int32_t n_quantiles;                  /* (behind n_bins, the other width of a per-action block: the struct still ends in
+                                           * hl_sigma, double_q.)  QR-DQN quantile-regression heads (Dabney et al., "Distributional
+                                           * Reinforcement Learning with Quantile Regression", AAAI 2018).  n_quantiles = N.  0: off --
+                                           * every result, workspace size and region offset keeps the bits it had before the field
+                                           * existed.  2..256: on.  Anything else: ISDQN_ERR_ARG; together with n_bins > 0:
+                                           * ISDQN_ERR_ARG; with munchausen_tau > 0: ISDQN_ERR_UNSUPPORTED (M-IQN's atom-wise form is a
+                                           * follow-up); with batch_norm: ISDQN_ERR_UNSUPPORTED; more than 64 regressed heads or
+                                           * n_heads * n_actions * N > 5456: ISDQN_ERR_UNSUPPORTED.  THE definition, with N > 0: the last
+                                           * Dense has n_heads * n_actions * N outputs, output ((h * A) + a) * N + i is theta_i of action a
+                                           * of head h, the estimate of the quantile at tau_i = (i + 1/2) / N.
+                                           * Q_h(s, a) = (1 / N) sum_i theta_i -- what forward / best_action(s) return and argmax with the
+                                           * existing tie rule.  For every regressed pair k < K with value head v = target_head + k and
+                                           * online head o = online_head + k:
+                                           *     a*     = the FIRST index attaining max_a Q^val_v(s', a); with double_q = 1 the first
+                                           *              argmax of the selector head Q^sel_{online_head+k}(s', .) (same parameters or
+                                           *              target_params exactly as for scalar heads)
+                                           *     t_j    = r + ((1 - terminal) * gamma^n) * theta^val_j(s', a*)     (the target atoms, fp32,
+                                           *              evaluated in that order, uncontracted)
+                                           *     u_ij   = t_j - theta^on_i(s, a_b)
+                                           *     l_bk   = sum_i (1 / N) sum_j |tau_i - 1{u_ij < 0}| * h_kappa(u_ij),  kappa = huber_delta
+                                           *              kappa > 0: h_kappa(u) = L_kappa(u) / kappa with L_kappa(u) = u^2 / 2 for
+                                           *              |u| <= kappa and kappa (|u| - kappa / 2) beyond (Dopamine's form);
+                                           *              kappa = 0: h_0(u) = |u|, the plain pinball loss
+                                           *     losses[k] = (1 / B) sum_b w_b l_bk
+                                           *     dL/dtheta^on_i = -(w_b / (B N)) sum_j |tau_i - 1{u_ij < 0}| * h'_kappa(u_ij), with
+                                           *              h'_kappa = clip(u, -kappa, kappa) / kappa, or sign(u) at kappa = 0 (sign(0) = 0);
+                                           *              zero on every other output
+                                           * No gradient flows through any target atom, even where that head is itself learned in another
+                                           * pair.  q_values = the online mean; targets = r + (1 - terminal) gamma^n Q^val_v(s', a*), a
+                                           * scalar (the mean of the atoms in exact arithmetic); priorities = sqrt(mean_k (q - target)^2 +
+                                           * 1e-10) on those scalars, as for histogram heads; loss_weights, losses_accum and
+                                           * priorities_ready behave as without the option.  huber_delta > 0 is allowed here: it is
+                                           * kappa (QR-DQN's usual value is 1).  Quantile crossing is not prevented, as in the paper.
+                                           * The workspace regions keep the names of the histogram heads ("logits", "logits_target",
+                                           * "q_target") and hold quantile values.                                                    */
+    float hl_min, hl_max, hl_sigma;      /* n_bins > 0: support [hl_min, hl_max] (hl_max > hl_min) and sigma > 0; ignored at 0 */
     int32_t double_q;                     /* 0: the bootstrap value is max_a' Q(s', a') of the value head (the reference; every result
                                            * keeps the bits it had before the field existed).  1: Double Q-learning (van Hasselt et al.
                                            * 2016).  Anything else: ISDQN_ERR_ARG.  THE definition: for every regressed pair k < K with

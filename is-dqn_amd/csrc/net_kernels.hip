@@ -15,6 +15,7 @@
 #include "conv_s8_pair.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
+#include "quantile.h"
 #include "net_plan.h"
 #include "net_problems.h"
 
@@ -1759,7 +1760,7 @@ static int loss_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, 
 }
 
 // targets, per-transition loss and dL/d(head output) of rows [0, B) from the head outputs of a finished forward (TD loss on the Q rows, or
-// the HL-Gauss loss on the logit rows), then loss_finalize over the head layer's width (nlog_p: nha_p without histogram heads).
+// the HL-Gauss loss on the logit rows, the quantile-regression loss on the quantile rows), then loss_finalize over the head layer's width (nlog_p: nha_p without histogram heads).
 // `val_rows`: head-output rows [B][nlog_p] of the next states that supply the bootstrap value (null: rows [B, 2B) of the forward);
 // `double_q`: selector head on0 + k of rows [B, 2B) of the forward -- the online parameters on the next states -- picks the action;
 // Munchausen targets (cfg->munchausen_tau > 0): `state_val_rows`, head-output rows [B][nlog_p] of the states from the network that
@@ -1774,13 +1775,26 @@ static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* 
     const float* next_rows = ws + P.out_off + (int64_t)B * P.nlog_p;
     if (val_rows == nullptr) val_rows = next_rows;
     const float* sel_rows = double_q ? next_rows : nullptr;
-    const int hl_R = P.hl_nb > 0 ? hl_rows_per_wg(K, P.hl_nb) : 0;
+    const int hl_R = P.head_nb > 0 ? (P.qr ? qr_rows_per_wg(K, P.head_nb) : hl_rows_per_wg(K, P.head_nb)) : 0;
     const int n_blk = hl_R ? ceil_div(B, hl_R) : ceil_div(B, TD_ROWS);
     float* loss_part = ws + P.lpart_off;
     float* dbh_part = loss_part + (int64_t)n_blk * K;
-    if (hl_R)
-        hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.hl_nb * sizeof(float), st, ws + P.logits_off, val_rows,
-                           sel_rows, P.nlog_p, on0, mun_rows, P.nlog_p, tg0, mu, B, hl_R, K, on0, tg0, P.n_actions, P.hl_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, P.hl_sigma,
+    if (P.qr) {
+        // quantile heads (quantile.h): NT = 64-quantile groups a lane owns, kappa = cfg->huber_delta (0: the plain pinball loss)
+        auto launch_qr = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(n_blk), dim3(QR_THREADS), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows, sel_rows,
+                               P.nlog_p, on0, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, cfg->huber_delta, batch->action, batch->reward,
+                               batch->terminal, batch->loss_weights, cfg->gamma_n, learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part,
+                               dbh_part);
+        };
+        const int nt = ceil_div(P.head_nb, 64);
+        if (cfg->huber_delta > 0.f)
+            nt == 1 ? launch_qr(qr_loss_kernel<1, true>) : nt == 2 ? launch_qr(qr_loss_kernel<2, true>) : nt == 3 ? launch_qr(qr_loss_kernel<3, true>) : launch_qr(qr_loss_kernel<4, true>);
+        else
+            nt == 1 ? launch_qr(qr_loss_kernel<1, false>) : nt == 2 ? launch_qr(qr_loss_kernel<2, false>) : nt == 3 ? launch_qr(qr_loss_kernel<3, false>) : launch_qr(qr_loss_kernel<4, false>);
+    } else if (hl_R)
+        hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows,
+                           sel_rows, P.nlog_p, on0, mun_rows, P.nlog_p, tg0, mu, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.head_nb, P.hl_sigma,
                            batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n,
                            learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
     else
@@ -1973,14 +1987,23 @@ extern "C" int isdqn_net_workspace_region(const isdqn_net_config* cfg, const cha
     return ISDQN_ERR_ARG;
 }
 
-// Histogram heads: Q rows ("q" region) <- expectations of the logit rows the forward left in the "logits" region (no-op otherwise).
-static int hl_expect(const Plan& P, float* ws, int n_rows, hipStream_t st) {
-    if (P.hl_nb == 0) return ISDQN_OK;
+// Histogram / quantile heads: Q rows `q` [n_rows][nha_p] <- expectations of the logit rows / means of the quantile rows `rows`
+// [n_rows][nlog_p] (no-op for scalar heads).
+static int head_expect_rows(const Plan& P, const float* rows, int n_rows, float* q, hipStream_t st) {
+    if (P.head_nb == 0) return ISDQN_OK;
     const int64_t waves = (int64_t)n_rows * P.nha;
-    hipLaunchKernelGGL(hl_expect_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, ws + P.logits_off, n_rows, P.nha, P.hl_nb,
-                       P.nlog_p, P.nha_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, ws + P.q_off);
+    if (P.qr)
+        hipLaunchKernelGGL(qr_expect_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rows, n_rows, P.nha, P.head_nb, P.nlog_p,
+                           P.nha_p, q);
+    else
+        hipLaunchKernelGGL(hl_expect_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, rows, n_rows, P.nha, P.head_nb,
+                           P.nlog_p, P.nha_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.head_nb, q);
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
+}
+// the rows the forward left in the "logits" region -> the "q" region
+static int head_expect(const Plan& P, float* ws, int n_rows, hipStream_t st) {
+    return head_expect_rows(P, ws + P.logits_off, n_rows, ws + P.q_off, st);
 }
 
 static int check_input(const isdqn_net_config* cfg, const uint8_t* frames, int64_t frame_stride,
@@ -2012,7 +2035,7 @@ extern "C" int isdqn_net_forward(const isdqn_net_config* cfg, const float* param
     if (rc) return rc;
     rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.out_off, st);
     if (rc) return rc;
-    rc = hl_expect(P, ws, n_rows, st);
+    rc = head_expect(P, ws, n_rows, st);
     if (rc) return rc;
     // q_out is the unpadded (n_rows, nha) view
     ISDQN_HIP_CHECK(hipMemcpy2DAsync(q_out, (size_t)P.nha * 4, ws + P.q_off, (size_t)P.nha_p * 4, (size_t)P.nha * 4,
@@ -2089,8 +2112,8 @@ static void head_chain_plan(LearnCtx& c, bool plan_heads) {
     const Plan& P = c.P;
     const Layer& hid = c.hid();
     static const bool hc_disabled = ISDQN_DEV_ENV("ISDQN_NO_HEAD_CHAIN");
-    // (histogram heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
-    if (!(c.learn && c.update && plan_heads && !hc_disabled && c.target_params == nullptr && P.hl_nb == 0 && P.n_layers >= 2 && hid.kind == 1 &&
+    // (histogram and quantile heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
+    if (!(c.learn && c.update && plan_heads && !hc_disabled && c.target_params == nullptr && P.head_nb == 0 && P.n_layers >= 2 && hid.kind == 1 &&
           !hid.is_head && hid.has_relu && hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0))
         return;
     // transitions per workgroup: the per-transition phases scale with S (the kernel is instruction-issue bound) while
@@ -2117,10 +2140,9 @@ static int learn_forward(const LearnCtx& c) {
         if (rc) return rc;
         rc = net_forward(P, c.x3, c.target_params, c.in, P.N2, 0, ws, ws + P.out_t_off, c.st);
         if (rc) return rc;
-        if (P.hl_nb > 0) {
-            hipLaunchKernelGGL(hl_expect_kernel, dim3((unsigned)(((int64_t)P.N2 * P.nha + 3) / 4)), dim3(256), 0, c.st, ws + P.logits_t_off, P.N2,
-                               P.nha, P.hl_nb, P.nlog_p, P.nha_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, ws + P.qt_off);
-            ISDQN_HIP_CHECK(hipGetLastError());
+        if (P.head_nb > 0) {
+            rc = head_expect_rows(P, ws + P.logits_t_off, P.N2, ws + P.qt_off, c.st);
+            if (rc) return rc;
         }
         rc = refresh_mirror(P, c.params, ws, c.st);
         if (rc) return rc;
@@ -2136,10 +2158,9 @@ static int learn_forward(const LearnCtx& c) {
         if (rc) return rc;
         rc = net_forward(P, c.x3, c.target_params, nx, B, 0, ws, ws + P.out_t_off, c.st);
         if (rc) return rc;
-        if (P.hl_nb > 0) {
-            hipLaunchKernelGGL(hl_expect_kernel, dim3((unsigned)(((int64_t)B * P.nha + 3) / 4)), dim3(256), 0, c.st, ws + P.logits_t_off, B, P.nha,
-                               P.hl_nb, P.nlog_p, P.nha_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.hl_nb, ws + P.qt_off);
-            ISDQN_HIP_CHECK(hipGetLastError());
+        if (P.head_nb > 0) {
+            rc = head_expect_rows(P, ws + P.logits_t_off, B, ws + P.qt_off, c.st);
+            if (rc) return rc;
         }
         rc = refresh_mirror(P, c.params, ws, c.st);
         if (rc) return rc;
@@ -2726,7 +2747,7 @@ extern "C" int isdqn_net_shift_params(const isdqn_net_config* cfg, float* params
     ISDQN_REQUIRE(params != nullptr, ISDQN_ERR_ARG, "null pointer");
     const Layer& l = P.L[P.n_layers - 1];
     hipLaunchKernelGGL(shift_kernel, dim3(ceil_div(l.in_p + 1, 256)), dim3(256), 0, (hipStream_t)stream,
-                       params + l.w_off, params + l.b_off, P.nlog, P.n_actions * (P.hl_nb > 0 ? P.hl_nb : 1), l.in_p);
+                       params + l.w_off, params + l.b_off, P.nlog, P.n_actions * (P.head_nb > 0 ? P.head_nb : 1), l.in_p);
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }
@@ -2749,7 +2770,7 @@ extern "C" int isdqn_net_best_action(const isdqn_net_config* cfg, const float* p
     if (rc) return rc;
     rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, 1, 0, ws, ws + P.out_off, st);
     if (rc) return rc;
-    rc = hl_expect(P, ws, 1, st);
+    rc = head_expect(P, ws, 1, st);
     if (rc) return rc;
     hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(64), 0, st, ws + P.q_off, P.n_actions, P.oh + idx_network, out_action);
     ISDQN_HIP_CHECK(hipGetLastError());
@@ -2779,7 +2800,7 @@ extern "C" int isdqn_net_best_actions(const isdqn_net_config* cfg, const float* 
     }
     rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.out_off, st);
     if (rc) return rc;
-    rc = hl_expect(P, ws, n_rows, st);
+    rc = head_expect(P, ws, n_rows, st);
     if (rc) return rc;
     hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, st, ws + P.q_off, n_rows, P.nha_p, P.n_actions,
                        P.oh, P.K, idx_networks, out_actions);

@@ -89,8 +89,10 @@ struct Plan {
     BnSite bns[MAX_LAYERS + 1 + 2 * IMP_STACKS];
     int64_t x0_off;  // BatchNorm, cnn: the network input frames / 255 as S8 [N2][h * w][8]; fc: concat(state, next_state) fp32 [N2][obs]
     int n_heads, n_actions, nha, nha_p;
-    // head layer width: nha Q-values, or nha * hl_nb logits with the HL-Gauss histogram loss (cfg->n_bins > 0)
-    int nlog, nlog_p, hl_nb;
+    // head layer width: nha Q-values, or nha * head_nb outputs with per-action blocks of head_nb values: the logits of the HL-Gauss
+    // histogram loss (cfg->n_bins > 0) or the quantile values of QR-DQN (cfg->n_quantiles > 0; `qr` says which loss runs)
+    int nlog, nlog_p, head_nb;
+    bool qr;
     float hl_min, hl_max, hl_sigma;
     // K regressed heads; head k + oh (online rows) is regressed on head k (next-state rows).  iS-DQN: n_heads = 1 + K,
     // oh = 1 (isdqn.py:96-98).  A single head (n_heads = 1) is TF-DQN: K = 1, oh = 0 -- the head is regressed on its own
@@ -138,6 +140,14 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         ISDQN_REQUIRE(std::isfinite(cfg->munchausen_clip) && cfg->munchausen_clip <= 0.f, ISDQN_ERR_ARG, "munchausen_clip must be finite and <= 0");
         ISDQN_REQUIRE(cfg->double_q == 0, ISDQN_ERR_ARG, "double_q and munchausen_tau > 0 exclude each other (the soft value has no argmax to decouple)");
     }
+    ISDQN_REQUIRE(cfg->n_quantiles == 0 || (cfg->n_quantiles >= 2 && cfg->n_quantiles <= 256), ISDQN_ERR_ARG,
+                  "n_quantiles must be 0 (off) or in [2, 256]");
+    if (cfg->n_quantiles > 0) {  // (huber_delta > 0 is allowed here: it is kappa)
+        ISDQN_REQUIRE(cfg->n_bins == 0, ISDQN_ERR_ARG, "n_quantiles > 0 and the histogram loss (n_bins > 0) exclude each other");
+        ISDQN_REQUIRE(cfg->munchausen_tau == 0.f, ISDQN_ERR_UNSUPPORTED,
+                      "n_quantiles > 0: Munchausen targets (munchausen_tau > 0) are not built for quantile heads");
+        ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "n_quantiles > 0: quantile heads are not built for BatchNorm networks");
+    }
     ISDQN_REQUIRE(cfg->n_bins == 0 || (cfg->n_bins >= 2 && cfg->n_bins <= 256), ISDQN_ERR_ARG, "n_bins must be 0 (off) or in [2, 256]");
     if (cfg->n_bins > 0) {
         ISDQN_REQUIRE(cfg->hl_max > cfg->hl_min, ISDQN_ERR_ARG, "histogram loss: hl_max must be > hl_min");
@@ -158,13 +168,16 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.n_actions = cfg->n_actions;
     P.nha = cfg->n_heads * cfg->n_actions;
     P.nha_p = round_up(P.nha, 8);
-    P.hl_nb = cfg->n_bins;
+    P.qr = cfg->n_quantiles > 0;
+    P.head_nb = P.qr ? cfg->n_quantiles : cfg->n_bins;
     P.hl_min = cfg->hl_min; P.hl_max = cfg->hl_max; P.hl_sigma = cfg->hl_sigma;
-    P.nlog = P.hl_nb > 0 ? P.nha * P.hl_nb : P.nha;
+    P.nlog = P.head_nb > 0 ? P.nha * P.head_nb : P.nha;
     P.nlog_p = round_up(P.nlog, 8);
-    ISDQN_REQUIRE(P.hl_nb == 0 || P.K <= 64, ISDQN_ERR_UNSUPPORTED, "the histogram loss is built for at most 64 regressed heads");
+    ISDQN_REQUIRE(P.qr || P.head_nb == 0 || P.K <= 64, ISDQN_ERR_UNSUPPORTED, "the histogram loss is built for at most 64 regressed heads");
+    ISDQN_REQUIRE(!P.qr || P.K <= 64, ISDQN_ERR_UNSUPPORTED, "n_quantiles > 0: the quantile loss is built for at most 64 regressed heads");
     // (dense_post_kernel stages a whole head row, bias and LayerNorm rows in 64 KB of LDS: 3 * 5456 floats)
-    ISDQN_REQUIRE(P.hl_nb == 0 || P.nlog <= 5456, ISDQN_ERR_UNSUPPORTED, "histogram heads: n_heads * n_actions * n_bins must be <= 5456");
+    ISDQN_REQUIRE(P.qr || P.head_nb == 0 || P.nlog <= 5456, ISDQN_ERR_UNSUPPORTED, "histogram heads: n_heads * n_actions * n_bins must be <= 5456");
+    ISDQN_REQUIRE(!P.qr || P.nlog <= 5456, ISDQN_ERR_UNSUPPORTED, "quantile heads: n_heads * n_actions * n_quantiles must be <= 5456");
     int nl = 0;
     int n_conv = 0, n_dense = 0, n_ln = 0;
     int64_t poff = 0;
@@ -533,10 +546,10 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     if (P.bn && cfg->arch == ISDQN_ARCH_FC)  // concat(state, next_state) as one matrix (the first layer's weight gradient contracts over all 2B rows)
         P.x0_off = region("bn/x0", (int64_t)P.N2 * P.L[0].in_f);
     P.q_off = region("q", (int64_t)P.N2 * P.nha_p);
-    // the head layer's output rows [2B][nlog_p]: the Q-values themselves, or the histogram logits (the "q" rows then hold their
-    // expectations, written by hl_expect_kernel for forward / best_action(s))
-    P.logits_off = P.hl_nb > 0 ? region("logits", (int64_t)P.N2 * P.nlog_p) : -1;
-    P.out_off = P.hl_nb > 0 ? P.logits_off : P.q_off;
+    // the head layer's output rows [2B][nlog_p]: the Q-values themselves, or the histogram logits / quantile values (the "q" rows then
+    // hold their expectations / means, written by hl_expect_kernel / qr_expect_kernel for forward / best_action(s))
+    P.logits_off = P.head_nb > 0 ? region("logits", (int64_t)P.N2 * P.nlog_p) : -1;
+    P.out_off = P.head_nb > 0 ? P.logits_off : P.q_off;
     P.dout_off = region("dout", (int64_t)P.Bb * P.nlog_p);
     P.da_off = region("da", P.da_floats);
     P.slab_off = region("slab", P.slab_floats);
@@ -553,8 +566,8 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.munchausen = cfg->munchausen_tau > 0.f;
     P.qt_rows = P.munchausen ? P.N2 : P.double_q ? P.B : 0;
     P.qt_off = P.qt_rows ? region("q_target", (int64_t)P.qt_rows * P.nha_p) : -1;
-    P.logits_t_off = (P.qt_rows && P.hl_nb > 0) ? region("logits_target", (int64_t)P.qt_rows * P.nlog_p) : -1;
-    P.out_t_off = P.hl_nb > 0 ? P.logits_t_off : P.qt_off;
+    P.logits_t_off = (P.qt_rows && P.head_nb > 0) ? region("logits_target", (int64_t)P.qt_rows * P.nlog_p) : -1;
+    P.out_t_off = P.head_nb > 0 ? P.logits_t_off : P.qt_off;
     P.ws_bytes = off * 4;
     return ISDQN_OK;
 }

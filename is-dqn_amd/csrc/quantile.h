@@ -1,0 +1,237 @@
+// QR-DQN quantile-regression heads (Dabney et al., "Distributional Reinforcement Learning with Quantile Regression", AAAI 2018) on the
+// Q-network heads; THE definition is include/isdqn_hip.h, isdqn_net_config::n_quantiles.  With n_quantiles = N > 0 the head layer has
+// n_heads * A * N outputs, output ((h * A) + a) * N + i being theta_i of action a of head h, the quantile at tau_i = (i + 1/2) / N;
+//   Q_h(s, a) = (1 / N) sum_i theta_i.
+// Two kernels, both one wave per (row, head / action) or (transition, pair) with the lanes over the quantiles (lane owns theta_i for
+// i = lane + 64 t), fp32, every sum in a fixed order (a lane's own values in ascending t, then a __shfl_xor butterfly; the j loop of the
+// pairwise loss in ascending j): bit-identical from run to run, no atomics.
+//   qr_expect_kernel: quantile rows -> Q rows (forward / best_action / best_actions and the DQN-form target rows, where
+//                     hl_expect_kernel runs for histogram heads);
+//   qr_loss_kernel:   where hl_loss_kernel runs for histogram heads (learn / loss / grad, every head selection).
+#pragma once
+
+namespace isdqn {
+
+constexpr int QR_MAX_QUANTILES = 256;
+constexpr int QR_PER_LANE = QR_MAX_QUANTILES / 64;
+constexpr int QR_MAX_ROWS = 4;  // transitions per workgroup of qr_loss_kernel
+// Waves per workgroup of qr_loss_kernel.  A (transition, pair) is a chain of dependent steps -- A row loads, each followed by a butterfly,
+// then the N x N loop -- so a wave's time is the number of pairs it takes in turn: 16 waves share the R * K pairs of a workgroup (9 each
+// with 4 waves at K = 9, 98.8 us measured at B = 256; 3 each with 16), and the partial rows the workgroup leaves stay as many.
+constexpr int QR_WAVES = 16;
+constexpr int QR_THREADS = 64 * QR_WAVES;
+constexpr int QR_AHEAD = 4;  // actions whose rows are requested before the first of them is reduced
+
+__device__ __forceinline__ float qr_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The N quantile values at `th` (one action of one head) into the lanes' registers (0 past N) ...
+__device__ __forceinline__ void qr_load(const float* __restrict__ th, int N, int lane, float (&v)[QR_PER_LANE]) {
+#pragma unroll
+    for (int t = 0; t < QR_PER_LANE; ++t) {
+        const int i = lane + 64 * t;
+        v[t] = i < N ? th[i] : 0.f;
+    }
+}
+// ... and their mean: the lane's own values in ascending t, the butterfly, one division -- the same bits in every lane and wherever
+// it is called.
+__device__ __forceinline__ float qr_reduce(const float (&v)[QR_PER_LANE], int N) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < QR_PER_LANE; ++t) s += v[t];
+    return qr_wave_sum(s) / (float)N;
+}
+__device__ __forceinline__ float qr_mean(const float* __restrict__ th, int N, int lane, float (&v)[QR_PER_LANE]) {
+    qr_load(th, N, lane, v);
+    return qr_reduce(v, N);
+}
+
+// q[row][c] = mean of the quantile values of column c = h * A + a (c < nha) at rows[row][c * N .. c * N + N); the padding columns of
+// q are not written.
+__global__ __launch_bounds__(256) void qr_expect_kernel(const float* __restrict__ rows, int n_rows, int nha, int N, int nlog_p, int nha_p,
+                                                        float* __restrict__ q) {
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)n_rows * nha) return;  // (whole waves: the shuffles below see every lane of theirs)
+    const int row = (int)(item / nha), c = (int)(item - (int64_t)row * nha);
+    float v[QR_PER_LANE];
+    const float qv = qr_mean(rows + (int64_t)row * nlog_p + (int64_t)c * N, N, lane, v);
+    if (lane == 0) q[(int64_t)row * nha_p + c] = qv;
+}
+
+// The N x N pairwise sums of one (transition, pair): the lane's online quantiles th[t] (i = lane + 64 t, t < NT) against the target
+// atoms tv[t2] (j = lane + 64 t2, held by the lanes and broadcast one at a time, ascending j).  Leaves in g[t] / ls[t] the sums over j
+// of |tau_i - 1{u < 0}| * clip(u, -kappa, kappa) and |tau_i - 1{u < 0}| * L_kappa(u) (HUBER), or * sign(u) and * |u| (kappa = 0),
+// u = t_j - theta_i.  The indicator is a select and h' a clamp: the loop body has no branch.
+template <int NT, bool HUBER>
+__device__ __forceinline__ void qr_pairwise(const float (&th)[QR_PER_LANE], const float (&tv)[QR_PER_LANE], int N, int lane, float kappa,
+                                            float (&g)[QR_PER_LANE], float (&ls)[QR_PER_LANE]) {
+    float tau[NT], omt[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        tau[t] = ((float)(lane + 64 * t) + 0.5f) / (float)N;
+        // 1 - tau_i from its own exact numerator: 1.f - tau[t] would carry tau's rounding, N ulps of 1 - tau at the last quantile
+        omt[t] = ((float)(N - 1 - (lane + 64 * t)) + 0.5f) / (float)N;
+        g[t] = ls[t] = 0.f;
+    }
+#pragma unroll
+    for (int t2 = 0; t2 < NT; ++t2) {
+        const int nj = min(64, N - 64 * t2);
+        for (int jj = 0; jj < nj; ++jj) {
+            const float tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tv[t2]), jj));
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float u = tj - th[t];
+                const float wgt = u < 0.f ? omt[t] : tau[t];
+                const float au = fabsf(u);
+                float c, L;
+                if (HUBER) {
+                    c = fminf(fmaxf(u, -kappa), kappa);
+                    L = au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa);
+                } else {
+                    c = (u > 0.f ? 1.f : 0.f) - (u < 0.f ? 1.f : 0.f);
+                    L = au;
+                }
+                g[t] += wgt * c;
+                ls[t] += wgt * L;
+            }
+        }
+    }
+}
+
+// Iterated Bellman target atoms + quantile-regression (Huber) loss.  Workgroup = R <= QR_MAX_ROWS transitions; wave w of QR_WAVES takes the
+// (transition, k) pairs w, w + QR_WAVES, ...: online head on0 + k at the taken action is regressed on head tg0 + k of the next-state rows.
+//   a* = first argmax_a of the means of the value head (`slogits` != null, isdqn_net_config::double_q: of head sh + k of the selector
+//        rows, pitch s_pitch);  t_j = r + ((1 - terminal) gamma^n) theta^val_j(s', a*);  u_ij = t_j - theta_i(s, a_b)
+//   l = sum_i (1 / N) sum_j |tau_i - 1{u_ij < 0}| h_kappa(u_ij),  dL/dtheta_i = -(w_b / (B N)) sum_j |tau_i - 1{u_ij < 0}| h'_kappa(u_ij)
+//   on the taken action's N outputs, 0 elsewhere (w_b: isdqn_batch.loss_weights, 1 without).
+// `vlogits`: the value rows of the B next states (pitch nlog_p).  Writes q_values / targets [B][K] (online mean, r + (1 - terminal)
+// gamma^n * mean of the value row at a*), priorities[B] = sqrt(mean_k (q - target)^2 + 1e-10), per-workgroup partials of the per-pair
+// loss sums (loss_part [n_blk][K]) and, with `dout`, the dL/dtheta rows (zero-filled) and their column sums over the workgroup's rows
+// (dbh_part [n_blk][nlog_p], the head-bias gradient); loss_finalize_kernel reduces both in a fixed order.
+// Dynamic LDS: R * K * N floats of dL/dtheta.
+template <int NT, bool HUBER>
+__global__ __launch_bounds__(QR_THREADS) void qr_loss_kernel(const float* __restrict__ logits, const float* __restrict__ vlogits,
+                                                      const float* __restrict__ slogits, int s_pitch, int sh, int B, int R, int K, int on0,
+                                                      int tg0, int A, int N, int nlog_p, float kappa, const int* __restrict__ action,
+                                                      const float* __restrict__ reward, const uint8_t* __restrict__ terminal,
+                                                      const float* __restrict__ loss_weights, float gamma_n, float* __restrict__ dout,
+                                                      float* __restrict__ q_values, float* __restrict__ targets,
+                                                      double* __restrict__ priorities, float* __restrict__ loss_part,
+                                                      float* __restrict__ dbh_part) {
+    extern __shared__ float s_dl[];  // [R][K][N]
+    __shared__ int s_action[QR_MAX_ROWS];
+    __shared__ float s_r[QR_MAX_ROWS], s_nt[QR_MAX_ROWS], s_w[QR_MAX_ROWS];  // s_w: importance-sampling weights (none: 1)
+    __shared__ float s_l[QR_MAX_ROWS * 64], s_td2[QR_MAX_ROWS * 64];  // [R][K], K <= 64 (checked by the host)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * R;
+    const int rows = min(R, B - b0);
+    const int ldk = A * N;  // outputs of one head
+    if (dout != nullptr)
+        for (int i = tid; i < rows * nlog_p; i += QR_THREADS) dout[(int64_t)b0 * nlog_p + i] = 0.f;
+    if (tid < R) {
+        const bool on = tid < rows;
+        s_action[tid] = on ? action[b0 + tid] : -1;
+        s_r[tid] = on ? reward[b0 + tid] : 0.f;
+        s_nt[tid] = on ? 1.f - (float)terminal[b0 + tid] : 0.f;
+        s_w[tid] = (on && loss_weights != nullptr) ? loss_weights[b0 + tid] : 1.f;
+    }
+    __syncthreads();
+    const float inv_n = 1.f / (float)N;
+    for (int pr = wave; pr < R * K; pr += QR_WAVES) {
+        const int bl = pr / K, k = pr - bl * K;
+        if (bl >= rows) {
+            if (lane == 0) s_l[pr] = s_td2[pr] = 0.f;
+            continue;
+        }
+        const int b = b0 + bl;
+        const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(tg0 + k) * ldk;
+        // a*: first argmax of the deciding head's means (strict >: the lowest index wins); tv: the value head's quantiles at a*
+        const float* drow = nrow;
+        if (slogits != nullptr) {  // Double Q-learning: the selector head decides, the value head supplies the atoms
+            drow = slogits + (int64_t)b * s_pitch + (int64_t)(sh + k) * ldk;
+            ISDQN_BOUNDS_CHECK(drow + min(lane, ldk - 1), 4, 32);
+        }
+        ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 33);
+        float tv[QR_PER_LANE], x[QR_AHEAD][QR_PER_LANE];
+        int best = 0;
+        float mx = -INFINITY;
+        for (int a0 = 0; a0 < A; a0 += QR_AHEAD) {  // QR_AHEAD rows in flight, reduced and compared in ascending a
+#pragma unroll
+            for (int d = 0; d < QR_AHEAD; ++d) qr_load(drow + (int64_t)min(a0 + d, A - 1) * N, N, lane, x[d]);
+#pragma unroll
+            for (int d = 0; d < QR_AHEAD; ++d) {
+                const float m = qr_reduce(x[d], N);
+                if (a0 + d < A && (m > mx || a0 + d == 0)) {
+                    mx = m;
+                    best = a0 + d;
+#pragma unroll
+                    for (int t = 0; t < QR_PER_LANE; ++t) tv[t] = x[d][t];
+                }
+            }
+        }
+        if (slogits != nullptr) mx = qr_mean(nrow + (int64_t)best * N, N, lane, tv);
+        const float disc = s_nt[bl] * gamma_n;
+        const float tg = s_r[bl] + disc * mx;
+#pragma unroll
+        for (int t = 0; t < QR_PER_LANE; ++t) tv[t] = s_r[bl] + disc * tv[t];  // the target atoms t_j, j = lane + 64 t
+        float th[QR_PER_LANE], g[QR_PER_LANE], ls[QR_PER_LANE];
+        const float qv = qr_mean(logits + (int64_t)b * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * N, N, lane, th);
+        qr_pairwise<NT, HUBER>(th, tv, N, lane, kappa, g, ls);
+        const float scale = s_w[bl] / (float)(B * N);
+        float l = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int i = lane + 64 * t;
+            if (i < N) {
+                const float gs = HUBER ? g[t] / kappa : g[t];
+                l += (HUBER ? ls[t] / kappa : ls[t]) * inv_n;
+                s_dl[(int64_t)pr * N + i] = -(scale * gs);
+            }
+        }
+        l = qr_wave_sum(l);
+        if (lane == 0) {
+            s_l[pr] = l * s_w[bl];  // (s_td2 stays unweighted: the priorities are the raw TD error)
+            s_td2[pr] = (qv - tg) * (qv - tg);
+            if (q_values) q_values[(int64_t)b * K + k] = qv;
+            if (targets) targets[(int64_t)b * K + k] = tg;
+        }
+    }
+    __syncthreads();  // dout zero-fill (this workgroup's rows), s_dl / s_l / s_td2 complete
+    for (int k = tid; k < K; k += QR_THREADS) {
+        float sum = 0.f;
+        for (int bl = 0; bl < R; ++bl) sum += s_l[bl * K + k];
+        loss_part[(int64_t)blockIdx.x * K + k] = sum;
+    }
+    if (dout != nullptr) {
+        for (int i = tid; i < rows * K * N; i += QR_THREADS) {
+            const int pr = i / N, j = i - pr * N;
+            const int bl = pr / K, k = pr - bl * K;
+            dout[(int64_t)(b0 + bl) * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * N + j] = s_dl[i];
+        }
+        // column c = (h * A + a) * N + j collects the rows whose action is a, for the regressed heads h in [on0, on0 + K)
+        for (int c = tid; c < nlog_p; c += QR_THREADS) {
+            const int h = c / ldk, rem = c - h * ldk, a = rem / N, j = rem - a * N;
+            float sum = 0.f;
+            if (h >= on0 && h < on0 + K)
+                for (int bl = 0; bl < rows; ++bl) sum += (s_action[bl] == a) ? s_dl[((int64_t)bl * K + h - on0) * N + j] : 0.f;
+            dbh_part[(int64_t)blockIdx.x * nlog_p + c] = sum;
+        }
+    }
+    if (priorities != nullptr && tid < rows) {
+        float sum = 0.f;
+        for (int k = 0; k < K; ++k) sum += s_td2[tid * K + k];
+        priorities[b0 + tid] = sqrt((double)(sum / (float)K) + 1e-10);
+    }
+}
+
+// Transitions per workgroup of qr_loss_kernel: QR_MAX_ROWS while the dL/dtheta staging stays within 32 KB of LDS.
+static inline int qr_rows_per_wg(int K, int N) {
+    int R = (8192 / (K * N));
+    return R < 1 ? 1 : R > QR_MAX_ROWS ? QR_MAX_ROWS : R;
+}
+
+}  // namespace isdqn

@@ -43,13 +43,15 @@ _ENGINE = [
     ("-pe", "--priority_exponent", dict(type=float, default=1.0, help="alpha of prioritized replay: leaves hold priority ** alpha. Means nothing without -per.")),
     ("-isb", "--is_beta", dict(type=float, default=0.0, help="Importance-sampling exponent beta at the first gradient step; 0 = no importance-sampling weights. Needs -per.")),
     ("-isbe", "--is_beta_end", dict(type=float, default=None, help="beta at the last gradient step of the run (linear in between); default: constant -isb. Means nothing without -per and -isb.")),
-    ("-hd", "--huber_delta", dict(type=float, default=0.0, help="0: squared TD error (the reference's loss); > 0: Huber loss with this delta.")),
+    ("-hd", "--huber_delta", dict(type=float, default=0.0, help="0: squared TD error (the reference's loss); > 0: Huber loss with this delta. With -qr it is kappa of the quantile Huber loss (0: plain pinball loss); QR-DQN's usual value is 1.")),
     ("-hl", "--histogram_loss", dict(action="store_true", default=False, help="HL-Gauss histogram loss on the heads (the four flags below; off: scalar heads).")),
     # add_histogram_loss_parameters (reference parser_argument.py:199-228): names, types and defaults of the reference
     ("-nb", "--n_bins", dict(type=int, default=50, help="Number of bins composing the histogram.")),
     ("-minn", "--min_value", dict(type=float, default=-100, help="Value of the lowest learnable value of the target.")),
     ("-maxn", "--max_value", dict(type=float, default=100, help="Value of the highest learnable value of the target.")),
     ("-sigma", "--sigma", dict(type=float, default=3, help="Standard deviation of each target sample. If sigma / eta = 0.75, then sigma = 0.75 * (max_value - min_value) / n_bins")),
+    ("-qr", "--quantile_regression", dict(action="store_true", default=False, help="QR-DQN quantile-regression heads (Dabney et al. 2018): every action of every head predicts -nq quantile values, acting uses their means; -hd is kappa. Not with -hl, -mq or -bn.")),
+    ("-nq", "--n_quantiles", dict(type=int, default=32, help="Number of quantiles per action. Means nothing without -qr.")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
     ("-mq", "--munchausen", dict(action="store_true", default=False, help="Munchausen targets (Vieillard et al. 2020): soft-value bootstrap plus the scaled, clipped log-policy of the taken action (the three flags below). Not with -dq.")),
     ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
@@ -125,6 +127,26 @@ def munchausen_kwargs(p) -> dict:
     """The agents' Munchausen keywords from parsed parameters: tau = 0 (off) unless -mq is given."""
     return dict(munchausen_tau=p["munchausen_tau"] if p["munchausen"] else 0.0, munchausen_alpha=p["munchausen_alpha"],
                 munchausen_clip=p["munchausen_clip"])
+
+
+# (-qr and -nq stay out of parameters.json like -hl, -hd and -prec: it holds the reference's groups, which the comparisons between runs read)
+def check_quantiles(p: dict) -> None:
+    """-qr together with -hl, -mq or -bn fails before anything is written, with the agents' own message."""
+    if p.get("quantile_regression"):
+        from slimdqn._engine import check_quantiles as check
+
+        check(p["n_quantiles"], p["n_bins"] if p.get("histogram_loss") else 0, p["munchausen_tau"] if p.get("munchausen") else 0.0,
+              bool(p.get("batch_norm", False)))
+
+
+def quantile_kwargs(p) -> dict:
+    """The agents' quantile-regression keyword from parsed parameters: n_quantiles = 0 (off) unless -qr is given."""
+    return dict(n_quantiles=p["n_quantiles"] if p["quantile_regression"] else 0)
+
+
+def quantile_kappa(p) -> float:
+    """huber_delta for the agents whose entry points never took -hd (DQN, TF-DQN): kappa under -qr, else the 0 they always ran with."""
+    return float(p["huber_delta"]) if p["quantile_regression"] else 0.0
 
 
 def check_engine_arguments(p: dict) -> None:

@@ -30,6 +30,23 @@ def check_munchausen(double_q, munchausen_tau) -> None:
         raise ValueError(MUNCHAUSEN_DOUBLE_Q_REFUSED)
 
 
+QUANTILE_HISTOGRAM_REFUSED = "n_quantiles > 0 and n_bins > 0 exclude each other: a head is either quantile values or a histogram"
+QUANTILE_MUNCHAUSEN_REFUSED = (
+    "n_quantiles > 0 with munchausen_tau > 0 is not built: the Munchausen target of quantile heads is M-IQN's atom-wise form")
+QUANTILE_BATCH_NORM_REFUSED = "n_quantiles > 0 with batch_norm is not built (ISDQN_ERR_UNSUPPORTED)"
+
+
+def check_quantiles(n_quantiles, n_bins=0, munchausen_tau=0.0, batch_norm=False) -> None:
+    """The combinations the library refuses with quantile heads, said before anything is allocated or written."""
+    if int(n_quantiles) > 0:
+        if int(n_bins) > 0:
+            raise ValueError(QUANTILE_HISTOGRAM_REFUSED)
+        if float(munchausen_tau) > 0.0:
+            raise ValueError(QUANTILE_MUNCHAUSEN_REFUSED)
+        if batch_norm:
+            raise ValueError(QUANTILE_BATCH_NORM_REFUSED)
+
+
 class QNetEngine:
     """One Q-network (slimdqn/networks/architectures/dqn.py DQNNet + isdqn.py head view) on one GPU."""
 
@@ -57,8 +74,10 @@ class QNetEngine:
         munchausen_tau: float = 0.0,
         munchausen_alpha: float = 0.9,
         munchausen_clip: float = -1.0,
+        n_quantiles: int = 0,
     ):
         check_munchausen(double_q, munchausen_tau)
+        check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
         _hip.require_gpu()
         self.lib = _hip.lib()
         self.device = _hip.resolve_device(device)
@@ -98,6 +117,10 @@ class QNetEngine:
         cfg.n_bins = int(n_bins)
         cfg.hl_min, cfg.hl_max, cfg.hl_sigma = (float(min_value), float(max_value), float(sigma)) if n_bins else (0.0, 0.0, 0.0)
         self.n_bins = int(n_bins)
+        # n_quantiles > 0: QR-DQN heads (n_heads * n_actions * n_quantiles quantile values, region "logits"; kappa = huber_delta);
+        # forward still returns Q-values, their means
+        cfg.n_quantiles = int(n_quantiles)
+        self.n_quantiles = int(n_quantiles)
         # Double Q-learning targets (include/isdqn_hip.h, isdqn_net_config::double_q); the *_target forms then keep the target
         # network's rows in region "q_target"
         cfg.double_q = 1 if double_q else 0
