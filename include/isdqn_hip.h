@@ -223,6 +223,39 @@ typedef struct isdqn_net_config {
                                            * learn / loss entry points (DQN) return ISDQN_ERR_UNSUPPORTED with it: the reference's
                                            * DQN cannot run with it either (dqn.py:86 applies the network without a mutable
                                            * batch_stats collection).                                                           */
+    int32_t categorical;                  /* (between batch_norm and n_bins, whose loss it switches: huber_delta .. batch_norm and n_bins,
+                                           * n_quantiles, hl_min stay contiguous and the struct still ends in hl_sigma, double_q.)  The C51
+                                           * categorical projection loss (Bellemare, Dabney and Munos, "A Distributional Perspective on
+                                           * Reinforcement Learning", ICML 2017) on the histogram heads.  0: off -- every result, workspace
+                                           * size and region offset keeps the bits it had before the field existed.  1: on.  Anything else:
+                                           * ISDQN_ERR_ARG; 1 with n_bins = 0 or with n_quantiles > 0: ISDQN_ERR_ARG; with munchausen_tau >
+                                           * 0: ISDQN_ERR_UNSUPPORTED (the atom-wise Munchausen form is a follow-up); huber_delta > 0,
+                                           * batch_norm, more than 64 regressed heads and n_heads * n_actions * n_bins > 5456 are refused
+                                           * exactly as the histogram heads refuse them.  hl_sigma is ignored (it may be 0).  THE
+                                           * definition, with categorical = 1: the heads are the histogram heads of n_bins = nb with the
+                                           * same layout -- logit ((h * A) + a) * nb + j is atom j of action a of head h, eta = (hl_max -
+                                           * hl_min) / nb, the atoms are the bin centres z_j = c_j = hl_min + (j + 1/2) eta (Bellemare's 51
+                                           * atoms on [-10, 10] are nb = 51 on [-10.2, 10.2]), Q_h(s, a) = sum_j softmax(l_{h,a})_j z_j;
+                                           * forward, best_action(s) and shift_params do not change at all.  For every regressed pair
+                                           * k < K with online head o = online_head + k and value head v = target_head + k:
+                                           *     a*    = the FIRST index attaining max_a Q^val_v(s', a); with double_q = 1 the first argmax
+                                           *             of Q^sel_{online_head+k}(s', .) (same parameters or target_params exactly as for
+                                           *             HL-Gauss heads)
+                                           *     p_j   = softmax(l^val_v(s', a*))_j
+                                           *     g     = (1 - terminal) * gamma^n
+                                           *     Tz_j  = min(max(r + g * z_j, z_0), z_{nb-1})
+                                           *     b_j   = (Tz_j - z_0) / eta                              in [0, nb - 1]
+                                           *     m_i   = sum_j p_j * max(0, 1 - |b_j - i|)               summed in ascending j
+                                           *     l_bk  = logsumexp(l^on_o(s, a_b)) - sum_i m_i * l^on_o(s, a_b)_i
+                                           *     losses[k] = (1 / B) sum_b w_b l_bk
+                                           *     dL/dl_i   = w_b (softmax(l^on)_i - m_i) / B on the taken action's nb logits of head o, zero on
+                                           *             every other output
+                                           * m is the usual C51 projection written as a gather: in exact arithmetic it equals the
+                                           * floor / floor + 1 scatter form, has no l == u case (an atom landing exactly on a support point
+                                           * keeps its mass) and needs no atomics.  No gradient flows through p, a* or any target term.
+                                           * q_values = the online expectation; targets = the unclamped scalar r + g * Q^val_v(s', a*);
+                                           * priorities = sqrt(mean_k (q - target)^2 + 1e-10) on those scalars, not the cross-entropy;
+                                           * loss_weights, losses_accum and priorities_ready behave as without the option.           */
     int32_t n_bins;                       /* 0: scalar Q heads (the reference's network).  2..256: HL-Gauss histogram loss ("Stop
                                            * Regressing", Farebrother et al. 2024; the flags of the reference's
                                            * add_histogram_loss_parameters, parser_argument.py:199-228): the last Dense has

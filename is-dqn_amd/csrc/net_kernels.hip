@@ -16,6 +16,7 @@
 #include "munchausen.h"
 #include "hl_gauss.h"
 #include "quantile.h"
+#include "categorical.h"
 #include "net_plan.h"
 #include "net_problems.h"
 
@@ -1760,7 +1761,7 @@ static int loss_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, 
 }
 
 // targets, per-transition loss and dL/d(head output) of rows [0, B) from the head outputs of a finished forward (TD loss on the Q rows, or
-// the HL-Gauss loss on the logit rows, the quantile-regression loss on the quantile rows), then loss_finalize over the head layer's width (nlog_p: nha_p without histogram heads).
+// the HL-Gauss or the categorical projection loss on the logit rows, the quantile-regression loss on the quantile rows), then loss_finalize over the head layer's width (nlog_p: nha_p without histogram heads).
 // `val_rows`: head-output rows [B][nlog_p] of the next states that supply the bootstrap value (null: rows [B, 2B) of the forward);
 // `double_q`: selector head on0 + k of rows [B, 2B) of the forward -- the online parameters on the next states -- picks the action;
 // Munchausen targets (cfg->munchausen_tau > 0): `state_val_rows`, head-output rows [B][nlog_p] of the states from the network that
@@ -1775,7 +1776,7 @@ static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* 
     const float* next_rows = ws + P.out_off + (int64_t)B * P.nlog_p;
     if (val_rows == nullptr) val_rows = next_rows;
     const float* sel_rows = double_q ? next_rows : nullptr;
-    const int hl_R = P.head_nb > 0 ? (P.qr ? qr_rows_per_wg(K, P.head_nb) : hl_rows_per_wg(K, P.head_nb)) : 0;
+    const int hl_R = P.head_nb > 0 ? (P.qr ? qr_rows_per_wg(K, P.head_nb) : P.c51 ? c51_rows_per_wg(K, P.head_nb) : hl_rows_per_wg(K, P.head_nb)) : 0;
     const int n_blk = hl_R ? ceil_div(B, hl_R) : ceil_div(B, TD_ROWS);
     float* loss_part = ws + P.lpart_off;
     float* dbh_part = loss_part + (int64_t)n_blk * K;
@@ -1792,6 +1793,16 @@ static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* 
             nt == 1 ? launch_qr(qr_loss_kernel<1, true>) : nt == 2 ? launch_qr(qr_loss_kernel<2, true>) : nt == 3 ? launch_qr(qr_loss_kernel<3, true>) : launch_qr(qr_loss_kernel<4, true>);
         else
             nt == 1 ? launch_qr(qr_loss_kernel<1, false>) : nt == 2 ? launch_qr(qr_loss_kernel<2, false>) : nt == 3 ? launch_qr(qr_loss_kernel<3, false>) : launch_qr(qr_loss_kernel<4, false>);
+    } else if (P.c51) {
+        // categorical projection loss on the histogram heads (categorical.h): NT = 64-atom groups a lane owns
+        auto launch_c51 = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(n_blk), dim3(C51_THREADS), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows, sel_rows,
+                               P.nlog_p, on0, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.head_nb,
+                               batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, learn ? ws + P.dout_off : nullptr, qv, tg,
+                               priorities, loss_part, dbh_part);
+        };
+        const int nt = ceil_div(P.head_nb, 64);
+        nt == 1 ? launch_c51(c51_loss_kernel<1>) : nt == 2 ? launch_c51(c51_loss_kernel<2>) : nt == 3 ? launch_c51(c51_loss_kernel<3>) : launch_c51(c51_loss_kernel<4>);
     } else if (hl_R)
         hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows,
                            sel_rows, P.nlog_p, on0, mun_rows, P.nlog_p, tg0, mu, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.head_nb, P.hl_sigma,

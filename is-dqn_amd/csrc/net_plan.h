@@ -90,9 +90,10 @@ struct Plan {
     int64_t x0_off;  // BatchNorm, cnn: the network input frames / 255 as S8 [N2][h * w][8]; fc: concat(state, next_state) fp32 [N2][obs]
     int n_heads, n_actions, nha, nha_p;
     // head layer width: nha Q-values, or nha * head_nb outputs with per-action blocks of head_nb values: the logits of the HL-Gauss
-    // histogram loss (cfg->n_bins > 0) or the quantile values of QR-DQN (cfg->n_quantiles > 0; `qr` says which loss runs)
+    // histogram loss (cfg->n_bins > 0) or the quantile values of QR-DQN (cfg->n_quantiles > 0; `qr` says which loss runs); `c51`:
+    // the histogram heads train on the C51 categorical projection loss (cfg->categorical) instead of HL-Gauss
     int nlog, nlog_p, head_nb;
-    bool qr;
+    bool qr, c51;
     float hl_min, hl_max, hl_sigma;
     // K regressed heads; head k + oh (online rows) is regressed on head k (next-state rows).  iS-DQN: n_heads = 1 + K,
     // oh = 1 (isdqn.py:96-98).  A single head (n_heads = 1) is TF-DQN: K = 1, oh = 0 -- the head is regressed on its own
@@ -149,9 +150,16 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "n_quantiles > 0: quantile heads are not built for BatchNorm networks");
     }
     ISDQN_REQUIRE(cfg->n_bins == 0 || (cfg->n_bins >= 2 && cfg->n_bins <= 256), ISDQN_ERR_ARG, "n_bins must be 0 (off) or in [2, 256]");
+    ISDQN_REQUIRE(cfg->categorical == 0 || cfg->categorical == 1, ISDQN_ERR_ARG, "categorical must be 0 or 1");
+    if (cfg->categorical == 1) {  // (huber_delta, batch_norm and the size limits: refused below, as the histogram heads refuse them)
+        ISDQN_REQUIRE(cfg->n_quantiles == 0, ISDQN_ERR_ARG, "categorical = 1 and n_quantiles > 0 exclude each other");
+        ISDQN_REQUIRE(cfg->n_bins > 0, ISDQN_ERR_ARG, "categorical = 1 needs the histogram heads (n_bins > 0)");
+        ISDQN_REQUIRE(cfg->munchausen_tau == 0.f, ISDQN_ERR_UNSUPPORTED,
+                      "categorical = 1: Munchausen targets (munchausen_tau > 0) are not built for the categorical loss");
+    }
     if (cfg->n_bins > 0) {
         ISDQN_REQUIRE(cfg->hl_max > cfg->hl_min, ISDQN_ERR_ARG, "histogram loss: hl_max must be > hl_min");
-        ISDQN_REQUIRE(cfg->hl_sigma > 0.f, ISDQN_ERR_ARG, "histogram loss: hl_sigma must be > 0");
+        ISDQN_REQUIRE(cfg->categorical == 1 || cfg->hl_sigma > 0.f, ISDQN_ERR_ARG, "histogram loss: hl_sigma must be > 0");
         ISDQN_REQUIRE(cfg->huber_delta == 0.f, ISDQN_ERR_ARG, "huber_delta and the histogram loss (n_bins > 0) exclude each other");
         ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "the histogram loss is not built for BatchNorm networks");
     }
@@ -169,6 +177,7 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.nha = cfg->n_heads * cfg->n_actions;
     P.nha_p = round_up(P.nha, 8);
     P.qr = cfg->n_quantiles > 0;
+    P.c51 = cfg->categorical == 1;
     P.head_nb = P.qr ? cfg->n_quantiles : cfg->n_bins;
     P.hl_min = cfg->hl_min; P.hl_max = cfg->hl_max; P.hl_sigma = cfg->hl_sigma;
     P.nlog = P.head_nb > 0 ? P.nha * P.head_nb : P.nha;

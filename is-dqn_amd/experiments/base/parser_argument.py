@@ -50,6 +50,7 @@ _ENGINE = [
     ("-minn", "--min_value", dict(type=float, default=-100, help="Value of the lowest learnable value of the target.")),
     ("-maxn", "--max_value", dict(type=float, default=100, help="Value of the highest learnable value of the target.")),
     ("-sigma", "--sigma", dict(type=float, default=3, help="Standard deviation of each target sample. If sigma / eta = 0.75, then sigma = 0.75 * (max_value - min_value) / n_bins")),
+    ("-cat", "--categorical", dict(action="store_true", default=False, help="With -hl: train the histogram heads on the C51 categorical projection loss (Bellemare et al. 2017) instead of HL-Gauss; the atoms are the bin centres (the paper's 51 atoms on [-10, 10]: -nb 51 -minn -10.2 -maxn 10.2), -sigma is ignored. Needs -hl; not with -qr or -mq.")),
     ("-qr", "--quantile_regression", dict(action="store_true", default=False, help="QR-DQN quantile-regression heads (Dabney et al. 2018): every action of every head predicts -nq quantile values, acting uses their means; -hd is kappa. Not with -hl, -mq or -bn.")),
     ("-nq", "--n_quantiles", dict(type=int, default=32, help="Number of quantiles per action. Means nothing without -qr.")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
@@ -149,6 +150,16 @@ def quantile_kappa(p) -> float:
     return float(p["huber_delta"]) if p["quantile_regression"] else 0.0
 
 
+# (-cat stays out of parameters.json like -hl, which it modifies)
+def check_categorical(p: dict) -> None:
+    """-cat without -hl, or with -qr or -mq, fails before anything is written, with the agents' own message."""
+    if p.get("categorical"):
+        from slimdqn._engine import check_categorical as check
+
+        check(True, p["n_bins"] if p.get("histogram_loss") else 0, p["n_quantiles"] if p.get("quantile_regression") else 0,
+              p["munchausen_tau"] if p.get("munchausen") else 0.0)
+
+
 def check_engine_arguments(p: dict) -> None:
     if p["is_beta"] != 0.0 and not p["prioritized"]:
         raise ValueError("-isb / --is_beta weighs prioritized samples: it needs -per / --prioritized")
@@ -161,5 +172,9 @@ def n_gradient_steps(p: dict) -> int:
 
 
 def histogram_loss_kwargs(p) -> dict:
-    """The agents' histogram-loss keywords from parsed parameters: n_bins = 0 (scalar heads) unless -hl is given."""
-    return dict(n_bins=p["n_bins"] if p["histogram_loss"] else 0, min_value=p["min_value"], max_value=p["max_value"], sigma=p["sigma"])
+    """The agents' histogram-loss keywords from parsed parameters: n_bins = 0 (scalar heads) unless -hl is given.  -cat adds
+    categorical=True (the C51 loss on those heads); without it the keywords are the ones they were before the flag existed."""
+    kw = dict(n_bins=p["n_bins"] if p["histogram_loss"] else 0, min_value=p["min_value"], max_value=p["max_value"], sigma=p["sigma"])
+    if p.get("categorical"):
+        kw["categorical"] = True
+    return kw

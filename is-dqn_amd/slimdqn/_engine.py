@@ -47,6 +47,23 @@ def check_quantiles(n_quantiles, n_bins=0, munchausen_tau=0.0, batch_norm=False)
             raise ValueError(QUANTILE_BATCH_NORM_REFUSED)
 
 
+CATEGORICAL_NEEDS_HISTOGRAM = "categorical needs the histogram heads: n_bins > 0 (the entry points: -cat modifies -hl)"
+CATEGORICAL_QUANTILE_REFUSED = "categorical and n_quantiles > 0 exclude each other: the categorical loss is one of the histogram heads"
+CATEGORICAL_MUNCHAUSEN_REFUSED = (
+    "categorical with munchausen_tau > 0 is not built: the Munchausen target of a categorical head is an atom-wise form")
+
+
+def check_categorical(categorical, n_bins=0, n_quantiles=0, munchausen_tau=0.0) -> None:
+    """The combinations the library refuses with the categorical loss, said before anything is allocated or written."""
+    if categorical:
+        if int(n_quantiles) > 0:
+            raise ValueError(CATEGORICAL_QUANTILE_REFUSED)
+        if int(n_bins) <= 0:
+            raise ValueError(CATEGORICAL_NEEDS_HISTOGRAM)
+        if float(munchausen_tau) > 0.0:
+            raise ValueError(CATEGORICAL_MUNCHAUSEN_REFUSED)
+
+
 class QNetEngine:
     """One Q-network (slimdqn/networks/architectures/dqn.py DQNNet + isdqn.py head view) on one GPU."""
 
@@ -75,8 +92,10 @@ class QNetEngine:
         munchausen_alpha: float = 0.9,
         munchausen_clip: float = -1.0,
         n_quantiles: int = 0,
+        categorical: bool = False,
     ):
         check_munchausen(double_q, munchausen_tau)
+        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
         _hip.require_gpu()
         self.lib = _hip.lib()
@@ -117,6 +136,11 @@ class QNetEngine:
         cfg.n_bins = int(n_bins)
         cfg.hl_min, cfg.hl_max, cfg.hl_sigma = (float(min_value), float(max_value), float(sigma)) if n_bins else (0.0, 0.0, 0.0)
         self.n_bins = int(n_bins)
+        # categorical: the histogram heads train on the C51 categorical projection loss (include/isdqn_hip.h,
+        # isdqn_net_config::categorical) instead of HL-Gauss; sigma is then ignored.  False leaves the field at its 0
+        if categorical:
+            cfg.categorical = 1
+        self.categorical = bool(categorical)
         # n_quantiles > 0: QR-DQN heads (n_heads * n_actions * n_quantiles quantile values, region "logits"; kappa = huber_delta);
         # forward still returns Q-values, their means
         cfg.n_quantiles = int(n_quantiles)

@@ -47,6 +47,7 @@ class NetConfig(ctypes.Structure):
         ("munchausen_alpha", c_float),
         ("munchausen_clip", c_float),
         ("batch_norm", c_int32),
+        ("categorical", c_int32),  # 0: off; 1: the C51 categorical projection loss on the histogram heads of n_bins (include/isdqn_hip.h)
         ("n_bins", c_int32),  # 0: scalar heads; > 0: HL-Gauss histogram loss over [hl_min, hl_max] (include/isdqn_hip.h)
         ("n_quantiles", c_int32),  # 0: off; 2..256: QR-DQN quantile-regression heads, kappa = huber_delta (include/isdqn_hip.h)
         ("hl_min", c_float),

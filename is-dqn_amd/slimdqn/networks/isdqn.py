@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import QNetEngine, check_munchausen, check_quantiles
+from slimdqn._engine import QNetEngine, check_categorical, check_munchausen, check_quantiles
 from slimdqn.networks._agent import DeviceParams, EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -56,8 +56,12 @@ class iSDQN(EngineAgent):
         munchausen_alpha: float = 0.9,
         munchausen_clip: float = -1.0,
         n_quantiles: int = 0,
+        categorical: bool = False,
     ):
-        """``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
+        """``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
+        isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
+        ``n_quantiles`` > 0 or Munchausen targets (ValueError).
+        ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
         quantile-regression loss with kappa = ``huber_delta`` (include/isdqn_hip.h, isdqn_net_config::n_quantiles); acting uses
         their means.  Not with ``n_bins`` > 0, Munchausen targets or batch_norm (ValueError).
         ``munchausen_tau`` > 0: Munchausen targets (Vieillard et al. 2020) -- the bootstrap value is the soft value
@@ -69,6 +73,7 @@ class iSDQN(EngineAgent):
         ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
         cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
         check_munchausen(double_q, munchausen_tau)
+        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
         self.n_bellman_iterations = n_bellman_iterations
         self.last_idx_mlp = len(features) if architecture_type == "fc" else len(features) - 3
@@ -82,7 +87,7 @@ class iSDQN(EngineAgent):
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
-                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles)
+                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from slimdqn._engine import check_quantiles
+from slimdqn._engine import check_categorical, check_quantiles
 from slimdqn.networks._agent import EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -49,8 +49,12 @@ class TFDQN(EngineAgent):
         munchausen_clip: float = -1.0,
         n_quantiles: int = 0,
         huber_delta: float = 0.0,
+        categorical: bool = False,
     ):
-        """``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
+        """``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
+        isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
+        ``n_quantiles`` > 0 or Munchausen targets (ValueError).
+        ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
         quantile-regression loss with kappa = ``huber_delta`` (include/isdqn_hip.h, isdqn_net_config::n_quantiles); acting uses
         their means.  Not with ``n_bins`` > 0, Munchausen targets or batch_norm (ValueError).
         ``huber_delta``: 0 keeps the reference's squared TD error; > 0 trains on the Huber loss (with quantile heads: kappa).
@@ -60,6 +64,7 @@ class TFDQN(EngineAgent):
         ``double_q`` is refused: see DOUBLE_Q_REFUSED."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
+        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, n_actions * max(int(n_bins), int(n_quantiles), 1), layer_norm, batch_norm)
@@ -69,7 +74,7 @@ class TFDQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, batch_norm=batch_norm,
                                 n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta)
+                                huber_delta=huber_delta, categorical=categorical)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54
