@@ -7,55 +7,51 @@
 // Two kernels, both one wave per (row, head / action) with the lanes over the bins, fp32 with max subtraction, every sum a fixed
 // __shfl_xor butterfly (bit-identical from run to run, no atomics):
 //   hl_expect_kernel: logits rows -> Q rows (forward / best_action / best_actions, in front of the argmax kernels);
-//   hl_loss_kernel:   where td_kernel runs for scalar heads (learn / loss / grad, every head selection).
+//   hl_loss_kernel:   where td_kernel runs for scalar heads (learn / loss / grad, every head selection; head_loss.h).
 #pragma once
 
 namespace isdqn {
 
-constexpr int HL_MAX_BINS = 256;
-constexpr int HL_PER_LANE = HL_MAX_BINS / 64;
-constexpr int HL_MAX_ROWS = 4;  // transitions per workgroup of hl_loss_kernel
-
-__device__ __forceinline__ float hl_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ float hl_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
 // The nb logits at `l` (one action of one head) in the lanes' registers: lane owns bins lane + 64 t.  Returns the row maximum and
 // fills e[t] = exp(l_j - max) (0 past nb), *sum = sum_j e_j, *wsum = sum_j e_j c_j.  Every lane ends with the same values.
 __device__ __forceinline__ float hl_softmax_parts(const float* __restrict__ l, int nb, int lane, float vmin, float eta,
-                                                  float (&v)[HL_PER_LANE], float (&e)[HL_PER_LANE], float* sum, float* wsum) {
+                                                  float (&v)[PER_LANE], float (&e)[PER_LANE], float* sum, float* wsum) {
     float m = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < HL_PER_LANE; ++t) {
+    for (int t = 0; t < PER_LANE; ++t) {
         const int j = lane + 64 * t;
         v[t] = j < nb ? l[j] : -INFINITY;
         m = fmaxf(m, v[t]);
     }
-    m = hl_wave_max(m);
+    m = wave_max(m);
     float s = 0.f, w = 0.f;
 #pragma unroll
-    for (int t = 0; t < HL_PER_LANE; ++t) {
+    for (int t = 0; t < PER_LANE; ++t) {
         const int j = lane + 64 * t;
         e[t] = j < nb ? expf(v[t] - m) : 0.f;
         s += e[t];
         w += e[t] * (vmin + ((float)j + 0.5f) * eta);
     }
-    *sum = hl_wave_sum(s);
-    *wsum = hl_wave_sum(w);
+    *sum = wave_sum(s);
+    *wsum = wave_sum(w);
     return m;
 }
 
 __device__ __forceinline__ float hl_expectation(const float* __restrict__ l, int nb, int lane, float vmin, float eta) {
-    float v[HL_PER_LANE], e[HL_PER_LANE], s, w;
+    float v[PER_LANE], e[PER_LANE], s, w;
     hl_softmax_parts(l, nb, lane, vmin, eta, v, e, &s, &w);
     return w / s;
+}
+
+// First argmax of the expectations of the A actions at a head's logit row: strict >, the lowest index wins (argmax_kernel's rule).
+__device__ __forceinline__ int hl_argmax_first(const float* __restrict__ row, int A, int nb, int lane, float vmin, float eta) {
+    int best = 0;
+    float bv = hl_expectation(row, nb, lane, vmin, eta);
+    for (int a2 = 1; a2 < A; ++a2) {
+        const float x = hl_expectation(row + (int64_t)a2 * nb, nb, lane, vmin, eta);
+        if (x > bv) { bv = x; best = a2; }
+    }
+    return best;
 }
 
 // Soft value tau log(sum_a exp(Q_a / tau)) of the A expectations of one head's logits at `row` (munchausen.h: the maximum is
@@ -89,87 +85,61 @@ __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict_
     if (lane == 0) q[(int64_t)row * nha_p + c] = qv;
 }
 
-// Iterated Bellman target on expectations + HL-Gauss cross-entropy.  Workgroup = R <= HL_MAX_ROWS transitions; wave w takes the
-// (transition, k) pairs w, w + 4, ...: online head on0 + k at the taken action is regressed on head tg0 + k of the next-state rows.
+// Iterated Bellman target on expectations + HL-Gauss cross-entropy, in the frame of head_loss.h (THE contract: there).  Wave w of 4 takes
+// the (transition, k) pairs w, w + 4, ...
 //   target = r + (1 - terminal) gamma^n max_a' Q_{tg0+k}(s', a');  y = clamp(target, v_min, v_max)
 //   u_i = erf((e_i - y) / (sqrt(2) sigma)),  p_j = (u_{j+1} - u_j) / (u_nb - u_0)   (the clamp keeps u_nb - u_0 away from 0/0)
-//   CE = w_b (logsumexp(l) - sum_j p_j l_j),  dL/dl_j = w_b (softmax(l)_j - p_j) / B on the taken action's nb logits, 0 elsewhere
-//   (w_b: isdqn_batch.loss_weights, 1 without).
-// `vlogits`: the value rows of the B next states (pitch nlog_p).  `slogits` != null (isdqn_net_config::double_q): max_a' becomes the
-// value head's expectation at the first argmax of the expectations of head sh + k of the selector rows (pitch s_pitch).
-// `mlogits` != null (isdqn_net_config::munchausen_tau > 0, munchausen.h): the target is the Munchausen one on the expectations of
-// the value head -- head mh + k of the STATE rows `mlogits` (pitch m_pitch) for the bonus, the soft value of the value rows.
-// Writes q_values / targets [B][K] (expectation, unclamped scalar target), priorities[B] = sqrt(mean_k (q - target)^2 + 1e-10) --
-// the expectations' TD error, not the CE (which never falls below the target histogram's entropy) -- per-workgroup partials of the
-// per-pair CE sums (loss_part [n_blk][K]) and, with `dout`, the dL/dlogits rows (zero-filled) and their column sums over the
-// workgroup's rows (dbh_part [n_blk][nlog_p], the head-bias gradient); loss_finalize_kernel reduces both in a fixed order.
+//   CE = w_b (logsumexp(l) - sum_j p_j l_j),  dL/dl_j = w_b (softmax(l)_j - p_j) / B on the taken action's nb logits, 0 elsewhere.
+// a.sel != null: max_a' becomes the value head's expectation at the first argmax of the expectations of the selector head.
+// a.mun != null: the target is the Munchausen one on the expectations of the value head -- its state row for the bonus, the soft
+// value of its next-state row.  q_values / targets: the expectation and the unclamped scalar target.
 // Dynamic LDS: R * K * nb floats of dL/dl.
-__global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ logits, const float* __restrict__ vlogits,
-                                                      const float* __restrict__ slogits, int s_pitch, int sh, const float* mlogits, int m_pitch,
-                                                      int mh, Munchausen mu, int B, int R, int K, int on0, int tg0, int A,
-                                                      int nb, int nlog_p, float vmin, float eta, float sigma,
-                                                      const int* __restrict__ action, const float* __restrict__ reward,
-                                                      const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
-                                                      float gamma_n, float* __restrict__ dout,
-                                                      float* __restrict__ q_values, float* __restrict__ targets,
-                                                      double* __restrict__ priorities, float* __restrict__ loss_part,
-                                                      float* __restrict__ dbh_part) {
+__global__ __launch_bounds__(256) void hl_loss_kernel(const HeadLossArgs a) {
     extern __shared__ float s_dl[];  // [R][K][nb]
-    __shared__ int s_action[HL_MAX_ROWS];
-    __shared__ float s_r[HL_MAX_ROWS], s_nt[HL_MAX_ROWS], s_w[HL_MAX_ROWS];  // s_w: importance-sampling weights (none: 1)
-    __shared__ float s_ce[HL_MAX_ROWS * 64], s_td2[HL_MAX_ROWS * 64];  // [R][K], K <= 64 (checked by the host)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ LossStage st;
+    const float *__restrict__ logits = a.out, *__restrict__ vlogits = a.val, *__restrict__ slogits = a.sel, *mlogits = a.mun;
+    float *__restrict__ q_values = a.q_values, *__restrict__ targets = a.targets;
+    const int B = a.B, R = a.R, K = a.K, A = a.A, nb = a.nb, nlog_p = a.pitch;
+    const float vmin = a.vmin, eta = a.eta, gamma_n = a.gamma_n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b0 = blockIdx.x * R;
     const int rows = min(R, B - b0);
     const float inv_b = 1.f / (float)B;
     const int ldk = A * nb;  // logits of one head
-    if (dout != nullptr)
-        for (int i = tid; i < rows * nlog_p; i += 256) dout[(int64_t)b0 * nlog_p + i] = 0.f;
-    if (tid < R) {
-        const bool on = tid < rows;
-        s_action[tid] = on ? action[b0 + tid] : -1;
-        s_r[tid] = on ? reward[b0 + tid] : 0.f;
-        s_nt[tid] = on ? 1.f - (float)terminal[b0 + tid] : 0.f;
-        s_w[tid] = (on && loss_weights != nullptr) ? loss_weights[b0 + tid] : 1.f;
-    }
+    loss_prologue<256>(a, st);
     __syncthreads();
-    const float inv_s = 1.f / (1.41421356237309515f * sigma);
+    const float inv_s = 1.f / (1.41421356237309515f * a.sigma);
     for (int pr = wave; pr < R * K; pr += 4) {
         const int bl = pr / K, k = pr - bl * K;
         if (bl >= rows) {
-            if (lane == 0) s_ce[pr] = s_td2[pr] = 0.f;
+            if (lane == 0) st.loss[pr] = st.td2[pr] = 0.f;
             continue;
         }
         const int b = b0 + bl;
-        const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(tg0 + k) * ldk;
+        const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(a.tg0 + k) * ldk;
         float mx = -INFINITY;
         float tg_m = 0.f;
         if (mlogits != nullptr) {  // Munchausen: bonus from the value head's state row, soft value of its next-state row
-            const float* srow = mlogits + (int64_t)b * m_pitch + (int64_t)(mh + k) * ldk;
+            const float* srow = mlogits + (int64_t)b * a.mun_pitch + (int64_t)(a.mun_head + k) * ldk;
             ISDQN_BOUNDS_CHECK(srow + min(lane, ldk - 1), 4, 31);
             ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 31);
             float qa = 0.f, unused;
-            const float vs = hl_soft_value(srow, A, nb, lane, vmin, eta, mu.tau, s_action[bl], &qa);
-            const float vn = hl_soft_value(nrow, A, nb, lane, vmin, eta, mu.tau, -1, &unused);
-            tg_m = munchausen_target(s_r[bl], s_nt[bl], gamma_n, qa, vs, vn, mu);
+            const float vs = hl_soft_value(srow, A, nb, lane, vmin, eta, a.mu.tau, st.action[bl], &qa);
+            const float vn = hl_soft_value(nrow, A, nb, lane, vmin, eta, a.mu.tau, -1, &unused);
+            tg_m = munchausen_target(st.r[bl], st.nt[bl], gamma_n, qa, vs, vn, a.mu);
             mx = 0.f;
-        } else if (slogits != nullptr) {  // Double Q-learning: first argmax of the selector head's expectations, valued by the value head
-            const float* srow = slogits + (int64_t)b * s_pitch + (int64_t)(sh + k) * ldk;
+        } else if (slogits != nullptr) {  // Double Q-learning: the selector head decides, the value head supplies the value
+            const float* srow = slogits + (int64_t)b * a.sel_pitch + (int64_t)(a.sel_head + k) * ldk;
             ISDQN_BOUNDS_CHECK(srow + min(lane, ldk - 1), 4, 30);
             ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 30);
-            int best = 0;
-            float bv = hl_expectation(srow, nb, lane, vmin, eta);
-            for (int a2 = 1; a2 < A; ++a2) {
-                const float x = hl_expectation(srow + (int64_t)a2 * nb, nb, lane, vmin, eta);
-                if (x > bv) { bv = x; best = a2; }
-            }
+            const int best = hl_argmax_first(srow, A, nb, lane, vmin, eta);
             mx = hl_expectation(nrow + (int64_t)best * nb, nb, lane, vmin, eta);
         } else {
             for (int a2 = 0; a2 < A; ++a2) mx = fmaxf(mx, hl_expectation(nrow + (int64_t)a2 * nb, nb, lane, vmin, eta));
         }
-        const float tg = mlogits != nullptr ? tg_m : s_r[bl] + s_nt[bl] * gamma_n * mx;
-        float v[HL_PER_LANE], e[HL_PER_LANE], s, w;
-        const float m = hl_softmax_parts(logits + (int64_t)b * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * nb, nb, lane,
+        const float tg = mlogits != nullptr ? tg_m : st.r[bl] + st.nt[bl] * gamma_n * mx;
+        float v[PER_LANE], e[PER_LANE], s, w;
+        const float m = hl_softmax_parts(logits + (int64_t)b * nlog_p + (int64_t)(a.on0 + k) * ldk + (int64_t)st.action[bl] * nb, nb, lane,
                                          vmin, eta, v, e, &s, &w);
         const float qv = w / s;
         const float y = fminf(fmaxf(tg, vmin), vmin + (float)nb * eta);
@@ -177,54 +147,24 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const float* __restrict__ 
         const float inv_norm = 1.f / (un - u0), inv_sum = 1.f / s;
         float pl = 0.f;
 #pragma unroll
-        for (int t = 0; t < HL_PER_LANE; ++t) {
+        for (int t = 0; t < PER_LANE; ++t) {
             const int j = lane + 64 * t;
             if (j < nb) {
                 const float p = (erff((vmin + (float)(j + 1) * eta - y) * inv_s) - erff((vmin + (float)j * eta - y) * inv_s)) * inv_norm;
                 pl += p * v[t];
-                s_dl[(int64_t)pr * nb + j] = (e[t] * inv_sum - p) * inv_b * s_w[bl];
+                s_dl[(int64_t)pr * nb + j] = (e[t] * inv_sum - p) * inv_b * st.w[bl];
             }
         }
-        pl = hl_wave_sum(pl);
+        pl = wave_sum(pl);
         if (lane == 0) {
-            s_ce[pr] = (m + logf(s) - pl) * s_w[bl];  // (s_td2 stays unweighted: the priorities are the raw TD error)
-            s_td2[pr] = (qv - tg) * (qv - tg);
+            st.loss[pr] = (m + logf(s) - pl) * st.w[bl];  // (st.td2 stays unweighted: the priorities are the raw TD error)
+            st.td2[pr] = (qv - tg) * (qv - tg);
             if (q_values) q_values[(int64_t)b * K + k] = qv;
             if (targets) targets[(int64_t)b * K + k] = tg;
         }
     }
-    __syncthreads();  // dout zero-fill (this workgroup's rows), s_dl / s_ce / s_td2 complete
-    for (int k = tid; k < K; k += 256) {
-        float sum = 0.f;
-        for (int bl = 0; bl < R; ++bl) sum += s_ce[bl * K + k];
-        loss_part[(int64_t)blockIdx.x * K + k] = sum;
-    }
-    if (dout != nullptr) {
-        for (int i = tid; i < rows * K * nb; i += 256) {
-            const int pr = i / nb, j = i - pr * nb;
-            const int bl = pr / K, k = pr - bl * K;
-            dout[(int64_t)(b0 + bl) * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * nb + j] = s_dl[i];
-        }
-        // column c = (h * A + a) * nb + j collects the rows whose action is a, for the regressed heads h in [on0, on0 + K)
-        for (int c = tid; c < nlog_p; c += 256) {
-            const int h = c / ldk, rem = c - h * ldk, a = rem / nb, j = rem - a * nb;
-            float sum = 0.f;
-            if (h >= on0 && h < on0 + K)
-                for (int bl = 0; bl < R; ++bl) sum += (s_action[bl] == a) ? s_dl[((int64_t)bl * K + h - on0) * nb + j] : 0.f;
-            dbh_part[(int64_t)blockIdx.x * nlog_p + c] = sum;
-        }
-    }
-    if (priorities != nullptr && tid < rows) {
-        float sum = 0.f;
-        for (int k = 0; k < K; ++k) sum += s_td2[tid * K + k];
-        priorities[b0 + tid] = sqrt((double)(sum / (float)K) + 1e-10);
-    }
-}
-
-// Transitions per workgroup of hl_loss_kernel: HL_MAX_ROWS while the dL/dl staging stays within 32 KB of LDS.
-static inline int hl_rows_per_wg(int K, int nb) {
-    int R = (8192 / (K * nb));
-    return R < 1 ? 1 : R > HL_MAX_ROWS ? HL_MAX_ROWS : R;
+    __syncthreads();  // dout zero-fill (this workgroup's rows), s_dl / st.loss / st.td2 complete
+    loss_epilogue<256>(a, st, s_dl);
 }
 
 }  // namespace isdqn

@@ -13,6 +13,7 @@
 #include "conv_img.h"
 #include "conv_u8_pair.h"
 #include "conv_s8_pair.h"
+#include "head_loss.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
 #include "quantile.h"
@@ -329,13 +330,13 @@ __global__ __launch_bounds__(256) void ln_bwd_wide_kernel(const float* __restric
     }
 }
 
-// Iterated Bellman target + squared TD loss (isdqn.py:92-109).
+// Iterated Bellman target + squared TD loss (isdqn.py:92-109); the arguments and THE contract of what it writes: head_loss.h.
 //   q_k(s,a) from head 1+k of the online rows, target_k = r + (1-terminal)*gamma^n*max_a' Q_k(s',a')
 //   from head k of the next-state rows (same parameters, stop-gradient), td = (q - target)^2.
 // One workgroup per 64 transitions, wave w takes heads k = w, w+4, ...  Emits dL/dq rows (dout),
 // q_values/targets/priorities and per-workgroup partials of the per-head loss sums and of the head
 // bias gradient (column sums of dout); loss_finalize_kernel reduces them in a fixed order.
-// `vq`: the value rows of the B next states (pitch nha_p; rows [B, 2B) of `q`, or the target network's own rows).  `sq` != null:
+// `vq` (args.val): the value rows of the B next states (pitch nha_p; rows [B, 2B) of `q`, or the target network's own rows).  `sq` != null:
 // Double Q-learning (isdqn_net_config::double_q) -- the value is taken at the first argmax of head sh + k of the selector rows
 // (pitch sq_pitch; they may come from another forward than the value rows); null: the max form.  `mq` != null: Munchausen targets
 // (munchausen.h) -- the value head th + k (mh + k in `mq`) of the STATE rows `mq` (pitch mq_pitch; rows [0, B) of `q`, or the target
@@ -360,15 +361,18 @@ __device__ __forceinline__ int argmax_first(const float* v, int n) {
     return best;
 }
 constexpr int TD_ROWS = 64;
-__global__ __launch_bounds__(256) void td_kernel(const float* __restrict__ q, const float* __restrict__ vq,
-                                                 const float* __restrict__ sq, int sq_pitch, int sh, const float* mq, int mq_pitch, int mh,
-                                                 Munchausen mu, int B, int K, int oh, int th, int A, int nha_p,
-                                                 const int* __restrict__ action, const float* __restrict__ reward,
-                                                 const uint8_t* __restrict__ terminal, const float* __restrict__ loss_weights,
-                                                 float gamma_n, float huber_delta, float* __restrict__ dout,
-                                                 float* __restrict__ q_values,
-                                                 float* __restrict__ targets, double* __restrict__ priorities,
-                                                 float* __restrict__ loss_part, float* __restrict__ dbh_part) {
+__global__ __launch_bounds__(256) void td_kernel(const HeadLossArgs args) {
+    const float *__restrict__ q = args.out, *__restrict__ vq = args.val, *__restrict__ sq = args.sel, *mq = args.mun;
+    const int sq_pitch = args.sel_pitch, sh = args.sel_head, mq_pitch = args.mun_pitch, mh = args.mun_head;
+    const Munchausen mu = args.mu;
+    const int B = args.B, K = args.K, oh = args.on0, th = args.tg0, A = args.A, nha_p = args.pitch;
+    const int* __restrict__ action = args.action;
+    const uint8_t* __restrict__ terminal = args.terminal;
+    const float *__restrict__ reward = args.reward, *__restrict__ loss_weights = args.loss_weights;
+    const float gamma_n = args.gamma_n, huber_delta = args.huber_delta;
+    float *__restrict__ dout = args.dout, *__restrict__ q_values = args.q_values, *__restrict__ targets = args.targets;
+    float *__restrict__ loss_part = args.loss_part, *__restrict__ dbh_part = args.dbh_part;
+    double* __restrict__ priorities = args.priorities;
     extern __shared__ float s_d[];  // [TD_ROWS][K] : 2*(q-target)/B ; then [TD_ROWS][K] td
     __shared__ int s_action[TD_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1776,42 +1780,45 @@ static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* 
     const float* next_rows = ws + P.out_off + (int64_t)B * P.nlog_p;
     if (val_rows == nullptr) val_rows = next_rows;
     const float* sel_rows = double_q ? next_rows : nullptr;
-    const int hl_R = P.head_nb > 0 ? (P.qr ? qr_rows_per_wg(K, P.head_nb) : P.c51 ? c51_rows_per_wg(K, P.head_nb) : hl_rows_per_wg(K, P.head_nb)) : 0;
-    const int n_blk = hl_R ? ceil_div(B, hl_R) : ceil_div(B, TD_ROWS);
+    const int R = P.head_nb > 0 ? rows_per_wg(K, P.head_nb) : 0;  // distributional kernels: transitions per workgroup
+    const int n_blk = R ? ceil_div(B, R) : ceil_div(B, TD_ROWS);
     float* loss_part = ws + P.lpart_off;
-    float* dbh_part = loss_part + (int64_t)n_blk * K;
-    if (P.qr) {
-        // quantile heads (quantile.h): NT = 64-quantile groups a lane owns, kappa = cfg->huber_delta (0: the plain pinball loss)
-        auto launch_qr = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(n_blk), dim3(QR_THREADS), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows, sel_rows,
-                               P.nlog_p, on0, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, cfg->huber_delta, batch->action, batch->reward,
-                               batch->terminal, batch->loss_weights, cfg->gamma_n, learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part,
-                               dbh_part);
-        };
-        const int nt = ceil_div(P.head_nb, 64);
-        if (cfg->huber_delta > 0.f)
-            nt == 1 ? launch_qr(qr_loss_kernel<1, true>) : nt == 2 ? launch_qr(qr_loss_kernel<2, true>) : nt == 3 ? launch_qr(qr_loss_kernel<3, true>) : launch_qr(qr_loss_kernel<4, true>);
-        else
-            nt == 1 ? launch_qr(qr_loss_kernel<1, false>) : nt == 2 ? launch_qr(qr_loss_kernel<2, false>) : nt == 3 ? launch_qr(qr_loss_kernel<3, false>) : launch_qr(qr_loss_kernel<4, false>);
-    } else if (P.c51) {
-        // categorical projection loss on the histogram heads (categorical.h): NT = 64-atom groups a lane owns
-        auto launch_c51 = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(n_blk), dim3(C51_THREADS), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows, sel_rows,
-                               P.nlog_p, on0, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.head_nb,
-                               batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, learn ? ws + P.dout_off : nullptr, qv, tg,
-                               priorities, loss_part, dbh_part);
-        };
-        const int nt = ceil_div(P.head_nb, 64);
-        nt == 1 ? launch_c51(c51_loss_kernel<1>) : nt == 2 ? launch_c51(c51_loss_kernel<2>) : nt == 3 ? launch_c51(c51_loss_kernel<3>) : launch_c51(c51_loss_kernel<4>);
-    } else if (hl_R)
-        hipLaunchKernelGGL(hl_loss_kernel, dim3(n_blk), dim3(256), (size_t)hl_R * K * P.head_nb * sizeof(float), st, ws + P.logits_off, val_rows,
-                           sel_rows, P.nlog_p, on0, mun_rows, P.nlog_p, tg0, mu, B, hl_R, K, on0, tg0, P.n_actions, P.head_nb, P.nlog_p, P.hl_min, (P.hl_max - P.hl_min) / (float)P.head_nb, P.hl_sigma,
-                           batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n,
-                           learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
+    HeadLossArgs a{};  // (head_loss.h)
+    a.out = ws + P.out_off;
+    a.val = val_rows;
+    a.sel = sel_rows; a.sel_pitch = P.nlog_p; a.sel_head = on0;
+    a.mun = mun_rows; a.mun_pitch = P.nlog_p; a.mun_head = tg0; a.mu = mu;
+    a.B = B; a.R = R; a.K = K; a.on0 = on0; a.tg0 = tg0; a.A = P.n_actions;
+    a.nb = P.head_nb; a.pitch = P.nlog_p;
+    a.vmin = P.hl_min; a.eta = P.head_nb > 0 ? (P.hl_max - P.hl_min) / (float)P.head_nb : 0.f; a.sigma = P.hl_sigma;
+    a.huber_delta = cfg->huber_delta;
+    a.action = batch->action; a.reward = batch->reward; a.terminal = batch->terminal; a.loss_weights = batch->loss_weights;
+    a.gamma_n = cfg->gamma_n;
+    a.dout = learn ? ws + P.dout_off : nullptr;
+    a.q_values = qv; a.targets = tg; a.priorities = priorities;
+    a.loss_part = loss_part; a.dbh_part = loss_part + (int64_t)n_blk * K;
+    auto launch = [&](auto kern, int threads, size_t dyn_lds) { hipLaunchKernelGGL(kern, dim3(n_blk), dim3(threads), dyn_lds, st, a); };
+    const size_t dl_bytes = (size_t)R * K * P.head_nb * sizeof(float);  // s_dl of head_loss.h
+    // NT = 64-value groups of a (head, action) a lane owns: the quantile and the categorical kernels are instantiated per count
+    auto with_nt = [&](auto f) {
+        switch (ceil_div(P.head_nb, 64)) {
+            case 1: f(std::integral_constant<int, 1>{}); break;
+            case 2: f(std::integral_constant<int, 2>{}); break;
+            case 3: f(std::integral_constant<int, 3>{}); break;
+            default: f(std::integral_constant<int, 4>{}); break;
+        }
+    };
+    if (P.qr)  // quantile heads (quantile.h): kappa = cfg->huber_delta (0: the plain pinball loss)
+        with_nt([&](auto nt) {
+            if (cfg->huber_delta > 0.f) launch(qr_loss_kernel<decltype(nt)::value, true>, QR_THREADS, dl_bytes);
+            else launch(qr_loss_kernel<decltype(nt)::value, false>, QR_THREADS, dl_bytes);
+        });
+    else if (P.c51)  // categorical projection loss on the histogram heads (categorical.h)
+        with_nt([&](auto nt) { launch(c51_loss_kernel<decltype(nt)::value>, C51_THREADS, dl_bytes); });
+    else if (R)
+        launch(hl_loss_kernel, 256, dl_bytes);
     else
-        hipLaunchKernelGGL(td_kernel, dim3(n_blk), dim3(256), 2 * TD_ROWS * K * sizeof(float), st, ws + P.q_off, val_rows, sel_rows,
-                           P.nha_p, on0, mun_rows, P.nha_p, tg0, mu, B, K, on0, tg0, P.n_actions, P.nha_p, batch->action, batch->reward, batch->terminal, batch->loss_weights, cfg->gamma_n, cfg->huber_delta,
-                           learn ? ws + P.dout_off : nullptr, qv, tg, priorities, loss_part, dbh_part);
+        launch(td_kernel, 256, 2 * TD_ROWS * K * sizeof(float));
     ISDQN_HIP_CHECK(hipGetLastError());
     return loss_finalize(P, cfg, ws, n_blk, K, P.nlog_p, losses, loss_accum, learn, adam_count, st);
 }

@@ -7,14 +7,11 @@
 // pairwise loss in ascending j): bit-identical from run to run, no atomics.
 //   qr_expect_kernel: quantile rows -> Q rows (forward / best_action / best_actions and the DQN-form target rows, where
 //                     hl_expect_kernel runs for histogram heads);
-//   qr_loss_kernel:   where hl_loss_kernel runs for histogram heads (learn / loss / grad, every head selection).
+//   qr_loss_kernel:   where hl_loss_kernel runs for histogram heads (learn / loss / grad, every head selection; head_loss.h).
 #pragma once
 
 namespace isdqn {
 
-constexpr int QR_MAX_QUANTILES = 256;
-constexpr int QR_PER_LANE = QR_MAX_QUANTILES / 64;
-constexpr int QR_MAX_ROWS = 4;  // transitions per workgroup of qr_loss_kernel
 // Waves per workgroup of qr_loss_kernel.  A (transition, pair) is a chain of dependent steps -- A row loads, each followed by a butterfly,
 // then the N x N loop -- so a wave's time is the number of pairs it takes in turn: 16 waves share the R * K pairs of a workgroup (9 each
 // with 4 waves at K = 9, 98.8 us measured at B = 256; 3 each with 16), and the partial rows the workgroup leaves stay as many.
@@ -22,29 +19,23 @@ constexpr int QR_WAVES = 16;
 constexpr int QR_THREADS = 64 * QR_WAVES;
 constexpr int QR_AHEAD = 4;  // actions whose rows are requested before the first of them is reduced
 
-__device__ __forceinline__ float qr_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // The N quantile values at `th` (one action of one head) into the lanes' registers (0 past N) ...
-__device__ __forceinline__ void qr_load(const float* __restrict__ th, int N, int lane, float (&v)[QR_PER_LANE]) {
+__device__ __forceinline__ void qr_load(const float* __restrict__ th, int N, int lane, float (&v)[PER_LANE]) {
 #pragma unroll
-    for (int t = 0; t < QR_PER_LANE; ++t) {
+    for (int t = 0; t < PER_LANE; ++t) {
         const int i = lane + 64 * t;
         v[t] = i < N ? th[i] : 0.f;
     }
 }
 // ... and their mean: the lane's own values in ascending t, the butterfly, one division -- the same bits in every lane and wherever
 // it is called.
-__device__ __forceinline__ float qr_reduce(const float (&v)[QR_PER_LANE], int N) {
+__device__ __forceinline__ float qr_reduce(const float (&v)[PER_LANE], int N) {
     float s = 0.f;
 #pragma unroll
-    for (int t = 0; t < QR_PER_LANE; ++t) s += v[t];
-    return qr_wave_sum(s) / (float)N;
+    for (int t = 0; t < PER_LANE; ++t) s += v[t];
+    return wave_sum(s) / (float)N;
 }
-__device__ __forceinline__ float qr_mean(const float* __restrict__ th, int N, int lane, float (&v)[QR_PER_LANE]) {
+__device__ __forceinline__ float qr_mean(const float* __restrict__ th, int N, int lane, float (&v)[PER_LANE]) {
     qr_load(th, N, lane, v);
     return qr_reduce(v, N);
 }
@@ -57,7 +48,7 @@ __global__ __launch_bounds__(256) void qr_expect_kernel(const float* __restrict_
     const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= (int64_t)n_rows * nha) return;  // (whole waves: the shuffles below see every lane of theirs)
     const int row = (int)(item / nha), c = (int)(item - (int64_t)row * nha);
-    float v[QR_PER_LANE];
+    float v[PER_LANE];
     const float qv = qr_mean(rows + (int64_t)row * nlog_p + (int64_t)c * N, N, lane, v);
     if (lane == 0) q[(int64_t)row * nha_p + c] = qv;
 }
@@ -67,8 +58,8 @@ __global__ __launch_bounds__(256) void qr_expect_kernel(const float* __restrict_
 // of |tau_i - 1{u < 0}| * clip(u, -kappa, kappa) and |tau_i - 1{u < 0}| * L_kappa(u) (HUBER), or * sign(u) and * |u| (kappa = 0),
 // u = t_j - theta_i.  The indicator is a select and h' a clamp: the loop body has no branch.
 template <int NT, bool HUBER>
-__device__ __forceinline__ void qr_pairwise(const float (&th)[QR_PER_LANE], const float (&tv)[QR_PER_LANE], int N, int lane, float kappa,
-                                            float (&g)[QR_PER_LANE], float (&ls)[QR_PER_LANE]) {
+__device__ __forceinline__ void qr_pairwise(const float (&th)[PER_LANE], const float (&tv)[PER_LANE], int N, int lane, float kappa,
+                                            float (&g)[PER_LANE], float (&ls)[PER_LANE]) {
     float tau[NT], omt[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -102,61 +93,47 @@ __device__ __forceinline__ void qr_pairwise(const float (&th)[QR_PER_LANE], cons
     }
 }
 
-// Iterated Bellman target atoms + quantile-regression (Huber) loss.  Workgroup = R <= QR_MAX_ROWS transitions; wave w of QR_WAVES takes the
-// (transition, k) pairs w, w + QR_WAVES, ...: online head on0 + k at the taken action is regressed on head tg0 + k of the next-state rows.
-//   a* = first argmax_a of the means of the value head (`slogits` != null, isdqn_net_config::double_q: of head sh + k of the selector
-//        rows, pitch s_pitch);  t_j = r + ((1 - terminal) gamma^n) theta^val_j(s', a*);  u_ij = t_j - theta_i(s, a_b)
+// Iterated Bellman target atoms + quantile-regression (Huber) loss, in the frame of head_loss.h (THE contract: there).  Wave w of
+// QR_WAVES takes the (transition, k) pairs w, w + QR_WAVES, ...; kappa = a.huber_delta.
+//   a* = first argmax_a of the means of the value head (a.sel != null: of the selector head);
+//   t_j = r + ((1 - terminal) gamma^n) theta^val_j(s', a*);  u_ij = t_j - theta_i(s, a_b)
 //   l = sum_i (1 / N) sum_j |tau_i - 1{u_ij < 0}| h_kappa(u_ij),  dL/dtheta_i = -(w_b / (B N)) sum_j |tau_i - 1{u_ij < 0}| h'_kappa(u_ij)
-//   on the taken action's N outputs, 0 elsewhere (w_b: isdqn_batch.loss_weights, 1 without).
-// `vlogits`: the value rows of the B next states (pitch nlog_p).  Writes q_values / targets [B][K] (online mean, r + (1 - terminal)
-// gamma^n * mean of the value row at a*), priorities[B] = sqrt(mean_k (q - target)^2 + 1e-10), per-workgroup partials of the per-pair
-// loss sums (loss_part [n_blk][K]) and, with `dout`, the dL/dtheta rows (zero-filled) and their column sums over the workgroup's rows
-// (dbh_part [n_blk][nlog_p], the head-bias gradient); loss_finalize_kernel reduces both in a fixed order.
+//   on the taken action's N outputs, 0 elsewhere.
+// q_values / targets: the online mean and r + (1 - terminal) gamma^n * mean of the value row at a*.
+// The selection below is this kernel's own, not hl_argmax_first's shape: QR_AHEAD rows are requested before the first is reduced (a
+// measured optimisation), and the loop also captures the winning row's quantiles.
 // Dynamic LDS: R * K * N floats of dL/dtheta.
 template <int NT, bool HUBER>
-__global__ __launch_bounds__(QR_THREADS) void qr_loss_kernel(const float* __restrict__ logits, const float* __restrict__ vlogits,
-                                                      const float* __restrict__ slogits, int s_pitch, int sh, int B, int R, int K, int on0,
-                                                      int tg0, int A, int N, int nlog_p, float kappa, const int* __restrict__ action,
-                                                      const float* __restrict__ reward, const uint8_t* __restrict__ terminal,
-                                                      const float* __restrict__ loss_weights, float gamma_n, float* __restrict__ dout,
-                                                      float* __restrict__ q_values, float* __restrict__ targets,
-                                                      double* __restrict__ priorities, float* __restrict__ loss_part,
-                                                      float* __restrict__ dbh_part) {
+__global__ __launch_bounds__(QR_THREADS) void qr_loss_kernel(const HeadLossArgs a) {
     extern __shared__ float s_dl[];  // [R][K][N]
-    __shared__ int s_action[QR_MAX_ROWS];
-    __shared__ float s_r[QR_MAX_ROWS], s_nt[QR_MAX_ROWS], s_w[QR_MAX_ROWS];  // s_w: importance-sampling weights (none: 1)
-    __shared__ float s_l[QR_MAX_ROWS * 64], s_td2[QR_MAX_ROWS * 64];  // [R][K], K <= 64 (checked by the host)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ LossStage st;
+    const float *__restrict__ logits = a.out, *__restrict__ vlogits = a.val, *__restrict__ slogits = a.sel;
+    float *__restrict__ q_values = a.q_values, *__restrict__ targets = a.targets;
+    const int B = a.B, R = a.R, K = a.K, A = a.A, N = a.nb, nlog_p = a.pitch;
+    const float kappa = a.huber_delta;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b0 = blockIdx.x * R;
     const int rows = min(R, B - b0);
     const int ldk = A * N;  // outputs of one head
-    if (dout != nullptr)
-        for (int i = tid; i < rows * nlog_p; i += QR_THREADS) dout[(int64_t)b0 * nlog_p + i] = 0.f;
-    if (tid < R) {
-        const bool on = tid < rows;
-        s_action[tid] = on ? action[b0 + tid] : -1;
-        s_r[tid] = on ? reward[b0 + tid] : 0.f;
-        s_nt[tid] = on ? 1.f - (float)terminal[b0 + tid] : 0.f;
-        s_w[tid] = (on && loss_weights != nullptr) ? loss_weights[b0 + tid] : 1.f;
-    }
+    loss_prologue<QR_THREADS>(a, st);
     __syncthreads();
     const float inv_n = 1.f / (float)N;
     for (int pr = wave; pr < R * K; pr += QR_WAVES) {
         const int bl = pr / K, k = pr - bl * K;
         if (bl >= rows) {
-            if (lane == 0) s_l[pr] = s_td2[pr] = 0.f;
+            if (lane == 0) st.loss[pr] = st.td2[pr] = 0.f;
             continue;
         }
         const int b = b0 + bl;
-        const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(tg0 + k) * ldk;
+        const float* nrow = vlogits + (int64_t)b * nlog_p + (int64_t)(a.tg0 + k) * ldk;
         // a*: first argmax of the deciding head's means (strict >: the lowest index wins); tv: the value head's quantiles at a*
         const float* drow = nrow;
         if (slogits != nullptr) {  // Double Q-learning: the selector head decides, the value head supplies the atoms
-            drow = slogits + (int64_t)b * s_pitch + (int64_t)(sh + k) * ldk;
+            drow = slogits + (int64_t)b * a.sel_pitch + (int64_t)(a.sel_head + k) * ldk;
             ISDQN_BOUNDS_CHECK(drow + min(lane, ldk - 1), 4, 32);
         }
         ISDQN_BOUNDS_CHECK(nrow + min(lane, ldk - 1), 4, 33);
-        float tv[QR_PER_LANE], x[QR_AHEAD][QR_PER_LANE];
+        float tv[PER_LANE], x[QR_AHEAD][PER_LANE];
         int best = 0;
         float mx = -INFINITY;
         for (int a0 = 0; a0 < A; a0 += QR_AHEAD) {  // QR_AHEAD rows in flight, reduced and compared in ascending a
@@ -169,19 +146,19 @@ __global__ __launch_bounds__(QR_THREADS) void qr_loss_kernel(const float* __rest
                     mx = m;
                     best = a0 + d;
 #pragma unroll
-                    for (int t = 0; t < QR_PER_LANE; ++t) tv[t] = x[d][t];
+                    for (int t = 0; t < PER_LANE; ++t) tv[t] = x[d][t];
                 }
             }
         }
         if (slogits != nullptr) mx = qr_mean(nrow + (int64_t)best * N, N, lane, tv);
-        const float disc = s_nt[bl] * gamma_n;
-        const float tg = s_r[bl] + disc * mx;
+        const float disc = st.nt[bl] * a.gamma_n;
+        const float tg = st.r[bl] + disc * mx;
 #pragma unroll
-        for (int t = 0; t < QR_PER_LANE; ++t) tv[t] = s_r[bl] + disc * tv[t];  // the target atoms t_j, j = lane + 64 t
-        float th[QR_PER_LANE], g[QR_PER_LANE], ls[QR_PER_LANE];
-        const float qv = qr_mean(logits + (int64_t)b * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * N, N, lane, th);
+        for (int t = 0; t < PER_LANE; ++t) tv[t] = st.r[bl] + disc * tv[t];  // the target atoms t_j, j = lane + 64 t
+        float th[PER_LANE], g[PER_LANE], ls[PER_LANE];
+        const float qv = qr_mean(logits + (int64_t)b * nlog_p + (int64_t)(a.on0 + k) * ldk + (int64_t)st.action[bl] * N, N, lane, th);
         qr_pairwise<NT, HUBER>(th, tv, N, lane, kappa, g, ls);
-        const float scale = s_w[bl] / (float)(B * N);
+        const float scale = st.w[bl] / (float)(B * N);
         float l = 0.f;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -192,46 +169,16 @@ __global__ __launch_bounds__(QR_THREADS) void qr_loss_kernel(const float* __rest
                 s_dl[(int64_t)pr * N + i] = -(scale * gs);
             }
         }
-        l = qr_wave_sum(l);
+        l = wave_sum(l);
         if (lane == 0) {
-            s_l[pr] = l * s_w[bl];  // (s_td2 stays unweighted: the priorities are the raw TD error)
-            s_td2[pr] = (qv - tg) * (qv - tg);
+            st.loss[pr] = l * st.w[bl];  // (st.td2 stays unweighted: the priorities are the raw TD error)
+            st.td2[pr] = (qv - tg) * (qv - tg);
             if (q_values) q_values[(int64_t)b * K + k] = qv;
             if (targets) targets[(int64_t)b * K + k] = tg;
         }
     }
-    __syncthreads();  // dout zero-fill (this workgroup's rows), s_dl / s_l / s_td2 complete
-    for (int k = tid; k < K; k += QR_THREADS) {
-        float sum = 0.f;
-        for (int bl = 0; bl < R; ++bl) sum += s_l[bl * K + k];
-        loss_part[(int64_t)blockIdx.x * K + k] = sum;
-    }
-    if (dout != nullptr) {
-        for (int i = tid; i < rows * K * N; i += QR_THREADS) {
-            const int pr = i / N, j = i - pr * N;
-            const int bl = pr / K, k = pr - bl * K;
-            dout[(int64_t)(b0 + bl) * nlog_p + (int64_t)(on0 + k) * ldk + (int64_t)s_action[bl] * N + j] = s_dl[i];
-        }
-        // column c = (h * A + a) * N + j collects the rows whose action is a, for the regressed heads h in [on0, on0 + K)
-        for (int c = tid; c < nlog_p; c += QR_THREADS) {
-            const int h = c / ldk, rem = c - h * ldk, a = rem / N, j = rem - a * N;
-            float sum = 0.f;
-            if (h >= on0 && h < on0 + K)
-                for (int bl = 0; bl < rows; ++bl) sum += (s_action[bl] == a) ? s_dl[((int64_t)bl * K + h - on0) * N + j] : 0.f;
-            dbh_part[(int64_t)blockIdx.x * nlog_p + c] = sum;
-        }
-    }
-    if (priorities != nullptr && tid < rows) {
-        float sum = 0.f;
-        for (int k = 0; k < K; ++k) sum += s_td2[tid * K + k];
-        priorities[b0 + tid] = sqrt((double)(sum / (float)K) + 1e-10);
-    }
-}
-
-// Transitions per workgroup of qr_loss_kernel: QR_MAX_ROWS while the dL/dtheta staging stays within 32 KB of LDS.
-static inline int qr_rows_per_wg(int K, int N) {
-    int R = (8192 / (K * N));
-    return R < 1 ? 1 : R > QR_MAX_ROWS ? QR_MAX_ROWS : R;
+    __syncthreads();  // dout zero-fill (this workgroup's rows), s_dl / st.loss / st.td2 complete
+    loss_epilogue<QR_THREADS>(a, st, s_dl);
 }
 
 }  // namespace isdqn
