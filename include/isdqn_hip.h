@@ -491,6 +491,41 @@ int isdqn_net_analysis(const isdqn_net_config* cfg, const float* params, const u
                        const int32_t* frame_ids, const float* obs, int32_t n_rows, float* features_out, float* scores_out,
                        void* workspace, void* stream);
 
+/* ReDo: recycle dormant neurons (Sokar, Agarwal, Castro, Evci 2023, "The Dormant Neuron Phenomenon in Deep Reinforcement
+ * Learning"; the reference has no counterpart -- it only measures them, utils/analysis.py:12-17).  On the device, in place,
+ * stream-ordered, without a host synchronisation.
+ * Recyclable layers: the hidden layers of the cnn and fc architectures in network order (every layer but the last Dense).  A
+ * neuron of a conv layer is an output channel (n_neurons = cout, not npix * cout), of a Dense layer an output feature; the layout
+ * call returns their number and widths (n_neurons may be NULL; at most max_layers entries are written).  scores_out / mask_out
+ * hold sum(n_neurons) entries, the layers concatenated; n_recycled_out holds n_layers entries.
+ * Score: the weight mirror is rebuilt and the network runs without its last layer on `n_rows` observations (1 <= n_rows <=
+ * 2 * batch_size, inputs as in the forward call).  a_c = sum over rows and pixel positions of the post-ReLU activation of
+ * neuron c, divided by n_rows * positions (fp32; fixed order: rows per position first, then positions in ascending order; no
+ * atomics) -> scores_out.  mean_l = the fp32 mean of a over the layer in ascending c.  Neuron c of layer l is dormant iff
+ * a_c <= tau * mean_l (a layer that is zero everywhere is dormant everywhere) -> mask_out (0 / 1), the count per layer ->
+ * n_recycled_out.
+ * Recycle, for every dormant neuron c of layer l, in the internal layout of the parameter layout call:
+ *   - incoming: row c of layer l's kernel (the first convolution's [out][plane][ky][kx] form and padded input lanes included)
+ *     and bias c are copied from the same offsets of `fresh_params` (a parameter buffer of the same layout, e.g. a new
+ *     initialisation); with layer_norm also scale c and bias c of the LayerNorm behind layer l;
+ *   - outgoing: every weight of layer l + 1 that reads neuron c is set to 0 -- [out][tap][c] for a convolution, columns
+ *     p * c_pad + c for every position p of the first Dense behind the torso, column c of a Dense behind a Dense and of the last
+ *     Dense (every head, action, bin or quantile) -- in every row, the padded ones too.  The outgoing zeros are written after
+ *     the incoming copies: a weight from a dormant neuron into a dormant neuron ends up 0;
+ *   - adam_m / adam_v (both NULL or both given) are set to 0 at every position written above.  The Adam step count is not an
+ *     argument and is not touched.
+ * Everything else -- other parameters, moments, padding lanes -- keeps its bits.  The call ends by rebuilding the weight mirror
+ * from `params`: the mirror is current when it returns.  Without layer_norm and with tau = 0 the network's function on the
+ * scored rows is unchanged (a dormant neuron's activations were exactly 0 and nothing reads it afterwards); with layer_norm
+ * the recycled neuron changes the statistics of its layer's other channels.
+ * ISDQN_ERR_UNSUPPORTED: arch impala (the residual adds make "outgoing" ambiguous), batch_norm (per-position statistics sit
+ * between the layers).  ISDQN_ERR_ARG: a NULL params / fresh_params / scores_out / mask_out / n_recycled_out / workspace,
+ * exactly one of adam_m / adam_v NULL, tau negative or not finite.  ISDQN_ERR_SHAPE: n_rows out of range. */
+int isdqn_net_redo_layout(const isdqn_net_config* cfg, int32_t* n_layers, int32_t* n_neurons, int32_t max_layers);
+int isdqn_net_redo(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, const float* fresh_params,
+                   const uint8_t* frames, int64_t frame_stride, const int32_t* frame_ids, const float* obs, int32_t n_rows,
+                   float tau, float* scores_out, int32_t* mask_out, int32_t* n_recycled_out, void* workspace, void* stream);
+
 /* Engine self-test: C[M][N] = A . B on the MFMA tile engine for every operand-layout
  * combination (a_tr/b_tr: 0 = operand stored [rows][K], 1 = stored [K][rows]).  Test hook. */
 int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int32_t a_tr,

@@ -18,6 +18,7 @@
 #include "hl_gauss.h"
 #include "quantile.h"
 #include "categorical.h"
+#include "redo.h"
 #include "net_plan.h"
 #include "net_problems.h"
 
@@ -2905,6 +2906,86 @@ extern "C" int isdqn_net_analysis(const isdqn_net_config* cfg, const float* para
         }
     }
     return ISDQN_OK;
+}
+
+// ReDo (Sokar et al. 2023; csrc/redo.h): the recyclable layers are the hidden ones, in network order.
+static int redo_supported(const isdqn_net_config* cfg, const Plan& P) {
+    ISDQN_REQUIRE(cfg->arch != ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED,
+                  "ReDo is not built for the impala torso: its residual adds make a neuron's outgoing weights ambiguous");
+    ISDQN_REQUIRE(!P.bn, ISDQN_ERR_UNSUPPORTED, "ReDo is not built for BatchNorm networks: per-position statistics sit between the layers");
+    ISDQN_REQUIRE(P.n_layers >= 2, ISDQN_ERR_SHAPE, "no hidden layer");
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_redo_layout(const isdqn_net_config* cfg, int32_t* n_layers, int32_t* n_neurons, int32_t max_layers) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    const Plan& P = *Pp;
+    if ((rc = redo_supported(cfg, P))) return rc;
+    ISDQN_REQUIRE(n_layers != nullptr, ISDQN_ERR_ARG, "null pointer");
+    for (int i = 0; i < P.n_layers - 1 && n_neurons != nullptr && i < max_layers; ++i) n_neurons[i] = P.L[i].out_f;
+    *n_layers = P.n_layers - 1;
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_redo(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, const float* fresh_params,
+                              const uint8_t* frames, int64_t frame_stride, const int32_t* frame_ids, const float* obs, int32_t n_rows,
+                              float tau, float* scores_out, int32_t* mask_out, int32_t* n_recycled_out, void* workspace, void* stream) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    const Plan& P = *Pp;
+    if ((rc = redo_supported(cfg, P))) return rc;
+    ISDQN_REQUIRE(params && fresh_params && scores_out && mask_out && n_recycled_out && workspace, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE((adam_m == nullptr) == (adam_v == nullptr), ISDQN_ERR_ARG, "adam_m and adam_v must be both null or both given");
+    ISDQN_REQUIRE(std::isfinite(tau) && tau >= 0.f, ISDQN_ERR_ARG, "tau must be finite and >= 0");
+    ISDQN_REQUIRE(n_rows >= 1 && n_rows <= P.N2, ISDQN_ERR_SHAPE, "n_rows must be in [1, 2 * batch_size] (workspace rows)");
+    rc = check_input(cfg, frames, frame_stride, frame_ids, obs);
+    if (rc) return rc;
+    NetInput in{frames, frame_stride, frame_ids, 0, obs, nullptr, 0};
+    float* ws = (float*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_hidden = P.n_layers - 1;
+    rc = refresh_mirror(P, params, ws, st);
+    if (rc) return rc;
+    rc = net_forward(P, cfg->precision == ISDQN_PRECISION_BF16X3, params, in, n_rows, 0, ws, ws + P.q_off, st, n_hidden);
+    if (rc) return rc;
+    // score: per-position sums over the rows into scratch (the data-gradient region: the forward does not touch it, and it holds a
+    // batch of the widest input any layer above the first reads, so one image of any hidden layer's output), then one workgroup
+    float* possum = ws + P.da_off;
+    int64_t off = 0;
+    for (int i = 0; i < n_hidden; ++i) {
+        const Layer& l = P.L[i];
+        const int npix = l.kind == 0 ? l.npix : 1;
+        ISDQN_REQUIRE((int64_t)npix * l.out_f <= P.da_floats && l.out_f <= REDO_MAX_WIDTH, ISDQN_ERR_UNSUPPORTED, "ReDo: hidden layer too wide");
+        hipLaunchKernelGGL(act_rowsum_kernel, dim3(ceil_div(l.out_elems_p, 256)), dim3(256), 0, st, (const float*)(ws + l.act_off), n_rows,
+                           l.out_elems_p, l.out_p, l.out_f, possum, (float*)nullptr, 0);
+        ISDQN_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(redo_score_kernel, dim3(1), dim3(256), 0, st, (const float*)possum, npix, l.out_f, (float)((int64_t)n_rows * npix), tau,
+                           scores_out + off, mask_out + off, n_recycled_out + i);
+        ISDQN_HIP_CHECK(hipGetLastError());
+        off += l.out_f;
+    }
+    // recycle: every incoming side first, then every outgoing side -- where a dormant neuron reads a dormant neuron the weight is 0
+    off = 0;
+    for (int i = 0; i < n_hidden; ++i) {
+        const Layer& l = P.L[i];
+        hipLaunchKernelGGL(redo_incoming_kernel, dim3(ceil_div(l.K, 1024), l.out_f), dim3(256), 0, st, params, adam_m, adam_v, fresh_params,
+                           (const int*)(mask_out + off), l.w_off, l.K, l.b_off, l.g_off, l.be_off);
+        ISDQN_HIP_CHECK(hipGetLastError());
+        off += l.out_f;
+    }
+    off = 0;
+    for (int i = 0; i < n_hidden; ++i) {
+        const Layer& l = P.L[i];
+        const Layer& nx = P.L[i + 1];
+        hipLaunchKernelGGL(redo_outgoing_kernel, dim3(ceil_div(nx.K / 8, 256), nx.out_p), dim3(256), 0, st, params, adam_m, adam_v,
+                           (const int*)(mask_out + off), l.out_f, l.out_p, nx.w_off, nx.K);
+        ISDQN_HIP_CHECK(hipGetLastError());
+        off += l.out_f;
+    }
+    return refresh_mirror(P, params, ws, st);
 }
 
 extern "C" int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K,

@@ -46,6 +46,13 @@ def train(key, p: dict, agent, env, rb):
     run_return, run_length = ([0.0] * len(env), [0] * len(env)) if vector else (None, None)
 
     analysis_logs = {"srank": [], "dead_neurons": []}
+    # ReDo (-redo, not in the reference): at every redo_frequency-th step, a target update, the dormant neurons are recycled on the
+    # device; the per-layer counts are logged and kept beside the analysis metrics (alone in the file without -a)
+    redo_frequency = p.get("redo_frequency", 0)
+    if redo_frequency:
+        if not p.get("analysis"):
+            analysis_logs = {}
+        analysis_logs["recycled_neurons"] = []
 
     def after_target_update(step, logs):
         if p.get("analysis"):  # dqn.py:54-58 of the reference
@@ -53,8 +60,12 @@ def train(key, p: dict, agent, env, rb):
 
             at_update = eval_srank_and_dead_neurons(agent.params, rb, p)
             logs.update(at_update)
-            for metric in analysis_logs:
+            for metric in ("srank", "dead_neurons"):
                 analysis_logs[metric].append(at_update[metric])
+        if redo_frequency and step % redo_frequency == 0:
+            recycled = agent.recycle_dormant(rb, p["redo_tau"])
+            logs["recycled_neurons"] = recycled
+            analysis_logs["recycled_neurons"].append(recycled)
         p["wandb"].log({"n_training_steps": step, **logs})
 
     def after_step():

@@ -58,6 +58,8 @@ _ENGINE = [
     ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
     ("-mqa", "--munchausen_alpha", dict(type=float, default=0.9, help="Scale alpha in [0, 1] of the log-policy bonus (0: soft-DQN targets). Means nothing without -mq.")),
     ("-mqc", "--munchausen_clip", dict(type=float, default=-1.0, help="Lower clip l0 <= 0 of tau * ln pi(a|s). Means nothing without -mq.")),
+    ("-redo", "--redo_frequency", dict(type=int, default=0, help="ReDo (Sokar et al. 2023): training steps between two recycles of the dormant neurons of the hidden layers (incoming weights re-initialised, outgoing weights and Adam moments zeroed, on the device); 0 = off. A positive multiple of -tuf. Not with -bn or -at impala.")),
+    ("-redot", "--redo_tau", dict(type=float, default=0.1, help="ReDo threshold tau: a neuron is dormant when its mean activation is at most tau times its layer's mean. Means nothing without -redo.")),
     ("-nenvs", "--n_envs", dict(type=int, default=1, help="Host environments stepped in lockstep with one batched best_actions forward (1 = the reference's loop).")),
     ("-nworkers", "--n_env_workers", dict(type=int, default=0, help="Host worker processes stepping the -nenvs environments in parallel (0 = in this process).")),
     ("-env", "--env_backend", dict(type=str, default="ale", choices=["ale", "synthetic"], help="'synthetic' replaces ALE by random frames (no ROMs needed).")),
@@ -158,6 +160,25 @@ def check_categorical(p: dict) -> None:
 
         check(True, p["n_bins"] if p.get("histogram_loss") else 0, p["n_quantiles"] if p.get("quantile_regression") else 0,
               p["munchausen_tau"] if p.get("munchausen") else 0.0)
+
+
+# (-redo and -redot stay out of parameters.json like -hl and -qr)
+REDO_FREQUENCY_REFUSED = "-redo / --redo_frequency must be a positive multiple of -tuf / --target_update_frequency (recycling happens at target updates)"
+
+
+def check_redo(p: dict) -> None:
+    """-redo that is no positive multiple of -tuf, a tau that is negative or not finite, or -redo together with -bn or -at impala
+    (the agents' own message) fails before anything is written."""
+    if p.get("redo_frequency", 0) != 0:
+        import math
+
+        from slimdqn._engine import check_redo as check
+
+        if p["redo_frequency"] < 0 or p["redo_frequency"] % p["target_update_frequency"] != 0:
+            raise ValueError(REDO_FREQUENCY_REFUSED)
+        if not (math.isfinite(p["redo_tau"]) and p["redo_tau"] >= 0.0):
+            raise ValueError("-redot / --redo_tau must be finite and >= 0")
+        check(p["architecture_type"], bool(p.get("batch_norm", False)))
 
 
 def check_engine_arguments(p: dict) -> None:

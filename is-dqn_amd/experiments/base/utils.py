@@ -38,6 +38,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     parser_argument.check_munchausen(p)
     parser_argument.check_quantiles(p)
     parser_argument.check_categorical(p)
+    parser_argument.check_redo(p)
     p["env_name"] = env_name
     if env_name == "atari":
         p["game_name"] = p["experiment_name"].split("_")[-1]
@@ -107,6 +108,6 @@ def save_data(p: dict, episode_returns: list, episode_lengths: list, model, anal
     )
     if model is not None:
         pickle.dump(model, open(os.path.join(model_dir, str(p["seed"])), "wb"))
-    if p.get("analysis"):  # utils.py:137-144 of the reference: analysis/<seed>.json
+    if p.get("analysis") or p.get("redo_frequency"):  # utils.py:137-144 of the reference: analysis/<seed>.json (-redo: its recycle counts)
         os.makedirs(os.path.join(p["save_path"], "analysis"), exist_ok=True)
         json.dump(analysis_logs, open(os.path.join(p["save_path"], "analysis", f"{p['seed']}.json"), "w"), indent=4)

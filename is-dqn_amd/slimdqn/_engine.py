@@ -64,6 +64,18 @@ def check_categorical(categorical, n_bins=0, n_quantiles=0, munchausen_tau=0.0) 
             raise ValueError(CATEGORICAL_MUNCHAUSEN_REFUSED)
 
 
+REDO_IMPALA_REFUSED = "ReDo is not built for architecture_type 'impala': the residual adds make a neuron's outgoing weights ambiguous (ISDQN_ERR_UNSUPPORTED)"
+REDO_BATCH_NORM_REFUSED = "ReDo is not built for batch_norm: per-position statistics sit between the layers (ISDQN_ERR_UNSUPPORTED)"
+
+
+def check_redo(architecture_type, batch_norm=False) -> None:
+    """The networks whose dormant neurons the library refuses to recycle, said before anything is allocated or written."""
+    if architecture_type == "impala":
+        raise ValueError(REDO_IMPALA_REFUSED)
+    if batch_norm:
+        raise ValueError(REDO_BATCH_NORM_REFUSED)
+
+
 class QNetEngine:
     """One Q-network (slimdqn/networks/architectures/dqn.py DQNNet + isdqn.py head view) on one GPU."""
 
@@ -294,6 +306,16 @@ class QNetEngine:
     def init_params(self, seed: int) -> None:
         """Flax defaults (dqn.py:49, 90): xavier_uniform for cnn, lecun_normal for fc; biases 0, LN scale 1.
         Draws come from numpy PCG64 (JAX threefry streams are not reproducible offline)."""
+        self.import_flax(self._init_tree(seed))
+
+    def fresh_params(self, seed) -> torch.Tensor:
+        """A new device tensor in the internal layout holding what ``init_params(seed)`` would leave in ``params`` (the engine's own
+        buffers are not touched): the source of re-initialised weights for ``redo``."""
+        t = torch.empty_like(self.params)
+        self.import_flax(self._init_tree(seed), target=t)
+        return t
+
+    def _init_tree(self, seed) -> Dict[str, Dict[str, np.ndarray]]:
         rng = np.random.default_rng(seed)
         params: Dict[str, Dict[str, np.ndarray]] = {}
         for info in self.infos:
@@ -326,7 +348,7 @@ class QNetEngine:
                 continue
             else:
                 params.setdefault(mod, {})[leaf] = np.zeros(shape, np.float32)
-        self.import_flax(params)
+        return params
 
     # ------------------------------------------------------------------ workspace regions (tests / debugging)
     def region(self, name: str) -> torch.Tensor:
@@ -494,6 +516,37 @@ class QNetEngine:
         )
         self._mirror_holds(params)
         return feats, list(torch.split(scores, sizes))
+
+    def redo_layout(self) -> list:
+        """Widths of the recyclable layers (include/isdqn_hip.h, isdqn_net_redo_layout): the hidden layers in network order, a conv
+        layer counted in output channels."""
+        n = ctypes.c_int32()
+        widths = (ctypes.c_int32 * 32)()
+        _hip.check(self.lib.isdqn_net_redo_layout(ctypes.byref(self.cfg), ctypes.byref(n), widths, 32), "isdqn_net_redo_layout")
+        return [int(widths[i]) for i in range(n.value)]
+
+    def redo(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, n_rows: int, tau: float, fresh: torch.Tensor):
+        """ReDo (Sokar et al. 2023; include/isdqn_hip.h, isdqn_net_redo) on the engine's own params / adam_m / adam_v: score the hidden
+        neurons on n_rows observations, recycle the dormant ones from ``fresh`` (internal layout: ``fresh_params``).  Returns device
+        tensors, split per layer like ``analysis``: (scores, mask (int32 0 / 1), n_recycled int32 [n_layers]); nothing is read back."""
+        assert fresh.dtype == torch.float32 and fresh.numel() == self.n_param_floats and fresh.is_contiguous() and fresh.device == self.params.device
+        widths = self.redo_layout()
+        scores = torch.empty(sum(widths), dtype=torch.float32, device=self.device)
+        mask = torch.empty(sum(widths), dtype=torch.int32, device=self.device)
+        n_recycled = torch.empty(len(widths), dtype=torch.int32, device=self.device)
+        _hip.check(
+            self.lib.isdqn_net_redo(
+                ctypes.byref(self.cfg), _hip.ptr(self.params), _hip.ptr(self.adam_m), _hip.ptr(self.adam_v), _hip.ptr(fresh),
+                _hip.ptr(frames), int(frame_stride), _hip.ptr(frame_ids), _hip.ptr(obs), int(n_rows), float(tau),
+                _hip.ptr(scores), _hip.ptr(mask), _hip.ptr(n_recycled), _hip.ptr(self.workspace), _hip.stream_ptr(self.device),
+            ),
+            "isdqn_net_redo",
+        )
+        # The library wrote `params` through the raw pointer, which does not move torch's version counter -- and it rebuilt the
+        # mirror from the recycled parameters as its last launch.  So "mirror == params at this version" is exactly what holds now,
+        # and _mirror_is_current stays right under trust_mirror = True: a later torch write moves the counter and is seen as before.
+        self._mirror_holds(None)
+        return list(torch.split(scores, widths)), list(torch.split(mask, widths)), n_recycled
 
     # ------------------------------------------------------------------ weight-mirror bookkeeping
     # The library keeps a pre-split mirror of the weights in the workspace and rebuilds it at the head of every call unless

@@ -173,6 +173,12 @@ _SIGNATURES = {
         c_int32,
         [POINTER(NetConfig), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "isdqn_net_redo_layout": (c_int32, [POINTER(NetConfig), POINTER(c_int32), POINTER(c_int32), c_int32]),
+    "isdqn_net_redo": (
+        c_int32,
+        [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_float,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "isdqn_selftest_gemm": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
-from slimdqn._engine import QNetEngine, check_categorical, check_munchausen, check_quantiles
+from slimdqn._engine import QNetEngine, check_categorical, check_munchausen, check_quantiles, check_redo
 
 
 class DeviceParams:
@@ -67,6 +67,13 @@ def importance_beta(beta_start: float, beta_end, n_steps: int, step: int) -> np.
         return np.float32(beta_end)
     b0, b1 = np.float64(beta_start), np.float64(beta_end)
     return np.float32(b0 + (b1 - b0) * (np.float64(max(step, 0)) / np.float64(n_steps)))
+
+
+def recycle_seed(seed: int, k: int) -> int:
+    """Seed of the fresh parameters of the agent's k-th recycle (0-based): a child of the agent's seed in numpy's SeedSequence tree,
+    never the seed itself (``init_params(seed)`` draws from SeedSequence(seed) with an empty spawn key)."""
+    state = np.random.SeedSequence(entropy=int(seed), spawn_key=(1, int(k))).generate_state(4)
+    return int.from_bytes(state.tobytes(), "little")
 
 
 class EngineAgent:
@@ -428,6 +435,31 @@ class EngineAgent:
             return v["host_out"][:m].numpy().astype(np.int64)
 
         return result() if wait else result
+
+    # ------------------------------------------------------------------ ReDo
+    _recycles = 0  # recycles done so far: selects the seed of the next fresh parameters
+
+    def recycle_dormant(self, replay_buffer, tau: float) -> list:
+        """ReDo (Sokar et al. 2023; include/isdqn_hip.h, isdqn_net_redo): score the hidden neurons on the states of 2 * batch_size
+        sampled transitions and recycle the dormant ones (score <= tau * layer mean) on the device, Adam moments included.  The
+        online parameters only: a DQN's target parameters keep their bits.  Pointers do not move and the weight mirror is left
+        current, so a captured update stays valid.  Returns the recycled neurons per hidden layer -- the only host read."""
+        check_redo(self.architecture_type, self.batch_norm)
+        eng = self._engine
+        n = 2 * eng.batch_size
+        samples = replay_buffer.sample(size=n)
+        if self.architecture_type == "fc":
+            inputs = dict(obs=torch.as_tensor(samples.state).to(eng.device).to(torch.float32).reshape(n, -1).contiguous())
+        elif hasattr(samples, "frame_ids"):
+            stack = samples.frame_ids.shape[1] // 2
+            ids = samples.frame_ids[:, :stack].contiguous()  # the states of the sampled transitions
+            inputs = dict(frames=samples.frames, frame_stride=samples.frame_stride, frame_ids=ids)
+        else:
+            inputs = self._states_to_device(np.asarray(samples.state))
+        fresh = eng.fresh_params(recycle_seed(self._seed, self._recycles))
+        self._recycles += 1
+        _, _, n_recycled = eng.redo(n_rows=n, tau=float(tau), fresh=fresh, **inputs)
+        return [int(c) for c in n_recycled.cpu().numpy()]
 
     # generic forms (one head, per-step replays); iSDQN overrides both
     def best_actions_planes(self, params, planes, rows, key=None, wait: bool = True):
