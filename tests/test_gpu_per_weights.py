@@ -140,6 +140,50 @@ def test_zero_leaf_gets_weight_one_and_stays_out_of_the_minimum():
     assert rc == 0 and w.tolist() == [1.0] * 4 and int(status.item()) & _hip.STATUS_EMPTY_TREE
 
 
+def _minimum_tree(tie=False):
+    """64 leaves, every value a multiple of 2^-10 (all partial sums and midpoints are exact, so the absolute target
+    cum[j] - value[j] / 2 lands in leaf j on any descent): leaf 37 holds 2^-10, the others 0.5 to 4; ``tie``: leaf 5 holds 2^-10 too."""
+    from oracle.sum_tree import SumTree as Oracle
+    from slimdqn.sample_collection.sum_tree import SumTree
+
+    vals = np.random.default_rng(64).integers(512, 4097, 64) / 1024.0
+    vals[37] = 1.0 / 1024.0
+    if tie:
+        vals[5] = 1.0 / 1024.0
+    o, tree = Oracle(64), SumTree(64)
+    o.set(np.arange(64, dtype=np.int32), vals)
+    tree.set(np.arange(64, dtype=np.int32), vals)
+    return o, tree, vals, np.cumsum(vals) - vals / 2.0
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 1024, 1025, 4096])
+def test_batch_minimum_found_at_every_draw_position(n):
+    """The smallest leaf is drawn at exactly one position p of the batch -- the first or last lane of a wave, the last draw, a
+    thread's second entry (p >= 1024) -- or twice, or tied with another leaf: a reduction that loses that lane leaves weights
+    above 1 behind, which _check_weighted_query rejects."""
+    o, tree, vals, mid = _minimum_tree()
+    rng = np.random.default_rng(n)
+    others = np.delete(np.arange(64), 37)
+    for p in sorted({q for q in (0, 63, 64, n - 1) if q < n}):
+        leaves = rng.choice(others, n)
+        leaves[p] = 37
+        targets = mid[leaves]
+        np.testing.assert_array_equal(o.query(targets), leaves)
+        for beta in (0.5, 1.0):
+            _check_weighted_query(tree, _d(targets), beta, unit=False)
+        got = tree.query_device(_d(targets)).cpu().numpy()
+        assert got[p] == 37 and (got == 37).sum() == 1
+    if n >= 65:  # the minimum twice (two threads, or one thread's two entries at n = 1025); then tied between two leaves
+        leaves = rng.choice(others, n)
+        leaves[0] = leaves[n - 1] = 37
+        _check_weighted_query(tree, _d(mid[leaves]), 0.5, unit=False)
+        o2, tree2, vals2, mid2 = _minimum_tree(tie=True)
+        leaves = rng.choice(np.delete(np.arange(64), [5, 37]), n)
+        leaves[63], leaves[64] = 5, 37
+        np.testing.assert_array_equal(o2.query(mid2[leaves]), leaves)
+        _check_weighted_query(tree2, _d(mid2[leaves]), 0.5, unit=False)
+
+
 # ===================================================================================== engines and batches
 CONFIGS = {
     # name: (feats, n_heads, A, B, arch, ln, extra engine keywords, target parameters)

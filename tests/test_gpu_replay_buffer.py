@@ -4,6 +4,8 @@ classes, plus batch-for-batch equality with the oracle replay on the same seed."
 import numpy as np
 import pytest
 
+from tests.helpers import sum_tree_edges as edges
+
 pytestmark = pytest.mark.gpu
 
 OBS = (84, 84)
@@ -142,3 +144,22 @@ def test_power_of_two_capacity_survives_the_first_eviction():
         rb.add(_t(np.full(OBS, i, np.uint8), i, 0.0, False, False), priority=1.0 + i)
     keys = rb._sampling_distribution.sample(64)
     assert keys.min() >= 20 - 1 - 8 and keys.max() <= 18
+
+
+@pytest.mark.parametrize("capacity,seed,exponent", edges.SAMPLER_RUNS)
+def test_prioritized_sampler_state_machine_equals_oracle(capacity, seed, exponent):
+    """About 3000 seeded ops (tests/helpers/sum_tree_edges.py: sampler_script) on the device sampler and on the oracle with the
+    documented staging (SamplerMirror): node bits and max_recorded_priority after every op that flushes, dense indices (and keys)
+    after every batch of the four sampling entry points used in turn, the key table at the end, a clean status word."""
+    from slimdqn.sample_collection.samplers import PrioritizedSamplingDistribution
+
+    assert (PrioritizedSamplingDistribution.MAX_PENDING, PrioritizedSamplingDistribution.PREFETCH,
+            PrioritizedSamplingDistribution.MAX_PRIORITY) == (edges.MAX_PENDING, edges.PREFETCH, edges.MAX_PRIORITY)
+    dev = PrioritizedSamplingDistribution(seed, capacity, priority_exponent=exponent)
+    mirror = edges.SamplerMirror(seed, capacity, exponent)
+    assert dev._tree._nodes.shape == mirror.tree._nodes.shape
+    stats = edges.run_sampler_script(edges.sampler_script(capacity, seed), mirror, dev, exact_update_device=exponent == 1.0)
+    print(dict(stats))
+    assert stats["key_comparison_lost"] == 0 and stats["batches"] >= 400
+    assert stats["mid_block_size_change"] >= 1 and stats["block_used_up"] >= 1
+    assert capacity != 4096 or stats["auto_flush"] >= 1
