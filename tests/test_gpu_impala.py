@@ -1,7 +1,21 @@
 """GPU parity of the Impala torso (reference slimdqn/networks/architectures/dqn.py:7-36 `Stack`, :75-88) against
 the oracle restatement (oracle/network.py: _impala_stack): forward, Bellman targets, per-head losses within 1e-3, the first-step
 gradient of EVERY leaf (15 convolutions, 6 block LayerNorms, the LayerNorm behind the torso, the dense tail), Adam steps, acting and
-the parameter layout round trip with Flax's nested module names."""
+the parameter layout round trip with Flax's nested module names.
+
+test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands then takes the torso apart: every kernel of csrc/impala.h and
+every convolution between them against a float64 model of that one stage on the run's own input (tests/helpers/impala_stages.py,
+tests/helpers/bf16_model.py), in bf16x3 and in single-pass bf16, on a non-square observation, and on flat frames whose pool
+windows are ties.  The pool's tie rule -- the first maximum in row-major window order -- is pinned there (winners compared
+exactly) and on the CPU in tests/test_impala_stages_host.py.
+
+Mutations (arithmetic only, applied to a scratch copy, one run of the stage test each; none is committed) and what fails:
+  * imp_pool_fwd_kernel `vv[e] > best[e]` -> `>=` (last maximum): flat-frames only -- "imp/s0/argmax: 21778 winners differ from
+    the first maximum, first at [0, 0, 0, 0]: got 8 want 0"; the two random-frame cases pass in both precisions (no ties there).
+  * imp_pool_bwd_kernel `a.x == me` -> `a.x <= me`: all 5 runs, s0/dz0 (a pixel no window chose holds a gradient).
+  * pool_pad forced to 0 in the pool backward launch: all 5 runs, s2/dz0 (the one Stack of each case whose pool pads in front).
+  * s8_store_quad truncating hi: all 5 runs, imp/s0/a1_0 is not a nearest-even split.
+  * imp_add_kernel writing vb only: all 5 runs, s0/r1-r0 (every element outside the bound)."""
 import numpy as np
 import pytest
 import torch
@@ -188,3 +202,217 @@ def test_entry_point_with_the_impala_torso(tmp_path):
     assert json.load(open(out / "parameters.json"))["shared_parameters"]["architecture_type"] == "impala"
     model = pickle.load(open(out / "isdqn" / "models" / "1", "rb"))["params"]
     assert model["params"]["Stack_2"]["Conv_4"]["kernel"].shape == (3, 3, 8, 8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Stage by stage: every kernel of csrc/impala.h and every convolution between them against a float64 model of that ONE stage on
+# the HIP run's own input tensor of the stage (tests/helpers/impala_stages.py, tests/helpers/bf16_model.py).  Nothing is shared
+# between the two sides but the stage's input, so an error cannot accumulate and no decision (pool winner, ReLU mask) is pinned.
+STAGE_CASES = {
+    # 84x84: B * 42 * 42 = 7056 rows take the row-wise kernels' grid-stride loop (256 workgroups of 16 rows) twice; pool paddings 0, 0, 1
+    "tiny-ln-B4": dict(feats=(8, 16, 16, 24), obs=(84, 84, 4), K=2, A=5, B=4, ln=True, flat=False),
+    # widths that are no multiple of 8 (C_p 16, 24, 16), H != W in every Stack (22x18, 11x9, 6x5), a ragged last 16-row block, 3 frames
+    "nonsquare-44x36x3-noln-B2": dict(feats=(12, 20, 9, 16), obs=(44, 36, 3), K=3, A=4, B=2, ln=False, flat=False),
+    # flat backgrounds + rectangles, one all-zero state: most pool windows are ties of bit-equal values
+    "flat-frames-ln-B3": dict(feats=(8, 16, 16, 24), obs=(44, 44, 3), K=2, A=5, B=3, ln=True, flat=True),
+}
+STAGE_RUNS = [pytest.param(c, p, id=f"{c}-{p}") for c in ("tiny-ln-B4", "nonsquare-44x36x3-noln-B2") for p in ("bf16x3", "bf16")] + [
+    pytest.param("flat-frames-ln-B3", "bf16x3", id="flat-frames-ln-B3-bf16x3")]
+
+
+@pytest.mark.parametrize("case,precision", STAGE_RUNS)
+def test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands(case, precision):
+    """loss_on_batch, then grad_on_batch(batch, g); then every stored tensor of the torso against ONE stage recomputed in float64
+    from the run's own input of that stage.  `passes` = 3 (bf16x3) / 1 (bf16); bounds are bf16_model's c 2^-24 S with c the depth
+    of the fp32 chain (ROUNDING = 2 units per operation), derived, not fitted.
+
+    Forward, all 2B images, every Stack s:
+      xin (S8)            == split_words(frames_to_x) / split_words(r2 of Stack s-1)              bit-exact (hipcc's / 255.0f is the
+                                                                                                  IEEE quotient: no fallback needed)
+      z0                  ~  conv(passes, xin planes, split(W)) + bias                            bound(S + |b|, chain_depth(9 cin_p))
+      r0, argmax          == pool_fwd(z0): values bit-exact, winners exact (first maximum)        true channels
+      a1_b (S8)           ~  ln_relu_fwd(r_b, gamma, beta, E_z = 0)                               its bound
+      a2_b (S8)           ~  relu(conv(a1_b planes) + bias)                                       conv bound + S8_STORE a
+      r_{b+1} - r_b       ~  conv(a2_b planes) + bias                                             conv bound + one rounding of the add;
+                                                                                                  b = 1: r2 == float32(zt + r1) bit-exact
+      act/Impala, z/Impala: ln_relu_fwd(r2 of Stack 2) within its bound; the copy of r2 (first B images) bit-exact
+      channels C .. C_p - 1 of every tensor: exactly 0; every S8 tensor: a nearest-even split (s8_malformed empty).
+    Backward, B images (what impala_backward leaves in place: g_pool(s) = imp/s2/dr for s = 2, the head of imp/s{s+1}/da for
+    s < 2 -- the next Stack's data gradient, updated in place by the two blocks' LayerNorm backward; dz0 and dzs are written
+    once per pass, dzs last by the conversion of dz0.  No row had to be dropped):
+      dz0                 ~  pool_bwd(g_pool, own argmax)                bound(S, ROUNDING 4); pixels no window chose: exactly 0
+      dzs (S8)            == split_words(dz0)                            bit-exact
+      Conv_0/bias of g    ~  column sums of dz0                          bound(sum |dz0|, ROUNDING (rows per lane + 16 + blocks))
+      Conv_0/kernel of g  ~  conv_wgrad(passes, xin planes, dzs planes)  bound(S, ROUNDING (MFMA_TREE + K steps + slabs + 2)), the
+                                                                         chain of impala_stages.wgrad_chain
+    Negative control (the other pass count at least 4x further away in the 2-norm) on z0, a2, the residual rows and the kernel
+    gradient; elementwise (it breaks the bound on half of the elements) on z0 and the residual rows -- not behind a ReLU (half of
+    a2 is 0 under either model) and not on weight gradients (test_gpu_bf16_model.py).
+    Case flat-frames: asserted first that at least a quarter of Stack 0's pool windows hold two or more values bit-equal to their
+    maximum in the HIP z0; then also the pinned-decision leaf comparison (_masked_impala_grads, 2e-4 per leaf).
+
+    Measured on the MI355X, max over the 5 runs (max |d| / bound; max |d| / 2^-24 S against c where S is the whole bound):
+      z0 0.134; 3.47 against c = 22 .. 26        residual rows 0.177; 4.91 against c = 22 .. 26
+      a1 0.69 with LayerNorm, 0.997 without (relu is exact: the S8 storage's worst case 2^-17 |a| is all that is left)
+      a2 0.70 (S8 storage dominates)             act/Impala 0.56 with LayerNorm, 0.996 without
+      dz0 0.254; 2.04 against c = 8              Conv_0/bias 0.026; 1.55 against c = 60 .. 558
+      Conv_0/kernel 0.069; 2.06 against c = 30 .. 280 (1 .. 7 K steps, 7 .. 126 slabs)
+    Other pass count outside the bound, smallest share: z0 83 % (flat frames; 99 % on random ones), residual rows 100 %, kernel
+    gradients 75 % (2-norm asserted only), a2 36 % .. 57 % (behind the ReLU: not asserted).  Flat frames: 93.7 % of Stack 0's pool
+    windows are ties."""
+    from tests.helpers import bf16_model as M
+    from tests.helpers import impala_stages as IS
+
+    cfg = STAGE_CASES[case]
+    feats, obs, K, A, B, ln = cfg["feats"], cfg["obs"], cfg["K"], cfg["A"], cfg["B"], cfg["ln"]
+    passes, other = (3, 1) if precision == "bf16x3" else (1, 3)
+    elementwise = True
+    N2, stack = 2 * B, obs[2]
+    _, eng, params = make_pair(feats, K, A, B, arch="impala", obs=obs, layer_norm=ln, seed=3, lr=1e-3, precision=precision)
+    make = IS.flat_frame_batch if cfg["flat"] else make_frame_batch
+    frames, ids, action, reward, terminal, ref = make(B, A, seed=11 if cfg["flat"] else 7, h=obs[0], w=obs[1], stack=stack)
+    batch = device_batch(eng, frames, ids, action, reward, terminal)
+    eng.loss_on_batch(batch)
+    g = torch.zeros_like(eng.params)
+    eng.grad_on_batch(batch, g)
+    torch.cuda.synchronize()
+    hip_g = eng.internal_to_flax_grads(g)
+    geo = IS.geometry(obs, feats)
+    dev = eng.params.device
+    f32 = lambda name, n: eng.region(name)[:n]
+    vec = lambda mod, leaf: torch.from_numpy(np.asarray(params[mod][leaf], np.float64)).to(dev)
+    wsplit = lambda mod: M.split(torch.from_numpy(np.asarray(params[mod]["kernel"])).to(dev))
+    report, usage = [], {}
+
+    def note(row, used, ratio=None, frac=None):
+        u = usage.setdefault(row, [0.0, 0.0, 1.0])
+        u[0], u[1] = max(u[0], used), max(u[1], ratio or 0.0)
+        u[2] = min(u[2], frac) if frac is not None else u[2]
+
+    def s8(name, rows, pitch, c, shape):
+        """planes (hi, lo) of an S8 tensor, true channels, shaped; padded channels are 0 and every element is a nearest-even split"""
+        hi, lo = M.s8_planes(eng.region(name), rows, pitch)
+        assert int(M.s8_malformed(hi, lo).sum()) == 0, f"{name}: elements that are not a nearest-even split"
+        hi, lo = hi.reshape(*shape, pitch), lo.reshape(*shape, pitch)
+        assert float(hi[..., c:].abs().max() if c < pitch else 0.0) == 0.0 and float(lo[..., c:].abs().max() if c < pitch else 0.0) == 0.0, \
+            f"{name}: padded channels are not 0"
+        return hi[..., :c], lo[..., :c]
+
+    def conv_row(label, x, mod, got, relu, extra, control_elementwise):
+        """got [N][pix][C] against conv(x planes, split(W of mod)) + bias at `passes`, control at `other`"""
+        w, b = wsplit(mod), vec(mod, "bias")
+        cin_p = -(-x[0].shape[-1] // 8) * 8
+        c = M.chain_depth(9 * cin_p, 1, 2)
+        v, S = M.conv(passes, x, w, 1)
+        alt, _ = M.conv(other, x, w, 1)
+        want, alt, S = v + b, alt + b, S + b.abs()
+        if relu:
+            want, alt = want.clamp_min(0), alt.clamp_min(0)
+        bnd = M.bound(S, c) + extra(want)
+        used, ratio, frac = M.check(got, want.reshape(got.shape), bnd.reshape(got.shape), S.reshape(got.shape), alt.reshape(got.shape),
+                                    elementwise_control=control_elementwise, label=label)
+        report.append(f"{label}: c = {c}, max |d| / bound = {used:.3f}, max |d| / 2^-24 S = {ratio:.2f}, other passes outside: {frac:.0%}")
+        return used, ratio, frac
+
+    # ---------------------------------------------------------------- forward, all 2B images
+    r2_prev = None
+    for s, G in enumerate(geo):
+        H, W, Hp, Wp, pad, cin, cin_p, C, C_p = (G[k] for k in ("H", "W", "Hp", "Wp", "pad", "cin", "cin_p", "C", "C_p"))
+        big, small, pre = N2 * H * W, N2 * Hp * Wp, f"imp/s{s}/"
+        words = eng.region(pre + "xin")[: big * cin_p].view(torch.int32)
+        if s == 0:
+            x0 = IS.frames_to_x(torch.from_numpy(frames).to(dev), IS.paired_ids(ids, stack), H, W, stack)
+            assert torch.equal(words, M.split_words(x0)), "imp/s0/xin is not the S8 split of uint8 / 255"
+        else:
+            assert torch.equal(words, M.split_words(r2_prev)), f"{pre}xin is not the S8 split of the previous Stack's output"
+        xin = s8(pre + "xin", big, cin_p, cin, (N2, H, W))
+        z0 = f32(pre + "z0", big * C_p).reshape(N2, H, W, C_p)
+        assert float(z0[..., C:].abs().max() if C < C_p else 0.0) == 0.0
+        note("z0", *conv_row(f"s{s}/z0", xin, f"Stack_{s}/Conv_0", z0[..., :C].reshape(N2, H * W, C).double(), False,
+                             lambda a: 0.0, elementwise))
+        # the pool: values bit for bit, winners exactly
+        r = [f32(pre + f"r{k}", small * C_p).reshape(N2, Hp, Wp, C_p) for k in range(3)]
+        arg = eng.region(pre + "argmax").view(torch.uint8)[: small * C_p].reshape(N2, Hp, Wp, C_p)
+        val, first = IS.pool_fwd(z0, pad)
+        if cfg["flat"] and s == 0:
+            tied = float((IS.pool_ties(z0, pad)[..., :C] >= 2).double().mean())
+            report.append(f"s0: pool windows with two or more values equal to the maximum: {tied:.1%}")
+            assert tied >= 0.25, f"only {tied:.1%} of Stack 0's pool windows are ties: the case no longer tests the tie rule"
+        assert torch.equal(r[0][..., :C].contiguous().view(torch.int32), val[..., :C].contiguous().view(torch.int32)), f"{pre}r0: pool values"
+        bad = (arg[..., :C].long() != first[..., :C]).nonzero()
+        assert bad.numel() == 0, f"{pre}argmax: {bad.shape[0]} winners differ from the first maximum, first at {bad[0].tolist()}: " \
+                                 f"got {int(arg[tuple(bad[0])])} want {int(first[tuple(bad[0])])}"
+        for k in range(3):
+            assert float(r[k][..., C:].abs().max() if C < C_p else 0.0) == 0.0, f"{pre}r{k}: padded channels"
+        for b in range(2):
+            gamma, beta = (vec(f"Stack_{s}/LayerNorm_{b}", k) if ln else None for k in ("scale", "bias"))
+            rb = r[b][..., :C].double()
+            a, E = M.ln_relu_fwd(rb, gamma, beta, torch.zeros_like(rb), has_ln=ln)
+            a1 = s8(pre + f"a1_{b}", small, C_p, C, (N2, Hp, Wp))
+            used, _, _ = M.check(a1[0] + a1[1], a, E, label=f"s{s}/a1_{b}")
+            note("a1", used)
+            a2 = s8(pre + f"a2_{b}", small, C_p, C, (N2, Hp, Wp))
+            note("a2", *conv_row(f"s{s}/a2_{b}", a1, f"Stack_{s}/Conv_{1 + 2 * b}", (a2[0] + a2[1]).reshape(N2, Hp * Wp, C), True,
+                                 lambda a_: M.S8_STORE * a_ + M.FLOOR, False))
+            diff = (r[b + 1][..., :C].double() - rb).reshape(N2, Hp * Wp, C)
+            one_add = (M.ROUNDING * M.U * r[b + 1][..., :C].double().abs()).reshape(N2, Hp * Wp, C)
+            note("residual", *conv_row(f"s{s}/r{b + 1}-r{b}", a2, f"Stack_{s}/Conv_{2 + 2 * b}", diff, False, lambda a_: one_add, elementwise))
+        zt = f32(pre + "zt", small * C_p).reshape(N2, Hp, Wp, C_p)  # still block 1's second convolution
+        assert torch.equal(r[2], IS.residual_add(zt, r[1])), f"{pre}r2 is not float32(zt + r1)"
+        r2_prev = r[2]
+    T = geo[2]
+    rows, C, C_p = N2 * T["Hp"] * T["Wp"], T["C"], T["C_p"]
+    gamma, beta = (vec("LayerNorm_0", k) if ln else None for k in ("scale", "bias"))
+    rT = r2_prev[..., :C].double()
+    a, E = M.ln_relu_fwd(rT, gamma, beta, torch.zeros_like(rT), has_ln=ln)
+    act = s8("act/Impala", rows, C_p, C, (N2, T["Hp"], T["Wp"]))
+    used, _, _ = M.check(act[0] + act[1], a, E, label="act/Impala")
+    note("act/Impala", used)
+    assert torch.equal(f32("z/Impala", B * T["Hp"] * T["Wp"] * C_p), r2_prev[:B].reshape(-1)), "z/Impala is not a copy of the online r2"
+
+    # ---------------------------------------------------------------- backward, B images
+    for s, G in enumerate(geo):
+        H, W, Hp, Wp, pad, cin, cin_p, C, C_p = (G[k] for k in ("H", "W", "Hp", "Wp", "pad", "cin", "cin_p", "C", "C_p"))
+        pre, rows = f"imp/s{s}/", B * H * W
+        g_pool = f32("imp/s2/dr" if s == 2 else f"imp/s{s + 1}/da", B * Hp * Wp * C_p).reshape(B, Hp, Wp, C_p)
+        assert float(g_pool.abs().max()) > 0
+        arg = eng.region(pre + "argmax").view(torch.uint8)[: B * Hp * Wp * C_p].reshape(B, Hp, Wp, C_p)
+        dz0 = f32(pre + "dz0", rows * C_p).reshape(B, H, W, C_p)
+        want, S, chosen = IS.pool_bwd(g_pool.double(), arg, H, W, pad)
+        used, ratio, _ = M.check(dz0.double(), want, M.bound(S, M.ROUNDING * 4), S, label=f"s{s}/dz0")
+        note("dz0", used, ratio)
+        assert float(dz0[chosen == 0].abs().max()) == 0.0, f"{pre}dz0: a pixel no window chose is not 0"
+        assert float(dz0[..., C:].abs().max() if C < C_p else 0.0) == 0.0
+        assert torch.equal(eng.region(pre + "dzs")[: rows * C_p].view(torch.int32), M.split_words(dz0)), f"{pre}dzs is not the S8 split of dz0"
+        # bias gradient: per lane a chain over its rows, the 16 row groups of a workgroup, then the workgroups' partials
+        _, _, cs, ca = IS.to_s8_masked(dz0.reshape(rows, C_p))
+        blocks, per_lane = IS.row_blocks(rows)
+        gb = torch.from_numpy(np.asarray(hip_g[f"Stack_{s}/Conv_0"]["bias"], np.float64)).to(dev)
+        used, ratio, _ = M.check(gb, cs[:C], M.bound(ca[:C], M.ROUNDING * (per_lane + 16 + blocks)), ca[:C], label=f"s{s}/Conv_0/bias")
+        note("Conv_0/bias", used, ratio)
+        # kernel gradient
+        xin = tuple(p[:B] for p in s8(pre + "xin", N2 * H * W, cin_p, cin, (N2, H, W)))
+        dzs = s8(pre + "dzs", rows, C_p, C, (B, H * W))
+        steps, slabs = IS.wgrad_chain(B, H * W, 9 * cin_p)
+        c = M.ROUNDING * (M.MFMA_TREE + steps + slabs + 2)
+        want, S = M.conv_wgrad(passes, xin, dzs, 3, 1)
+        alt, _ = M.conv_wgrad(other, xin, dzs, 3, 1)
+        gk = torch.from_numpy(np.asarray(hip_g[f"Stack_{s}/Conv_0"]["kernel"], np.float64)).to(dev)
+        used, ratio, frac = M.check(gk, want, M.bound(S, c), S, alt, elementwise_control=False, label=f"s{s}/Conv_0/kernel")
+        report.append(f"s{s}/Conv_0/kernel: c = {c} ({steps} K steps, {slabs} slabs), max |d| / bound = {used:.3f}, "
+                      f"max |d| / 2^-24 S = {ratio:.2f}, other passes outside: {frac:.0%}")
+        note("Conv_0/kernel", used, ratio, frac)
+    print()
+    for line in report:
+        print("  " + line)
+    for row, (used, ratio, frac) in usage.items():
+        print(f"  USAGE {case}-{precision} {row}: max |d| / bound = {used:.3f}, max |d| / 2^-24 S = {ratio:.2f}, other passes outside >= {frac:.0%}")
+
+    if cfg["flat"]:  # the pinned-decision comparison of every leaf, on frames where most decisions are ties
+        m_grads = _masked_impala_grads(eng, params, feats, K, A, B, ln, ref, eng.targets.cpu().numpy())
+        for mod in m_grads:
+            for leaf in m_grads[mod]:
+                a_, b_ = np.asarray(hip_g[mod][leaf], np.float64), m_grads[mod][leaf]
+                assert np.linalg.norm(b_) > 0, (mod, leaf)
+                e = np.linalg.norm(a_ - b_) / np.linalg.norm(b_)
+                assert e <= 2e-4, (mod, leaf, e)
