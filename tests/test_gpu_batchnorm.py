@@ -4,7 +4,9 @@ numerics -- the reference holds no numbers and flax is not installed), through t
 
 What is compared: the acting forward on the running averages; q-values / targets / per-head losses of the training-mode pass on
 concat(state, next_state) within 1e-3; every leaf's first-step gradient (BatchNorm scale / bias included: they carry the part of the
-gradient that reaches the next-state rows); the running averages a learn step leaves; parameters after Adam; three chained steps."""
+gradient that reaches the next-state rows); the running averages a learn step leaves; parameters after Adam; three chained steps.
+Below them, stage by stage on the run's own operands (bf16x3 and bf16):
+test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands."""
 import numpy as np
 import pytest
 import torch
@@ -308,3 +310,406 @@ def test_entry_points_with_the_batch_norm_flag(tmp_path, algo, arch):
         assert stats["Stack_2"]["BatchNorm_1"]["var"].shape == (11, 11) and model["params"]["Stack_0"]["BatchNorm_0"]["scale"].shape == (42, 42)
     else:
         assert model["params"]["BatchNorm_3"]["scale"].shape == (11 * 11 * 8,) and stats["BatchNorm_4"]["var"].shape == (16,)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Stage by stage: every kernel of csrc/batchnorm.h and every contraction between them against a float64 model of that ONE stage on
+# the HIP run's own input tensor of the stage (tests/helpers/batchnorm_stages.py, tests/helpers/bf16_model.py).
+def _bn_stage_runs():
+    from tests.helpers.batchnorm_stages import CASES
+
+    both = ("cnn-84x84x4-B40", "fc-d6-B37")
+    return [pytest.param(c, p, id=f"{c}-{p}") for c in CASES for p in (("bf16x3", "bf16") if c in both else
+                                                                         ("bf16",) if c == "cnn-headline-B8" else ("bf16x3",))]
+
+
+@pytest.mark.parametrize("case,precision", _bn_stage_runs())
+def test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands(case, precision):
+    """loss_on_batch, learn_on_batch(grad_out=g), then forward on the running averages; every stored tensor against ONE stage
+    recomputed in float64 from the run's own input of that stage.  `passes` = 3 (bf16x3) / 1 (bf16).  Bounds are derived
+    (batchnorm_stages.py: ROUNDING * depth * 2^-24 * magnitudes, depth from the kernel's own summation order; bf16_model.py:
+    c 2^-24 S), not fitted.  Every row and element of every tensor named here is asserted.
+
+    Cases (batchnorm_stages.CASES): cnn-84x84x4-B40 -- N = 80, the spatial lane loop's second iteration, partly filled;
+    cnn-52x60x2-B33-noln -- N = 66, C < Cp at the input site (2 frames of 8 channels), a spatial site (20 / 24) and the flatten site (12 / 16), non-square P;
+    cnn-headline-B8 in bf16 -- the 64-channel routes and a 512-wide feature site; fc-d6-B37 -- N = 74 (nine full row slices and a
+    partial one), width 304 (two workgroups, the second partly on), one head regressed on its own target (TF-DQN: built directly,
+    make_pair always adds a target head).
+
+    Forward, all 2B rows, in network order:
+      bn/x0                == split_words(frames_to_x) (cnn) / concat(state, next_state) (fc)                    bit for bit
+      bn/<site>/mean, var  ~  bn_stats(own input, S8 hi + lo)                                                    d_mean, d_var
+      bn/<site>/out (S8)   ~  bn_apply(own input, own mean / var, parameters); padded channels 0; well-formed S8 words
+      z/<layer>            ~  conv / dense(passes, own bn/<site>/out planes, split(W)) + bias   bound(S + |b|, chain_depth);
+                              control: the other pass count 4x further away in the 2-norm and outside the bound on half of the
+                              elements.  Conv_0 here is the generic engine on an 8-channel S8 input (K = 512): its only test.
+      act/<layer> (S8)     ~  ln_relu_fwd(own z);   q ~ the head on the last site's out;   q_values == own q, targets ~ Bellman
+      after loss_on_batch the whole parameter buffer (running averages included) is unchanged bit for bit.
+    Backward, all 2B rows (dout rows [B, 2B) are filled with 1.0 before the step: the workspace is zero only once):
+      dout                 rows [B, 2B) exactly 0; rows [0, B): 2 td / B at (online head + k, a_b), every other column exactly 0
+      da (cnn, as left)    ~  conv_dgrad(own dz/Conv_0): the data gradient into the first convolution's input
+      bn/BatchNorm_0/dbias, dscale (cnn)  ~  s1, s2 of bn_backward(own bn/x0, own da)                            d_s1, d_s2
+      every other site: da recomputed from own dz/<layer above> (or dout) and split(W) at `passes` with its bound E_da;
+        dbias, dscale      ~  s1, s2 of bn_backward(own act, da), bounds with E_da carried in
+        dz/<layer> (S8)    ~  ln_relu_bwd(own z, own ReLU mask, dx), dx from da and the run's OWN s1 / s2, E_da carried through
+        fc: region da, as left, ~ dx of BatchNorm_0
+      BatchNorm scale / bias leaves of g == the dscale / dbias regions bit for bit (one slab)
+      kernel leaves ~ conv_wgrad / wgrad(passes, own operands) over the 2B rows, bias leaves ~ sum dz  (bf16 model's bounds)
+      running averages after the step ~ running(before, own batch mean / var) within 2 ulp
+    Acting: forward() of all 2B rows and of row 3 alone, on the updated parameters and their running averages.  On q only, against
+    the chain of the same stage functions with every bound carried through the next (bn_apply's E_x, exact_layer, ln_relu_fwd's
+    E_z): a worst case in every layer, so loose (reported as bound / max |q|).  And stage by stage on what forward() leaves in the
+    workspace: bn/x0, every bn/<site>/out from its own input and the running averages, every act/<layer> through the model of its
+    contraction (z is not stored by forward), q from the last site's out, with the pass-count control.
+
+    Not covered: the impala + BatchNorm sites ("Stack_s/BatchNorm_b" reuse these six kernels; the impala stage test in
+    tests/test_gpu_impala.py covers that torso's own kernels), the LayerNorm scale / bias leaves (as in test_gpu_bf16_model.py).
+
+    Measured on the MI355X, max over the 6 runs (max |d| / bound; against 2^-24 S where S is the whole bound, with c):
+      mean 0.139, var 0.118                      bn/<site>/out 0.971 (S8 storage's worst case 2^-17 |y| dominates)
+      z 0.105; 4.04 against c = 18 .. 150        act 0.71 with LayerNorm, 0.997 without (relu is exact: S8 storage is all that is left)
+      q 0.068; 1.23 against c = 18 .. 48         targets 0.32, dout 0.34
+      dbias 0.054, dscale 0.041                  dz 0.78 (noln: S8 storage), 0.43 with LayerNorm
+      da as left 0.101; 3.07 against c <= 148    kernel leaves 0.185; 3.33 against c = 18 .. 276, bias leaves 0.45
+      running mean / var 0.000 of 2 ulp (bit-equal to the fp32 expression on every element)
+      acting, own operands: out 0.970, act 0.52, q 0.070; 1.26 against c.  Acting, chain as a whole: 0.002 -- its composed bound
+      is 0.036 .. 0.84 of max |q| (bf16x3: fc, noln cnn), 372 x with LayerNorm (row variances over 8 channels) and 4.8 .. 8.5e5 x in
+      bf16: a worst case in every layer says nothing there, which is why the acting forward is also checked stage by stage.
+    Other pass count outside the bound, smallest share: z 82 % (headline Conv_2 in bf16), q 99 %.
+    Mutations (scratch copies of csrc/batchnorm.h, one library each; new runs failing / end-to-end tests of this file failing):
+      spatial divisor N * Cp               4 cnn runs (BatchNorm_0/mean, all 7056 elements) / cnn 4, impala 2, tfdqn
+      spatial lane loop stops after n < 64 B40 x 2, B33 (BatchNorm_0/mean, every element)   / none: no other test has N > 64
+      feature kernel sums 7 of 8 slices    all 6                                            / cnn 4, impala 2, fc 2, tfdqn
+      inv_m without the C factor           4 cnn runs (dz/Conv_1)                           / cnn 4, impala 2
+      bn_bwd_apply reads the running var   all 6 (dz/Dense_0, dz/Dense_1)                   / cnn 4, impala 2, fc 2
+      bn_running_kernel with momentum 0.9  all 6 (running mean)                             / all 9 oracle tests
+      bn_zero_kernel skipped               all 6 (next-state rows of dL/dq)                 / none: a fresh workspace is zero"""
+    from slimdqn._engine import QNetEngine
+    from tests.helpers import batchnorm_stages as BS
+    from tests.helpers import bf16_model as M
+    from tests.helpers import impala_stages as IS
+    from tests.test_gpu_bf16_model import _conv_wgrad_chain, _dense_wgrad_slabs, _fwd_splits
+
+    inp = BS.case_inputs(case)
+    cfg = inp["cfg"]
+    arch, obs, feats, K, A, B, ln, n_heads = (cfg[k] for k in ("arch", "obs", "feats", "K", "A", "B", "ln", "n_heads"))
+    passes, other = (3, 1) if precision == "bf16x3" else (1, 3)
+    N2, nha, oh = 2 * B, n_heads * A, 1 if n_heads >= 2 else 0
+    nha_p = -(-nha // 8) * 8
+    if n_heads == 1 + K:
+        _, eng, params = make_pair(feats, K, A, B, arch=arch, obs=obs, layer_norm=ln, seed=BS.PARAM_SEED, batch_norm=True, precision=precision)
+        for m in params:  # the host test holds THESE inputs to account (tests/test_batchnorm_stages_host.py)
+            for n in params[m]:
+                np.testing.assert_array_equal(params[m][n], inp["params"][m][n])
+    else:
+        eng = QNetEngine(obs, A, n_heads, list(feats), arch, ln, B, gamma_n=0.99, learning_rate=1e-3, adam_eps=1.5e-4, precision=precision,
+                         batch_norm=True)
+        eng.import_flax(inp["params"], batch_stats=inp["stats"])
+    got_stats = eng.export_batch_stats()
+    for m in inp["stats"]:
+        for n in inp["stats"][m]:
+            np.testing.assert_array_equal(got_stats[m][n], inp["stats"][m][n])
+    dev = eng.params.device
+    d_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if arch == "cnn":
+        h, w, stack = obs
+        frames, ids = inp["frames"], inp["ids"]
+        batch = device_batch(eng, frames, ids, inp["action"], inp["reward"], inp["terminal"])
+    else:
+        obs_all = np.concatenate([inp["state"], inp["next_state"]])
+        batch = eng.make_batch(state=d_(inp["state"]), next_state=d_(inp["next_state"]), action=d_(inp["action"]), reward=d_(inp["reward"]),
+                               terminal=d_(inp["terminal"]))
+    layers, sites = BS.layers(cfg), BS.site_layout(cfg)
+    site_of = {s["layer"]: s for s in sites}
+    offs = {i.name.decode(): int(i.offset) for i in eng.infos}
+
+    p_before = eng.params.clone()
+    eng.loss_on_batch(batch)
+    torch.cuda.synchronize()
+    assert torch.equal(eng.params.view(torch.int32), p_before.view(torch.int32)), "loss_on_batch changed the parameter buffer"
+    eng.region("dout")[B * nha_p : N2 * nha_p] = 1.0  # whatever an earlier step left there: bn_zero_kernel has to clear it
+    g = torch.zeros_like(eng.params)
+    eng.learn_on_batch(batch, grad_out=g)
+    torch.cuda.synchronize()
+    hip_g = eng.internal_to_flax_grads(g)
+    p0 = inp["params"]
+
+    usage, report = {}, []
+
+    def check(row, got, want, bnd, S=None, alt=None, elementwise=True, label=None):
+        used, ratio, frac = M.check(got, want, bnd, S, alt, elementwise_control=elementwise, label=label or row)
+        u = usage.setdefault(row, [0.0, 0.0, 1.0])
+        u[0], u[1] = max(u[0], used), max(u[1], ratio or 0.0)
+        u[2] = min(u[2], frac) if frac is not None else u[2]
+        report.append(f"{label or row}: max |d| / bound = {used:.3f}" + (f", max |d| / 2^-24 S = {ratio:.2f}" if ratio is not None else "")
+                      + (f", other passes outside: {frac:.0%}" if frac is not None else ""))
+
+    vec = lambda mod, leaf: torch.from_numpy(np.asarray(p0[mod][leaf], np.float64)).to(dev)
+    wsplit = lambda mod: M.split(torch.from_numpy(np.asarray(p0[mod]["kernel"])).to(dev))
+    group = lambda s, leaf, src: src[offs[f"{s['name']}/{leaf}"] : offs[f"{s['name']}/{leaf}"] + s["G"]]  # internal groups of a site tensor
+    reg = lambda s, name: eng.region(s["prefix"] + name)[: s["G"]]
+
+    def s8(name, rows, pitch):
+        hi, lo = M.s8_planes(eng.region(name), rows, pitch)
+        assert int(M.s8_malformed(hi, lo).sum()) == 0, f"{name}: elements that are not a nearest-even split"
+        return hi, lo
+
+    def site_planes(s, which):
+        """(hi, lo) [N2][P][Cp] of a site's S8 input ("src") or output ("out")"""
+        name = s["src"] if which == "src" else s["prefix"] + "out"
+        return tuple(t.reshape(N2, s["P"], s["Cp"]) for t in s8(name, N2, s["P"] * s["Cp"]))
+
+    def true_planes(s, planes):
+        """a site's planes as the next layer reads them: true channels, [N2][P * C]"""
+        return tuple(t[:, :, : s["C"]].reshape(N2, -1) for t in planes)
+
+    def site_forward(s):
+        x = sum(site_planes(s, "src"))
+        mean, var, d_mean, d_var = BS.bn_stats(x, s["spatial"], s["C"])
+        own_mean, own_var = reg(s, "mean").double(), reg(s, "var").double()
+        check("mean", own_mean, mean, d_mean, label=f"{s['name']}/mean")
+        check("var", own_var, var, d_var, label=f"{s['name']}/var")
+        y, E = BS.bn_apply(x, own_mean, own_var, group(s, "scale", p_before).double(), group(s, "bias", p_before).double(), s["spatial"], s["C"])
+        out = site_planes(s, "out")
+        for t in out:
+            assert float(t[..., s["C"]:].abs().max() if s["C"] < s["Cp"] else 0.0) == 0.0, f"{s['name']}/out: padded channels are not 0"
+        check("out", sum(out), y, E, label=f"{s['name']}/out")
+        return out
+
+    # ---------------------------------------------------------------- forward
+    if arch == "cnn":
+        x0 = IS.frames_to_x(d_(frames), IS.paired_ids(ids, stack), h, w, stack)
+        assert torch.equal(eng.region("bn/x0")[: N2 * h * w * 8].view(torch.int32), M.split_words(x0)), "bn/x0 is not the S8 split of uint8 / 255"
+        cur = site_forward(site_of[-1])
+    else:
+        x_fc = d_(obs_all)
+        assert torch.equal(eng.region("bn/x0")[: N2 * obs[0]].view(torch.int32), x_fc.reshape(-1).view(torch.int32)), "bn/x0 is not concat(state, next_state)"
+        cur = None
+
+    def contraction(i, l, xin, mod, p, src=None):
+        """(value + bias, S + |bias|, c) of layer l (None: the head) on input planes xin at p passes; src: the parameters (default: before the step)"""
+        src = src or p0
+        wt = M.split(torch.from_numpy(np.asarray(src[mod]["kernel"])).to(dev))
+        b = torch.from_numpy(np.asarray(src[mod]["bias"], np.float64)).to(dev)
+        if l is not None and l["kind"] == 0:
+            v, S = M.conv(p, xin, wt, l["s"])
+            c = M.chain_depth(l["K"])
+        else:
+            v, S = M.dense(p, xin, wt)
+            in_p = l["in_p"] if l is not None else layers[-1]["cp"]
+            out_p = l["cp"] if l is not None else nha_p
+            c = M.chain_depth(in_p, slabs=_fwd_splits(N2, out_p, in_p, arch == "fc" and i == 0))
+        return v + b, S + b.abs(), c
+
+    def layer_input(i, l, below_out):
+        if l is not None and l["kind"] == 0:
+            return tuple(t.reshape(N2, l["hin"], l["win"], l["cin_p"])[..., : l["cin"]] for t in below_out)
+        if i == 0:
+            return M.split(x_fc)
+        return true_planes(site_of[i - 1], below_out)
+
+    inputs = {}
+    for i, l in enumerate(layers):
+        xin = inputs[i] = layer_input(i, l, cur)
+        want, S, c = contraction(i, l, xin, l["name"], passes)
+        alt, _, _ = contraction(i, l, xin, l["name"], other)
+        shape = (N2, l["npix"], l["c"])
+        z = eng.region(f"z/{l['name']}")[: N2 * l["npix"] * l["cp"]].reshape(N2, l["npix"], l["cp"])[:, :, : l["c"]].double()
+        check("z", z, want.reshape(shape), M.bound(S, c).reshape(shape), S.reshape(shape), alt.reshape(shape), label=f"z/{l['name']} (c = {c})")
+        gamma, beta = (vec(l["ln"], k) if l["ln"] else None for k in ("scale", "bias"))
+        a, E = M.ln_relu_fwd(z, gamma, beta, torch.zeros_like(z), has_ln=l["ln"] is not None)
+        act = sum(s8(f"act/{l['name']}", N2, l["npix"] * l["cp"])).reshape(N2, l["npix"], l["cp"])
+        assert float(act[..., l["c"]:].abs().max() if l["c"] < l["cp"] else 0.0) == 0.0, f"act/{l['name']}: padded channels are not 0"
+        check("act", act[:, :, : l["c"]], a, E, label=f"act/{l['name']}")
+        cur = site_forward(site_of[i])
+    head = f"Dense_{sum(l['kind'] == 1 for l in layers)}"
+    xin = inputs[len(layers)] = layer_input(len(layers), None, cur)
+    want, S, c = contraction(len(layers), None, xin, head, passes)
+    alt, _, _ = contraction(len(layers), None, xin, head, other)
+    q = eng.region("q")[: N2 * nha_p].reshape(N2, nha_p)[:, :nha]
+    check("q", q.double(), want, M.bound(S, c), S, alt, label=f"q (c = {c})")
+    a_idx = d_(inp["action"].astype(np.int64))
+    cols = (torch.arange(K, device=dev)[None, :] + oh) * A + a_idx[:, None]
+    assert torch.equal(eng.q_values, q[:B].gather(1, cols)), "q_values are not the taken actions' q"
+    r64, t64 = d_(inp["reward"].astype(np.float64)), d_(inp["terminal"].astype(np.float64))
+    tg = M.bellman_targets(q[B:].double(), r64, t64, 0.99, K, A)
+    check("targets", eng.targets.double(), tg, M.ROUNDING * 3 * M.U * (r64.abs()[:, None] + tg.abs()) + M.FLOOR)
+
+    # ---------------------------------------------------------------- backward
+    dout = eng.region("dout")[: N2 * nha_p].reshape(N2, nha_p)
+    assert float(dout[B:].abs().max()) == 0.0, "next-state rows of dL/dq are not zero"
+    td = eng.q_values.double() - eng.targets.double()
+    want = torch.zeros(B, nha_p, dtype=torch.float64, device=dev).scatter_(1, cols, 2.0 * td / B)
+    check("dout", dout[:B].double(), want, M.ROUNDING * 3 * M.U * want.abs() + (want != 0) * M.FLOOR)
+    hit = torch.zeros(B, nha_p, dtype=torch.bool, device=dev).scatter_(1, cols, torch.ones_like(cols, dtype=torch.bool))
+    assert torch.equal(dout[:B] != 0, hit), "dL/dq: not exactly one non-zero per transition and regressed head"
+
+    dq = M.split(dout[:, :nha])
+    wt = wsplit(head)
+    da, S = M.dense(passes, dq, tuple(t.T for t in wt))
+    E_da = M.bound(S, M.chain_depth(nha_p, epilogue=3))
+    dz_planes = {}
+    for i in range(len(layers) - 1, -1, -1):
+        l, s = layers[i], site_of[i]
+        pad = lambda t: BS._pad_channels(t.reshape(N2, s["P"], s["C"]), s["Cp"])
+        x = sum(site_planes(s, "src"))
+        mean, var, scale = reg(s, "mean").double(), reg(s, "var").double(), group(s, "scale", p_before).double()
+        dy, E_dy = pad(da), pad(E_da)
+        s1, d_s1, s2, d_s2, _, _ = BS.bn_backward(x, dy, mean, var, scale, s["spatial"], s["C"], E_dy=E_dy)
+        own_s1, own_s2 = reg(s, "dbias").double(), reg(s, "dscale").double()
+        check("dbias", own_s1, s1, d_s1, label=f"{s['name']}/dbias")
+        check("dscale", own_s2, s2, d_s2, label=f"{s['name']}/dscale")
+        _, _, _, _, dx, d_dx = BS.bn_backward(x, dy, mean, var, scale, s["spatial"], s["C"], E_dy=E_dy, s1=own_s1, s2=own_s2)
+        if arch == "fc" and i == 0:  # nothing is written over BatchNorm_0's in-place backward
+            own = eng.region("da")[: N2 * s["Cp"]].reshape(N2, 1, s["Cp"]).double()
+            check("da as left", own, dx, d_dx, label="da (fc: dx of BatchNorm_0)")
+        z = eng.region(f"z/{l['name']}")[: N2 * l["npix"] * l["cp"]].reshape(N2, l["npix"], l["cp"])[:, :, : l["c"]].double()
+        act = sum(M.s8_planes(eng.region(f"act/{l['name']}"), N2, l["npix"] * l["cp"])).reshape(N2, l["npix"], l["cp"])[:, :, : l["c"]]
+        gamma = vec(l["ln"], "scale") if l["ln"] else None
+        dzm, E = M.ln_relu_bwd(z, gamma, (act > 0).double(), dx[:, :, : l["c"]], d_dx[:, :, : l["c"]], has_ln=l["ln"] is not None)
+        dzp = tuple(t.reshape(N2, l["npix"], l["cp"]) for t in s8(f"dz/{l['name']}", N2, l["npix"] * l["cp"]))
+        for t in dzp:
+            assert float(t[..., l["c"]:].abs().max() if l["c"] < l["cp"] else 0.0) == 0.0, f"dz/{l['name']}: padded channels are not 0"
+        dzp = dz_planes[i] = tuple(t[:, :, : l["c"]] for t in dzp)
+        check("dz", sum(dzp), dzm, E, label=f"dz/{l['name']}")
+        wt = wsplit(l["name"])
+        if l["kind"] == 0:
+            da, S = M.conv_dgrad(passes, dzp, wt, (l["hin"], l["win"]), l["s"])
+            E_da = M.bound(S, M.chain_depth(l["k"] ** 2 * l["cp"], epilogue=4))
+        elif i > 0:
+            da, S = M.dense(passes, tuple(t.reshape(N2, -1) for t in dzp), tuple(t.T for t in wt))
+            E_da = M.bound(S, M.chain_depth(l["cp"], epilogue=3))
+    if arch == "cnn":  # the input site: `da` still holds Conv_0's data gradient (bn_site_backward(..., apply = false))
+        s = site_of[-1]
+        own_da = eng.region("da")[: N2 * s["P"] * 8].reshape(N2, s["P"], 8).double()
+        pad = lambda t: BS._pad_channels(t.reshape(N2, s["P"], s["C"]), 8)
+        check("da as left", own_da, pad(da), pad(E_da), pad(S), label="da (cnn: data gradient into Conv_0's input)")
+        x = sum(site_planes(s, "src"))
+        s1, d_s1, s2, d_s2, _, _ = BS.bn_backward(x, own_da, reg(s, "mean").double(), reg(s, "var").double(), group(s, "scale", p_before).double(),
+                                                  True, s["C"])
+        check("dbias", reg(s, "dbias").double(), s1, d_s1, label=f"{s['name']}/dbias (own da)")
+        check("dscale", reg(s, "dscale").double(), s2, d_s2, label=f"{s['name']}/dscale (own da)")
+
+    # ---------------------------------------------------------------- leaves of g, running averages
+    for s in sites:
+        for leaf, name in (("scale", "dscale"), ("bias", "dbias")):
+            assert torch.equal(group(s, leaf, g).view(torch.int32), reg(s, name).view(torch.int32)), f"{s['name']}/{leaf} of g is not the {name} region"
+        for leaf, name in (("mean", "mean"), ("var", "var")):
+            want, ulp2 = BS.running(group(s, leaf, p_before).cpu().numpy(), reg(s, name).cpu().numpy())
+            got = group(s, leaf, eng.params).cpu().numpy().astype(np.float64)
+            check(f"running {leaf}", torch.from_numpy(got), torch.from_numpy(want.astype(np.float64)), torch.from_numpy(ulp2), label=f"{s['name']} running {leaf}")
+    for i in range(len(layers) + 1):
+        l = layers[i] if i < len(layers) else None
+        mod = l["name"] if l is not None else head
+        dz = dz_planes[i] if l is not None else dq
+        xin = inputs[i]
+        if l is not None and l["kind"] == 0:
+            want, S = M.conv_wgrad(passes, xin, dz, l["k"], l["s"])
+            steps, slabs = _conv_wgrad_chain(N2, dict(l, name=l["name"] + " (S8 input)"))
+            c = M.ROUNDING * (M.MFMA_TREE + steps + slabs + 2)
+        else:
+            want, S = M.wgrad(passes, xin, tuple(t.reshape(N2, -1) for t in dz))
+            in_p = l["in_p"] if l is not None else layers[-1]["cp"]
+            c = M.chain_depth(N2, slabs=_dense_wgrad_slabs(N2, in_p, l["cp"] if l is not None else nha_p))
+        gk = torch.from_numpy(np.asarray(hip_g[mod]["kernel"], np.float64)).to(dev)
+        check("kernel leaves", gk, want, M.bound(S, c), S, label=f"{mod}/kernel (c = {c})")
+        dzv = (dz[0] + dz[1]).reshape(-1, dz[0].shape[-1])
+        bS = dzv.abs().sum(0)
+        gb = torch.from_numpy(np.asarray(hip_g[mod]["bias"], np.float64)).to(dev)
+        check("bias leaves", gb, dzv.sum(0), M.bound(bS, M.chain_depth(0, slabs=dzv.shape[0], epilogue=4)) + M.S8_STORE * bS, label=f"{mod}/bias")
+
+    # ---------------------------------------------------------------- acting: the running averages of the updated parameters
+    p1, after = eng.export_flax(), eng.params.clone()
+    k64 = lambda mod, leaf: torch.from_numpy(np.asarray(p1[mod][leaf], np.float64)).to(dev)
+
+    def site_running(s, x, E_x):
+        return BS.bn_apply(x, *(group(s, k, after).double() for k in ("mean", "var", "scale", "bias")), s["spatial"], s["C"], E_x=E_x)
+
+    if arch == "cnn":
+        flat_ids = np.concatenate([ids[:, :stack], ids[:, stack:]], 0).copy()
+        fwd = lambda rows: eng.forward(frames=batch._keep[0], frame_stride=frames.shape[1], frame_ids=d_(flat_ids[rows].copy()), n_rows=len(flat_ids[rows]))
+        x = sum(M.split(x0)).reshape(N2, h * w, 8)
+        y, E = site_running(site_of[-1], x, torch.zeros_like(x))
+    else:
+        fwd = lambda rows: eng.forward(obs=d_(obs_all[rows].copy()), n_rows=len(obs_all[rows]))
+        y, E = None, None
+
+    def acting_stages(q_got, rows):
+        """the acting forward's own tensors, as it left them in the workspace, one stage at a time: bn/<site>/out from its own input and
+        the running averages, act/<layer> through the model of its contraction on own bn/<site>/out (z is not stored: E_z goes through
+        ln_relu_fwd, as for the next-state rows in test_gpu_bf16_model.py), q on the last site's out"""
+        n = len(range(N2)[rows])
+        cur_ = None
+        if arch == "cnn":
+            assert torch.equal(eng.region("bn/x0")[: n * h * w * 8].view(torch.int32), M.split_words(x0[rows])), "acting: bn/x0"
+        for i, l in enumerate(layers + [None]):
+            sb = site_of.get(i - 1)
+            if sb is not None:
+                pitch = sb["P"] * sb["Cp"]
+                x = sum(M.s8_planes(eng.region(sb["src"]), n, pitch)).reshape(n, sb["P"], sb["Cp"])
+                y_, E_ = site_running(sb, x, None)
+                hi, lo = M.s8_planes(eng.region(sb["prefix"] + "out"), n, pitch)
+                assert int(M.s8_malformed(hi, lo).sum()) == 0, f"acting {sb['name']}/out: not a nearest-even split"
+                cur_ = tuple(t.reshape(n, sb["P"], sb["Cp"]) for t in (hi, lo))
+                check("acting out", sum(cur_), y_, E_, label=f"acting ({n} rows) {sb['name']}/out")
+                if l is not None and l["kind"] == 0:
+                    xin_ = tuple(t.reshape(n, l["hin"], l["win"], l["cin_p"])[..., : l["cin"]] for t in cur_)
+                else:
+                    xin_ = tuple(t[:, :, : sb["C"]].reshape(n, -1) for t in cur_)
+            else:
+                xin_ = M.split(x_fc[rows])
+            mod = l["name"] if l is not None else head
+            want_, S_, c_ = contraction(i, l, xin_, mod, passes, p1)
+            alt_, _, _ = contraction(i, l, xin_, mod, other, p1)
+            if l is None:
+                check("acting q (own operands)", q_got, want_, M.bound(S_, c_), S_, alt_, label=f"acting ({n} rows) q on own operands")
+                return
+            shape_ = (n, l["npix"], l["c"])
+            gamma, beta = (k64(l["ln"], k) if l["ln"] else None for k in ("scale", "bias"))
+            a_, Ea_ = M.ln_relu_fwd(want_.reshape(shape_), gamma, beta, M.bound(S_, c_).reshape(shape_), has_ln=l["ln"] is not None)
+            altA, _ = M.ln_relu_fwd(alt_.reshape(shape_), gamma, beta, M.bound(S_, c_).reshape(shape_), has_ln=l["ln"] is not None)
+            hi, lo = M.s8_planes(eng.region(f"act/{l['name']}"), n, l["npix"] * l["cp"])
+            assert int(M.s8_malformed(hi, lo).sum()) == 0, f"acting act/{l['name']}: not a nearest-even split"
+            got_ = (hi + lo).reshape(n, l["npix"], l["cp"])
+            assert float(got_[..., l["c"]:].abs().max() if l["c"] < l["cp"] else 0.0) == 0.0, f"acting act/{l['name']}: padded channels are not 0"
+            check("acting act", got_[:, :, : l["c"]], a_, Ea_, None, altA, elementwise=False, label=f"acting ({n} rows) act/{l['name']}")
+
+    q_all = fwd(slice(0, N2)).double()
+    torch.cuda.synchronize()
+    acting_stages(q_all, slice(0, N2))
+    q_one = fwd(slice(3, 4)).double()
+    torch.cuda.synchronize()
+    acting_stages(q_one, slice(3, 4))
+    # the chain as a whole, on q only: every stage's bound carried through the next (worst case in every layer: loose, reported below)
+    for i, l in enumerate(layers + [None]):
+        mod = l["name"] if l is not None else head
+        W, b = k64(mod, "kernel"), k64(mod, "bias")
+        if l is not None and l["kind"] == 0:
+            cut = lambda t: t.reshape(N2, l["hin"], l["win"], l["cin_p"])[..., : l["cin"]]
+            op = lambda a_, w_, s_=l["s"]: M.conv(1, (a_, None), (w_, None), s_)[0]
+            z, Ez, _ = BS.exact_layer(op, cut(y), cut(E), W, passes, M.chain_depth(l["K"]))
+        else:
+            if y is None:
+                xi, Ei = x_fc.double(), torch.zeros_like(x_fc, dtype=torch.float64)
+            else:
+                sb = site_of[i - 1]
+                xi, Ei = (t[:, :, : sb["C"]].reshape(N2, -1) for t in (y, E))
+            in_p = l["in_p"] if l is not None else layers[-1]["cp"]
+            c = M.chain_depth(in_p, slabs=_fwd_splits(N2, l["cp"] if l is not None else nha_p, in_p, arch == "fc" and i == 0))
+            z, Ez, _ = BS.exact_layer(torch.matmul, xi, Ei, W, passes, c)
+        z, Ez = z + b, Ez + M.ROUNDING * M.U * b.abs()
+        if l is None:
+            break
+        gamma, beta = (k64(l["ln"], k) if l["ln"] else None for k in ("scale", "bias"))
+        shape = (N2, l["npix"], l["c"])
+        a, Ea = M.ln_relu_fwd(z.reshape(shape), gamma, beta, Ez.reshape(shape), has_ln=l["ln"] is not None)
+        y, E = site_running(site_of[i], BS._pad_channels(a, l["cp"]), BS._pad_channels(Ea, l["cp"]))
+    check("acting q", q_all, z, Ez, label="forward(2B rows) on the running averages")
+    check("acting q", q_one, z[3:4], Ez[3:4], label="forward(row 3 alone)")
+    report.append(f"acting q: bound / max |q| = {float(Ez.max() / z.abs().max()):.2e}")
+
+    print()
+    for line in report:
+        print("  " + line)
+    for row, (used, ratio, frac) in usage.items():
+        print(f"  USAGE {case}-{precision} {row}: max |d| / bound = {used:.3f}, max |d| / 2^-24 S = {ratio:.2f}, other passes outside >= {frac:.0%}")

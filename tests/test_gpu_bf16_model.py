@@ -25,9 +25,10 @@ dropping the last transition of a partial workgroup (B1030's head test), round8 
 gradients running 3 passes (6: dz of every cnn case).
 
 Not covered here: the LayerNorm scale / bias leaves of g (their sums over B x pixels rows run through partial slabs whose order
-is not modelled), and the BatchNorm torsos in bf16 (their oracle tests hold bf16x3 tolerances).  The impala torso in bf16 and
-bf16x3 is covered stage by stage, with the same model and bounds, in tests/test_gpu_impala.py
-(test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands)."""
+is not modelled).  The impala torso in bf16 and bf16x3 is covered stage by stage, with the same model and bounds, in
+tests/test_gpu_impala.py (test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands), the BatchNorm cnn and fc networks
+in tests/test_gpu_batchnorm.py (test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands).  Still uncovered in
+bf16: the BatchNorm sites inside the impala torso ("Stack_s/BatchNorm_b"; they reuse the six kernels of csrc/batchnorm.h)."""
 import numpy as np
 import pytest
 import torch
