@@ -164,6 +164,46 @@ typedef struct isdqn_net_config {
     int32_t features[ISDQN_MAX_FEATURES]; /* cnn: 3 conv widths then dense widths; fc: dense widths     */
     int32_t n_actions;                    /* A                                                         */
     int32_t n_heads;                      /* 1 + n_bellman_iterations (isdqn.py:34-41); 1 = DQN / TF-DQN */
+    int32_t dueling;                      /* (behind n_heads, with the other head-shape fields: huber_delta .. hl_min stay contiguous and the
+                                           * struct still ends in hl_sigma, double_q.)  Dueling value / advantage heads (Wang et al., "Dueling Network Architectures for
+                                           * Deep Reinforcement Learning", ICML 2016).  0: off -- every result, workspace size, region
+                                           * offset and launch keeps what it had before the field existed.  1: on.  Anything else:
+                                           * ISDQN_ERR_ARG.  THE definition, with w = max(n_bins, n_quantiles, 1), A = n_actions,
+                                           * H = n_heads, F = features[n_features - 1] (the width of the last hidden Dense), F2 = F / 2:
+                                           * Raw head: the last Dense has R = H * (A + 1) * w outputs; output ((h * (A + 1)) + c) * w + j
+                                           * belongs to head h, stream row c, component j; c < A is advantage a = c, c = A is the value.
+                                           * Its Flax name stays the head's Dense_n, shape (F, R).
+                                           * Streams: the value rows read the hidden units [0, F2), the advantage rows read [F2, F); every
+                                           * other weight of the head kernel is a structural zero (-f 32 64 64 1024 gives Wang's two
+                                           * 512-wide streams).  With layer_norm the LayerNorm behind the last hidden layer spans both
+                                           * halves: the two streams share its statistics.
+                                           * Combine: for every row, head and j, in fp32 and in this order,
+                                           *     s    = sum_a raw[a][j]                                  in ascending a
+                                           *     mean = s / (float)A
+                                           *     out[(h * A + a) * w + j] = raw[A][j] + (raw[a][j] - mean)
+                                           * The combined rows have exactly the layout and pitch of the heads without the option ("q" at
+                                           * w = 1, "logits" at w > 1), and everything downstream reads them as it does without it: the
+                                           * four loss kernels, the expectations / means, the argmax kernels and isdqn_net_forward's q_out.
+                                           * For histogram heads this is Rainbow's per-atom dueling of the logits, for quantile heads it is
+                                           * per quantile.
+                                           * Backward: with d the loss kernels' dout [B][pitch],
+                                           *     draw[A][j] = sum_a d[a][j]                              in ascending a
+                                           *     draw[a][j] = d[a][j] - draw[A][j] / (float)A
+                                           * and the gradient of the raw head's bias is the same map applied to the reduced head-bias
+                                           * gradient.  Fixed order, no atomics, bit-identical from run to run.
+                                           * The structural zeros stay +0.0f for the life of the parameters in `params`, adam_m, adam_v,
+                                           * the bf16 hi / lo weight mirror and grad_out of grad_on_batch: they are re-zeroed behind the
+                                           * head's Adam launch on that launch's stream (Adam is per element, so this equals a masked
+                                           * gradient exactly).  The caller's initialisation writes the zeros.
+                                           * Unchanged, on the combined values: q_values, targets, priorities, loss_weights, losses_accum,
+                                           * priorities_ready, the tie rule, double_q, Munchausen, the *_target forms, grad_on_batch with
+                                           * n_pairs.  shift_params moves whole head blocks of (A + 1) * w rows, the value rows with them.
+                                           * isdqn_net_redo zeroes the outgoing column of a recycled last-hidden neuron in every raw row.
+                                           * Workspace regions, only with the option, behind every other region: "head_raw" [2B][R padded
+                                           * to 8] (the head Dense's output), "head_raw_target" (rows of "q_target" x R padded, whenever
+                                           * "q_target" exists), "dout_raw" [B][R padded] and "dbh_raw" [R padded].
+                                           * ISDQN_ERR_ARG: F odd, no hidden Dense in front of the head.  ISDQN_ERR_UNSUPPORTED: batch_norm,
+                                           * arch impala, w > 1 with R > 5456, more than 64 regressed heads.                          */
     int32_t layer_norm;                   /* 0/1 (dqn.py:56, 63, 70, 97)                               */
     int32_t batch_size;                   /* B: learn_on_batch runs the network on 2B rows (isdqn.py:95) */
     int32_t precision;                    /* ISDQN_PRECISION_*                                         */

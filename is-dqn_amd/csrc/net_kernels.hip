@@ -19,6 +19,7 @@
 #include "quantile.h"
 #include "categorical.h"
 #include "redo.h"
+#include "dueling.h"
 #include "net_plan.h"
 #include "net_problems.h"
 
@@ -1463,7 +1464,26 @@ static int impala_forward(const Plan& P, bool x3, const float* params, const flo
 static int bn_forward(const Plan& P, bool x3, const float* params, const NetInput& in, int n_img, int z_img, float* ws, float* q_out, bool running,
                       hipStream_t st);  // batchnorm.h
 
-// forward over n_img images; hidden activations -> ws act regions, head output -> q_out [n_img][nha_p]
+// Dueling heads: the raw rows ("head_raw" / "head_raw_target") that belong to the head-output rows `q_out` points at -- rows of the
+// "q" / "logits" region or of their *_target twin (null: neither)
+static float* duel_raw_rows(const Plan& P, float* ws, const float* q_out) {
+    const int64_t o = q_out - ws;
+    if (o >= P.out_off && o < P.out_off + (int64_t)P.N2 * P.nlog_p) return ws + P.raw_off + (o - P.out_off) / P.nlog_p * P.raw_p;
+    if (P.out_t_off >= 0 && o >= P.out_t_off && o < P.out_t_off + (int64_t)P.qt_rows * P.nlog_p)
+        return ws + P.raw_t_off + (o - P.out_t_off) / P.nlog_p * P.raw_p;
+    return nullptr;
+}
+// raw rows -> the combined head-output rows every consumer reads (dueling.h)
+static int duel_combine(const Plan& P, const float* raw, float* out, int n_rows, hipStream_t st) {
+    const int64_t threads = (int64_t)n_rows * P.n_heads * (P.head_nb > 0 ? P.head_nb : 1);
+    hipLaunchKernelGGL(duel_combine_kernel, dim3((unsigned)((threads + DUEL_THREADS - 1) / DUEL_THREADS)), dim3(DUEL_THREADS), 0, st, raw, P.raw_p, out,
+                       P.nlog_p, n_rows, P.n_heads, P.n_actions, P.head_nb > 0 ? P.head_nb : 1);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
+// forward over n_img images; hidden activations -> ws act regions, head output -> q_out [n_img][nha_p] (histogram / quantile heads:
+// [n_img][nlog_p]; dueling heads: the combined rows, the head Dense's own output goes to the raw rows behind them)
 static int net_forward(const Plan& P, bool x3, const float* params, const NetInput& in, int n_img, int z_img,
                        float* ws, float* q_out, hipStream_t st, int n_run = -1, int skip_post_layer = -1) {
     if (P.bn) {  // BatchNorm networks outside a learn step: the running averages (isdqn.py:130, use_running_average=True)
@@ -1478,6 +1498,10 @@ static int net_forward(const Plan& P, bool x3, const float* params, const NetInp
         float* act = l.is_head ? q_out : ws + l.act_off;
         float* z = l.is_head ? nullptr : ws + l.z_off;
         int rc;
+        if (l.is_head && P.dueling) {
+            act = duel_raw_rows(P, ws, q_out);
+            ISDQN_REQUIRE(act != nullptr, ISDQN_ERR_ARG, "dueling heads: the head output must go to the workspace's head rows");
+        }
         if (l.kind == 2)
             rc = impala_forward(P, x3, params, wmir, in, n_img, z_img, ws, st);
         else if (l.kind == 0)
@@ -1486,6 +1510,10 @@ static int net_forward(const Plan& P, bool x3, const float* params, const NetInp
             rc = dense_fwd(l, x3, params, wmir, in, prev, n_img, l.is_head ? 0 : z_img, ws + P.slab_off, act, z, st,
                            i == skip_post_layer);
         if (rc) return rc;
+        if (l.is_head && P.dueling) {
+            rc = duel_combine(P, act, q_out, n_img, st);
+            if (rc) return rc;
+        }
         prev = act;
     }
     return ISDQN_OK;
@@ -2132,6 +2160,8 @@ static void head_chain_plan(LearnCtx& c, bool plan_heads) {
     const Layer& hid = c.hid();
     static const bool hc_disabled = ISDQN_DEV_ENV("ISDQN_NO_HEAD_CHAIN");
     // (histogram and quantile heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
+    // (dueling heads too: the chain multiplies by the head kernel itself and knows no combine)
+    if (P.dueling) return;
     if (!(c.learn && c.update && plan_heads && !hc_disabled && c.target_params == nullptr && P.head_nb == 0 && P.n_layers >= 2 && hid.kind == 1 &&
           !hid.is_head && hid.has_relu && hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0))
         return;
@@ -2274,11 +2304,22 @@ static int head_chain_tail(const LearnCtx& c, hipStream_t s) {
 static int learn_loss(const LearnCtx& c) {
     // the target network's own head output ("q_target" / "logits_target": next states; Munchausen: states, then next states)
     const bool tnet = (c.double_q || c.munchausen) && c.target_params != nullptr;
-    if (!c.hc_S)
-        return loss_and_finalize(c.P, c.cfg, c.ws, c.batch, c.K, c.on0, c.tg0, c.learn, (c.learn && c.update) ? c.adam_count : nullptr, c.qv, c.tg,
-                                 c.priorities, c.losses, c.loss_accum, c.st, c.double_q,
-                                 tnet ? c.ws + c.P.out_t_off + (c.munchausen ? (int64_t)c.B * c.P.nlog_p : 0) : nullptr,
-                                 (tnet && c.munchausen) ? c.ws + c.P.out_t_off : nullptr);
+    if (!c.hc_S) {
+        int rc = loss_and_finalize(c.P, c.cfg, c.ws, c.batch, c.K, c.on0, c.tg0, c.learn, (c.learn && c.update) ? c.adam_count : nullptr, c.qv, c.tg,
+                                   c.priorities, c.losses, c.loss_accum, c.st, c.double_q,
+                                   tnet ? c.ws + c.P.out_t_off + (c.munchausen ? (int64_t)c.B * c.P.nlog_p : 0) : nullptr,
+                                   (tnet && c.munchausen) ? c.ws + c.P.out_t_off : nullptr);
+        if (rc || !(c.learn && c.P.dueling)) return rc;
+        // dueling heads: dL/d(combined rows) and the reduced head-bias gradient -> the raw head's (dueling.h), where the backward starts
+        const Plan& P = c.P;
+        const int w = P.head_nb > 0 ? P.head_nb : 1;
+        const int64_t threads = (int64_t)(c.B + 1) * P.n_heads * w;
+        hipLaunchKernelGGL(duel_backward_kernel, dim3((unsigned)((threads + DUEL_THREADS - 1) / DUEL_THREADS)), dim3(DUEL_THREADS), 0, c.st,
+                           (const float*)(c.ws + P.dout_off), P.nlog_p, c.ws + P.dout_raw_off, P.raw_p, (const float*)(c.ws + P.dbh_off),
+                           c.ws + P.dbh_raw_off, c.B, P.n_heads, P.n_actions, w);
+        ISDQN_HIP_CHECK(hipGetLastError());
+        return ISDQN_OK;
+    }
     if (int rc = launch_head_chain(c)) return rc;
     // with a weight-gradient stream the sums leave the critical path: BackwardSchedule enqueues head_chain_tail() there
     return c.ss ? ISDQN_OK : head_chain_sums(c, c.st);
@@ -2533,13 +2574,14 @@ static int learn_backward(const LearnCtx& c, BackwardSchedule& sched, AdamList* 
     float* ws = c.ws;
     const int B = c.B;
     int rc;
-    const float* dz_cur = ws + P.dout_off;  // gradient w.r.t. the current layer's pre-activation output
-    int dz_ld = P.nlog_p;
+    // gradient w.r.t. the current layer's pre-activation output (dueling heads: of the raw head, "dout_raw" / "dbh_raw")
+    const float* dz_cur = ws + (P.dueling ? P.dout_raw_off : P.dout_off);
+    int dz_ld = P.dueling ? P.raw_p : P.nlog_p;
     bool dz_fused = false;  // dz of layer i was already produced by the fused data gradient of layer i+1
     for (int i = P.n_layers - 1; i >= 0; --i) {
         const Layer& l = P.L[i];
         if (l.is_head) {
-            adam[c.hc_S && c.ss ? 1 : 0].add(l.b_off, l.out_p, ws + P.dbh_off, 1, 0);  // loss_finalize_kernel's stream
+            adam[c.hc_S && c.ss ? 1 : 0].add(l.b_off, l.out_p, ws + (P.dueling ? P.dbh_raw_off : P.dbh_off), 1, 0);  // loss_finalize_kernel's stream
         } else {
             dz_cur = ws + l.dz_off;
             dz_ld = l.out_p;
@@ -2614,7 +2656,23 @@ static int learn_optimizer(const LearnCtx& c, const BackwardSchedule& sched, con
     }
     rc = run_adam(adam[0], c.st);
     if (rc) return rc;
-    return sched.adam_on_side() ? chain(c.ss, c.wst, c.st) : run_adam(adam[1], c.st);
+    rc = sched.adam_on_side() ? chain(c.ss, c.wst, c.st) : run_adam(adam[1], c.st);
+    if (rc || !c.P.dueling) return rc;
+    // dueling heads: behind the head's Adam the structural zeros of the head kernel are written again (Adam is per element: this equals
+    // a masked gradient exactly).  What orders the launch: without a head chain BackwardSchedule keeps the head's weight gradient --
+    // fused into Adam, or reduced by run_adam(adam[0]) above -- and its bias entry on the caller's stream, and whatever the side stream
+    // updates is joined into the caller's stream by chain(c.ss, c.wst, c.st), in front of Adam or in the line above; so every optimizer
+    // launch of the step is behind this point on c.st.  A schedule that moves the head's update to the side stream has to keep that
+    // join in front of this launch.  A gradient-only pass masks grad_out alone
+    const Plan& P = c.P;
+    const Layer& head = c.head();
+    const int64_t threads = (int64_t)P.raw * P.duel_f2;
+    float* const none = nullptr;
+    hipLaunchKernelGGL(duel_mask_kernel, dim3((unsigned)((threads + DUEL_THREADS - 1) / DUEL_THREADS)), dim3(DUEL_THREADS), 0, c.st,
+                       c.update ? c.params : none, c.update ? c.adam_m : none, c.update ? c.adam_v : none, c.update ? c.ws + P.wsplit_off : none,
+                       c.grad_out, head.w_off, head.in_p, P.raw, P.n_actions, P.head_nb > 0 ? P.head_nb : 1, P.duel_f2);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
 }
 
 static int learn_or_loss(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, int32_t* adam_count,
@@ -2766,7 +2824,8 @@ extern "C" int isdqn_net_shift_params(const isdqn_net_config* cfg, float* params
     ISDQN_REQUIRE(params != nullptr, ISDQN_ERR_ARG, "null pointer");
     const Layer& l = P.L[P.n_layers - 1];
     hipLaunchKernelGGL(shift_kernel, dim3(ceil_div(l.in_p + 1, 256)), dim3(256), 0, (hipStream_t)stream,
-                       params + l.w_off, params + l.b_off, P.nlog, P.n_actions * (P.head_nb > 0 ? P.head_nb : 1), l.in_p);
+                       params + l.w_off, params + l.b_off, P.dueling ? P.raw : P.nlog,
+                       (P.n_actions + (P.dueling ? 1 : 0)) * (P.head_nb > 0 ? P.head_nb : 1), l.in_p);  // (dueling: the value rows move with their head)
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }

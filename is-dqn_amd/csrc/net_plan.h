@@ -109,6 +109,11 @@ struct Plan {
     int double_q, qt_rows;
     bool munchausen;
     int64_t qt_off, logits_t_off, out_t_off;
+    // Dueling heads (cfg->dueling; csrc/dueling.h): the head Dense writes raw rows of raw_p = (n_heads * (A + 1) * w padded to 8)
+    // values into "head_raw" / "head_raw_target", duel_combine_kernel turns them into the rows at out_off / out_t_off; the loss
+    // kernels' dout / dbh go through duel_backward_kernel into "dout_raw" / "dbh_raw", where the head's backward starts.  -1 without
+    int dueling, raw, raw_p, duel_f, duel_f2;  // duel_f: width of the last hidden Dense, duel_f2: its half (the value stream)
+    int64_t raw_off, raw_t_off, dout_raw_off, dbh_raw_off;
     int64_t wsplit_off;  // S8 mirror of the parameter buffer (same offsets as the fp32 master; weights only are read from it)
     int64_t slab_floats, da_floats;
     int64_t ws_bytes;
@@ -187,6 +192,22 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     // (dense_post_kernel stages a whole head row, bias and LayerNorm rows in 64 KB of LDS: 3 * 5456 floats)
     ISDQN_REQUIRE(P.qr || P.head_nb == 0 || P.nlog <= 5456, ISDQN_ERR_UNSUPPORTED, "histogram heads: n_heads * n_actions * n_bins must be <= 5456");
     ISDQN_REQUIRE(!P.qr || P.nlog <= 5456, ISDQN_ERR_UNSUPPORTED, "quantile heads: n_heads * n_actions * n_quantiles must be <= 5456");
+    ISDQN_REQUIRE(cfg->dueling == 0 || cfg->dueling == 1, ISDQN_ERR_ARG, "dueling must be 0 or 1");
+    P.dueling = cfg->dueling;
+    P.raw = P.dueling ? cfg->n_heads * (cfg->n_actions + 1) * (P.head_nb > 0 ? P.head_nb : 1) : 0;
+    P.raw_p = round_up(P.raw, 8);
+    P.duel_f = P.duel_f2 = 0;
+    if (P.dueling) {
+        ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "dueling heads are not built for BatchNorm networks");
+        ISDQN_REQUIRE(cfg->arch != ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED, "dueling heads are not built for the impala torso");
+        ISDQN_REQUIRE(P.K <= 64, ISDQN_ERR_UNSUPPORTED, "dueling heads are built for at most 64 regressed heads");
+        ISDQN_REQUIRE(P.head_nb == 0 || P.raw <= 5456, ISDQN_ERR_UNSUPPORTED,
+                      "dueling histogram / quantile heads: n_heads * (n_actions + 1) * width must be <= 5456");
+        ISDQN_REQUIRE(cfg->n_features > (cfg->arch == ISDQN_ARCH_FC ? 0 : 3), ISDQN_ERR_ARG, "dueling heads need a hidden Dense in front of the head");
+        P.duel_f = cfg->features[cfg->n_features - 1];
+        ISDQN_REQUIRE(P.duel_f >= 2 && P.duel_f % 2 == 0, ISDQN_ERR_ARG, "dueling heads: the last hidden Dense must have an even width");
+        P.duel_f2 = P.duel_f / 2;
+    }
     int nl = 0;
     int n_conv = 0, n_dense = 0, n_ln = 0;
     int64_t poff = 0;
@@ -364,7 +385,7 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         l.has_relu = l.is_head ? 0 : 1;
         l.in_f = in_f; l.in_p = in_p;
         l.in_unpadded_ld = (cfg->arch == ISDQN_ARCH_FC && i == 0) ? in_f : 0;
-        l.out_f = l.is_head ? P.nlog : cfg->features[i];
+        l.out_f = l.is_head ? (P.dueling ? P.raw : P.nlog) : cfg->features[i];
         ISDQN_REQUIRE(l.out_f >= 1 && l.out_f <= 8192, ISDQN_ERR_ARG, "bad dense width");
         l.out_p = round_up(l.out_f, 8);
         l.K = l.in_p;
@@ -577,6 +598,11 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.qt_off = P.qt_rows ? region("q_target", (int64_t)P.qt_rows * P.nha_p) : -1;
     P.logits_t_off = (P.qt_rows && P.head_nb > 0) ? region("logits_target", (int64_t)P.qt_rows * P.nlog_p) : -1;
     P.out_t_off = P.head_nb > 0 ? P.logits_t_off : P.qt_off;
+    // (dueling heads: appended behind everything else, so that an off configuration keeps every offset and the total it had)
+    P.raw_off = P.dueling ? region("head_raw", (int64_t)P.N2 * P.raw_p) : -1;
+    P.raw_t_off = (P.dueling && P.qt_rows) ? region("head_raw_target", (int64_t)P.qt_rows * P.raw_p) : -1;
+    P.dout_raw_off = P.dueling ? region("dout_raw", (int64_t)P.B * P.raw_p) : -1;
+    P.dbh_raw_off = P.dueling ? region("dbh_raw", P.raw_p) : -1;
     P.ws_bytes = off * 4;
     return ISDQN_OK;
 }

@@ -53,6 +53,7 @@ _ENGINE = [
     ("-cat", "--categorical", dict(action="store_true", default=False, help="With -hl: train the histogram heads on the C51 categorical projection loss (Bellemare et al. 2017) instead of HL-Gauss; the atoms are the bin centres (the paper's 51 atoms on [-10, 10]: -nb 51 -minn -10.2 -maxn 10.2), -sigma is ignored. Needs -hl; not with -qr or -mq.")),
     ("-qr", "--quantile_regression", dict(action="store_true", default=False, help="QR-DQN quantile-regression heads (Dabney et al. 2018): every action of every head predicts -nq quantile values, acting uses their means; -hd is kappa. Not with -hl, -mq or -bn.")),
     ("-nq", "--n_quantiles", dict(type=int, default=32, help="Number of quantiles per action. Means nothing without -qr.")),
+    ("-duel", "--dueling", dict(action="store_true", default=False, help="Dueling value / advantage heads (Wang et al. 2016): the last hidden layer of -f splits into two equal streams (-f 32 64 64 1024: two 512-wide ones), combined on the device as Q = V + A - mean(A), per bin with -hl and per quantile with -qr. Needs a hidden Dense layer of even width; not with -bn or -at impala.")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
     ("-mq", "--munchausen", dict(action="store_true", default=False, help="Munchausen targets (Vieillard et al. 2020): soft-value bootstrap plus the scaled, clipped log-policy of the taken action (the three flags below). Not with -dq.")),
     ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
@@ -160,6 +161,21 @@ def check_categorical(p: dict) -> None:
 
         check(True, p["n_bins"] if p.get("histogram_loss") else 0, p["n_quantiles"] if p.get("quantile_regression") else 0,
               p["munchausen_tau"] if p.get("munchausen") else 0.0)
+
+
+# (-duel stays out of parameters.json like -hl and -qr)
+def check_dueling(p: dict) -> None:
+    """-duel without a hidden Dense layer of even width, or with -bn or -at impala, fails before anything is written, with the
+    agents' own message."""
+    if p.get("dueling"):
+        from slimdqn._engine import check_dueling as check
+
+        check(True, p["architecture_type"], p["features"], bool(p.get("batch_norm", False)))
+
+
+def dueling_kwargs(p) -> dict:
+    """The agents' dueling keyword from parsed parameters; without -duel the keywords are the ones they were before the flag existed."""
+    return dict(dueling=True) if p.get("dueling") else {}
 
 
 # (-redo and -redot stay out of parameters.json like -hl and -qr)

@@ -76,6 +76,36 @@ def check_redo(architecture_type, batch_norm=False) -> None:
         raise ValueError(REDO_BATCH_NORM_REFUSED)
 
 
+DUELING_IMPALA_REFUSED = "dueling heads are not built for architecture_type 'impala' (ISDQN_ERR_UNSUPPORTED)"
+DUELING_BATCH_NORM_REFUSED = "dueling heads are not built for batch_norm (ISDQN_ERR_UNSUPPORTED)"
+DUELING_NEEDS_HIDDEN_DENSE = "dueling heads need a hidden Dense layer in front of the head: its two halves are the value and the advantage stream"
+DUELING_ODD_WIDTH_REFUSED = "dueling heads split the last hidden Dense into two equal streams: its width must be even"
+
+
+def check_dueling(dueling, architecture_type, features, batch_norm=False) -> None:
+    """The networks the library refuses to give dueling heads, said before anything is allocated or written."""
+    if dueling:
+        if architecture_type == "impala":
+            raise ValueError(DUELING_IMPALA_REFUSED)
+        if batch_norm:
+            raise ValueError(DUELING_BATCH_NORM_REFUSED)
+        feats = [int(f) for f in features]
+        if len(feats) <= (0 if architecture_type == "fc" else 3):
+            raise ValueError(DUELING_NEEDS_HIDDEN_DENSE)
+        if feats[-1] % 2 != 0:
+            raise ValueError(DUELING_ODD_WIDTH_REFUSED)
+
+
+def dueling_live_mask(n_hidden: int, n_heads: int, n_actions: int, width: int = 1) -> np.ndarray:
+    """Which entries of the dueling head's Flax kernel (F, R) are weights (True) and which structural zeros (include/isdqn_hip.h,
+    isdqn_net_config::dueling): column ((h * (A + 1)) + c) * width + j is a value column for c = A and reads the hidden units
+    [0, F / 2); the advantage columns c < A read [F / 2, F)."""
+    F2 = n_hidden // 2
+    c = (np.arange(n_heads * (n_actions + 1) * width) // width) % (n_actions + 1)
+    first_half = np.arange(n_hidden)[:, None] < F2
+    return np.where((c == n_actions)[None, :], first_half, ~first_half)
+
+
 class QNetEngine:
     """One Q-network (slimdqn/networks/architectures/dqn.py DQNNet + isdqn.py head view) on one GPU."""
 
@@ -105,7 +135,9 @@ class QNetEngine:
         munchausen_clip: float = -1.0,
         n_quantiles: int = 0,
         categorical: bool = False,
+        dueling: bool = False,
     ):
+        check_dueling(dueling, architecture_type, features, batch_norm)
         check_munchausen(double_q, munchausen_tau)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
@@ -157,6 +189,11 @@ class QNetEngine:
         # forward still returns Q-values, their means
         cfg.n_quantiles = int(n_quantiles)
         self.n_quantiles = int(n_quantiles)
+        # dueling: the last Dense holds a value row and n_actions advantage rows per head, read from the two halves of the last hidden
+        # layer and combined on the device (include/isdqn_hip.h, isdqn_net_config::dueling).  False leaves the field at its 0
+        if dueling:
+            cfg.dueling = 1
+        self.dueling = bool(dueling)
         # Double Q-learning targets (include/isdqn_hip.h, isdqn_net_config::double_q); the *_target forms then keep the target
         # network's rows in region "q_target"
         cfg.double_q = 1 if double_q else 0
@@ -266,10 +303,28 @@ class QNetEngine:
             return np.ascontiguousarray(flat[: d[0]].reshape(d[1], d[3])[:, : d[2]]).reshape(shape)
         return flat[: shape[0]].copy()
 
+    def head_kernel_info(self):
+        """The tensor table's entry of the last Dense's kernel."""
+        return max((i for i in self.infos if i.kind == 1), key=lambda i: i.layer)
+
+    def dueling_live_mask(self) -> np.ndarray:
+        """Boolean (F, R) over the dueling head's Flax kernel: True where a weight lives, False on the structural zeros."""
+        assert self.dueling
+        return dueling_live_mask(self.features[-1], self.n_heads, self.n_actions, max(self.n_bins, self.n_quantiles, 1))
+
     def import_flax(self, params: Dict[str, Dict[str, np.ndarray]], target: torch.Tensor | None = None, batch_stats=None) -> None:
         """Load a reference-layout pytree ({"Conv_0": {"kernel": HWIO, "bias"}, "LayerNorm_0": ...}).  BatchNorm networks: the
         running averages come from ``batch_stats`` ({"BatchNorm_0": {"mean", "var"}}, Flax's second collection); without it
-        they keep Flax's initial values (mean 0, var 1)."""
+        they keep Flax's initial values (mean 0, var 1).  Dueling heads: a non-zero structural zero of the head kernel is refused
+        (ValueError) before anything is written."""
+        if getattr(self, "dueling", False):  # (a host-side stand-in for the layout has no such attribute: off)
+            head = self.head_kernel_info()
+            mod, leaf = head.name.decode().rsplit("/", 1)
+            live = self.dueling_live_mask()
+            if np.any(np.asarray(params[mod][leaf])[~live] != 0):
+                raise ValueError(f"{mod}/{leaf}: a structural zero of the dueling head kernel is not zero (value columns read the hidden units "
+                                 "[0, F / 2), advantage columns [F / 2, F))")
+            params = {**params, mod: {**params[mod], leaf: np.where(live, params[mod][leaf], 0)}}  # (a -0.0 becomes the +0.0f the library keeps)
         flat = np.zeros(self.n_param_floats, np.float32)
         for info in self.infos:
             mod, leaf = info.name.decode().rsplit("/", 1)  # (impala: "Stack_0/Conv_1" / "kernel")
@@ -327,6 +382,10 @@ class QNetEngine:
                     fan_in, fan_out = rf * shape[2], rf * shape[3]
                 else:
                     fan_in, fan_out = shape
+                duel_head = getattr(self, "dueling", False) and info.kind == 1 and info.layer == self.head_kernel_info().layer
+                if duel_head:  # the live entries of a column are one F / 2-wide stream: drawn at that fan-in, scattered below
+                    full_shape, shape = shape, (shape[0] // 2, shape[1])
+                    fan_in = shape[0]
                 xavier = self.architecture_type == "cnn" or (self.architecture_type == "impala" and (info.kind == 1 or mod.endswith("/Conv_0")))
                 if xavier:  # (impala: kernel_init is passed to each Stack's first conv and to the Dense layers only, dqn.py:17-21, 96)
                     lim = math.sqrt(6.0 / (fan_in + fan_out))
@@ -341,6 +400,11 @@ class QNetEngine:
                         w[filled : filled + draw.size] = draw
                         filled += draw.size
                     w = w.reshape(shape) * std
+                if duel_head:
+                    live = self.dueling_live_mask()
+                    full = np.zeros(full_shape)
+                    full.T[live.T] = w.T.reshape(-1)  # column by column: every column has exactly F / 2 live rows, in ascending order
+                    w = full
                 params.setdefault(mod, {})[leaf] = w.astype(np.float32)
             elif info.kind in (3, 5):  # LayerNorm / BatchNorm scale
                 params.setdefault(mod, {})[leaf] = np.ones(shape, np.float32)

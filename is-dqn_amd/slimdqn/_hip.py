@@ -34,6 +34,7 @@ class NetConfig(ctypes.Structure):
         ("features", c_int32 * MAX_FEATURES),
         ("n_actions", c_int32),
         ("n_heads", c_int32),
+        ("dueling", c_int32),  # 0: off; 1: dueling value / advantage heads, combined on the device (include/isdqn_hip.h)
         ("layer_norm", c_int32),
         ("batch_size", c_int32),
         ("precision", c_int32),

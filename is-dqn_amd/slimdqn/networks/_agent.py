@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
-from slimdqn._engine import QNetEngine, check_categorical, check_munchausen, check_quantiles, check_redo
+from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_munchausen, check_quantiles, check_redo
 
 
 class DeviceParams:
@@ -112,7 +112,9 @@ class EngineAgent:
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
                            n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0, double_q=False,
-                           munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False):
+                           munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False, dueling=False):
+        check_dueling(dueling, architecture_type, features, batch_norm)
+        self.dueling = bool(dueling)
         check_munchausen(double_q, munchausen_tau)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         self.categorical = bool(categorical)
@@ -152,7 +154,7 @@ class EngineAgent:
             n_bins=self.n_bins, min_value=self.min_value, max_value=self.max_value, sigma=self.sigma,
             double_q=self.double_q,
             munchausen_tau=self.munchausen_tau, munchausen_alpha=self.munchausen_alpha, munchausen_clip=self.munchausen_clip,
-            n_quantiles=self.n_quantiles, categorical=self.categorical,
+            n_quantiles=self.n_quantiles, categorical=self.categorical, dueling=self.dueling,
         )
         if init:
             eng.init_params(self._seed)

@@ -82,6 +82,7 @@ class AnalysisDQN(iSDQN):
         included (padded entries have zero gradients anyway).  Dot products and norms do not depend on the order of entries."""
         if self._feature_mask is None:
             eng, A = self._engine, self.n_actions
+            A += 1 if eng.dueling else 0  # dueling heads: a head's block holds its value row behind the A advantage rows
             m = torch.zeros(eng.n_param_floats, dtype=torch.float32)
             last = max(i.layer for i in eng.infos)
             for info in eng.infos:

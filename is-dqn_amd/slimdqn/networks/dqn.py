@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import check_categorical, check_munchausen, check_quantiles
+from slimdqn._engine import check_categorical, check_dueling, check_munchausen, check_quantiles
 from slimdqn.networks._agent import DeviceParams, EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -45,8 +45,13 @@ class DQN(EngineAgent):
         n_quantiles: int = 0,
         huber_delta: float = 0.0,
         categorical: bool = False,
+        dueling: bool = False,
     ):
-        """``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
+        """``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
+        Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
+        halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
+        values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
+        ``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
         isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
         ``n_quantiles`` > 0 or Munchausen targets (ValueError).
         ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
@@ -61,10 +66,11 @@ class DQN(EngineAgent):
         value it (include/isdqn_hip.h, isdqn_net_config::double_q): one more forward per step.
         ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
         check_munchausen(double_q, munchausen_tau)
+        check_dueling(dueling, architecture_type, features, False)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
-        self.network = DQNNet([int(f) for f in features], architecture_type, n_actions * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
+        self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
         self.data_to_update = data_to_update
         self.target_update_frequency = target_update_frequency
         self.target_params = None
@@ -72,7 +78,7 @@ class DQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
                                 max_value=max_value, sigma=sigma, double_q=double_q, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical)
+                                huber_delta=huber_delta, categorical=categorical, dueling=dueling)
         self.target_params = self.params.copy()  # dqn.py:34
         self.cumulated_loss = 0
 

@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import QNetEngine, check_categorical, check_munchausen, check_quantiles
+from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_munchausen, check_quantiles
 from slimdqn.networks._agent import DeviceParams, EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -57,8 +57,13 @@ class iSDQN(EngineAgent):
         munchausen_clip: float = -1.0,
         n_quantiles: int = 0,
         categorical: bool = False,
+        dueling: bool = False,
     ):
-        """``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
+        """``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
+        Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
+        halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
+        values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
+        ``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
         isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
         ``n_quantiles`` > 0 or Munchausen targets (ValueError).
         ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
@@ -72,12 +77,13 @@ class iSDQN(EngineAgent):
         ``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss.
         ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
         cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
+        check_dueling(dueling, architecture_type, features, batch_norm)
         check_munchausen(double_q, munchausen_tau)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
         self.n_bellman_iterations = n_bellman_iterations
         self.last_idx_mlp = len(features) if architecture_type == "fc" else len(features) - 3
-        self.network = DQNNet([int(f) for f in features], architecture_type, (1 + n_bellman_iterations) * n_actions * max(int(n_bins), int(n_quantiles), 1),
+        self.network = DQNNet([int(f) for f in features], architecture_type, (1 + n_bellman_iterations) * (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1),
                               layer_norm, batch_norm)
         self.data_to_update = data_to_update
         self.target_update_frequency = target_update_frequency
@@ -87,7 +93,7 @@ class iSDQN(EngineAgent):
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
-                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical)
+                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical, dueling)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 

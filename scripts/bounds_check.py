@@ -53,10 +53,10 @@ def report(case, omit=None):
     print(json.dumps({"case": case, "bad": bad, "site": site, "addr": hex(addr), "omitted": omit}), flush=True)
 
 
-def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False, n_quantiles=0, categorical=False):
+def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False, n_quantiles=0, categorical=False, dueling=False):
     n_heads = 1 + K if K > 0 else 1
     eng = QNetEngine(obs, A, n_heads, feats, arch, ln, B, batch_norm=bn, double_q=double_q, n_bins=n_bins, min_value=-10.0, max_value=10.0, sigma=0.3,
-                     munchausen_tau=0.03 if munchausen else 0.0, n_quantiles=n_quantiles, huber_delta=1.0 if n_quantiles else 0.0, categorical=categorical)
+                     munchausen_tau=0.03 if munchausen else 0.0, n_quantiles=n_quantiles, huber_delta=1.0 if n_quantiles else 0.0, categorical=categorical, dueling=dueling)
     eng.init_params(0)
     rng = np.random.default_rng(0)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -176,6 +176,14 @@ if __name__ == "__main__":
         dict(name="c51-dq-cnn-tiny-nb65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, double_q=True, n_bins=65, categorical=True),
         dict(name="c51-dq-cnn-one-head-dqn-nb65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=0, A=5, B=6, target=True, double_q=True, n_bins=65,
              categorical=True),
+        # dueling heads (sites 36 / 37: the raw rows duel_combine_kernel reads and the dout / dbh rows duel_backward_kernel reads; F = 14:
+        # a group of 8 hidden units straddles the two streams), one case per head kind, the DQN forms' rows from region "head_raw_target"
+        dict(name="duel-scalar-cnn-tiny-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=3, A=5, B=6, dueling=True),
+        dict(name="duel-scalar-fc-one-head-dqn-B5", arch="fc", obs=(8,), feats=(20, 14), K=0, A=3, B=5, target=True, double_q=True, dueling=True),
+        dict(name="duel-hist-cnn-tiny-nb65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=3, A=5, B=6, n_bins=65, munchausen=True, dueling=True),
+        dict(name="duel-cat-cnn-one-head-dqn-nb65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=0, A=5, B=6, target=True, double_q=True, n_bins=65,
+             categorical=True, dueling=True),
+        dict(name="duel-quant-cnn-tiny-N65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=3, A=5, B=6, n_quantiles=65, dueling=True),
         # negative control: the checker must notice a tensor that was not registered
         dict(name="control-action-not-registered", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, omit="action"),
     ]
