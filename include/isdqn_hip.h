@@ -209,6 +209,39 @@ typedef struct isdqn_net_config {
     int32_t precision;                    /* ISDQN_PRECISION_*                                         */
     float gamma_n;                        /* gamma ** update_horizon (isdqn.py:107)                    */
     float learning_rate, adam_b1, adam_b2, adam_eps; /* optax.adam(lr, eps=adam_eps) (isdqn.py:46)    */
+    float max_grad_norm;                  /* (behind adam_eps, with the other fields of the optimizer: huber_delta .. hl_min stay contiguous
+                                           * and the struct still ends in hl_sigma, double_q.)  Clipping of the gradient by its global norm
+                                           * in front of Adam (optax.clip_by_global_norm chained with optax.adam).  0: off -- every result,
+                                           * workspace size, region offset and launch keeps what it had before the field existed.  > 0
+                                           * (+inf allowed: measure, never clip): on.  Negative or NaN: ISDQN_ERR_ARG.  THE definition,
+                                           * with c = max_grad_norm and g the reduced gradient the step would have fed to Adam (the sum of
+                                           * its split-K / per-image slabs in adam_kernel's own order):
+                                           *     n     = sqrt( sum over every trainable parameter element of g^2 )
+                                           *     scale = 1 if n < c or n == 0, else c / n
+                                           *     Adam consumes fl32(g * scale)
+                                           * The norm runs over all leaves together: conv and dense kernels, biases, LayerNorm scale and
+                                           * bias, all heads.  Padding elements carry a zero gradient.  With dueling = 1 the structural
+                                           * zeros of the head kernel are NOT part of the norm (their raw weight gradient is not zero):
+                                           * they are zeroed in the reduced gradient before the squares are taken.  The squares of the fp32
+                                           * gradient are accumulated in float64 in a fixed order, without atomics: per workgroup of the
+                                           * reduction over the float4 positions it owns (16 in ascending order where slabs are summed,
+                                           * 256 through a fixed tree where one slab is the gradient), then over the workgroups' partial
+                                           * sums by one workgroup (strided per thread, then a fixed tree).  n and scale are formed in
+                                           * float64 and stored as fp32; g * scale is one fp32 multiply per element in front of Adam's
+                                           * element update.  Every learn step computes them: learn_on_batch, its *_target and debug forms,
+                                           * and grad_on_batch, which updates nothing.  `grad_out`, where a caller passes it, stays the raw,
+                                           * unclipped reduced gradient (masked under dueling as without the option): the vector whose
+                                           * norm was taken.
+                                           * Workspace regions, only with the option, behind every other region: "grad_clip_partials" (one
+                                           * float64 per workgroup of the reduction) and "grad_clip", four floats:
+                                           *     [0] n of the last step            [1] scale of the last step
+                                           *     [2] running sum of n over update steps (fp32: [2] += [0])
+                                           *     [3] running count of update steps whose stored fp32 scale is < 1
+                                           * The caller zeroes [2] and [3], as it does losses_accum; a gradient-only pass writes [0] and [1]
+                                           * alone.  With the option no Dense weight gradient is fused into Adam and no optimizer launch
+                                           * runs beside a gradient that is still being written: both streams of the step join in front of
+                                           * the norm, and one Adam launch follows it.  ISDQN_ERR_UNSUPPORTED: batch_norm, arch impala (their learn paths run optimizer
+                                           * launches of their own).                                                                  */
     float huber_delta;                    /* 0: squared TD error, the reference's loss (isdqn.py:102); > 0: Huber loss with
                                            * this delta (0.5 d^2 for |d| <= delta, delta (|d| - delta/2) beyond; the north
                                            * star's wording), gradient clip(d, -delta, delta)                */

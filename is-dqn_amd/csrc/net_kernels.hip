@@ -1048,6 +1048,45 @@ struct AdamTable {
     AdamEntry e[ADAM_MAX_ENTRIES];
     int n, total_blocks;
 };
+// The slab reduction of one float4 position, shared by adam_kernel and grad_reduce_sq_kernel (grad_clip.h) so that both form the
+// reduced gradient in the same order: slab lane `sl` of 16 adds up the slabs sl, sl + 16, ... (adam_slab_lane_sum), the 16 lane sums
+// go through LDS and are added in ascending lane order (adam_slab_combine).
+__device__ __forceinline__ float4 adam_slab_lane_sum(const AdamEntry& en, int64_t i, int sl) {
+    float4 g = float4{0.f, 0.f, 0.f, 0.f};
+    int s = sl;
+    // (eight slabs in flight per thread first: the first layer's weight gradient leaves one slab per image at B = 256 -- 16 dependent
+    // loads per thread in batches of four were four round trips at the tail of the side queue)
+#if !defined(ISDQN_ADAM_4_IN_FLIGHT)
+    for (; s + 7 * 16 < en.n_slabs; s += 8 * 16) {
+        float4 h[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) h[u] = *reinterpret_cast<const float4*>(en.g + (int64_t)(s + u * 16) * en.slab_stride + i);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { g.x += h[u].x; g.y += h[u].y; g.z += h[u].z; g.w += h[u].w; }
+    }
+#endif
+    for (; s + 3 * 16 < en.n_slabs; s += 4 * 16) {
+        float4 h[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) h[u] = *reinterpret_cast<const float4*>(en.g + (int64_t)(s + u * 16) * en.slab_stride + i);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { g.x += h[u].x; g.y += h[u].y; g.z += h[u].z; g.w += h[u].w; }
+    }
+    for (; s < en.n_slabs; s += 16) {
+        float4 h = *reinterpret_cast<const float4*>(en.g + (int64_t)s * en.slab_stride + i);
+        g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
+    }
+    return g;
+}
+__device__ __forceinline__ float4 adam_slab_combine(const float4 (*s_g)[16], int pos) {
+    float4 g = s_g[0][pos];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) {
+        const float4 h = s_g[k][pos];
+        g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
+    }
+    return g;
+}
 __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab, float* __restrict__ p, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ consts, float lr,
                                                    float b1, float b2, float eps, float* __restrict__ grad_out,
@@ -1073,40 +1112,11 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab, float* _
         pv = *reinterpret_cast<const float4*>(v + o);
         pp = *reinterpret_cast<const float4*>(p + o);
     }
-    if (on) {
-        int s = sl;
-        // (eight slabs in flight per thread first: the first layer's weight gradient leaves one slab per image at B = 256 -- 16 dependent
-        // loads per thread in batches of four were four round trips at the tail of the side queue)
-#if !defined(ISDQN_ADAM_4_IN_FLIGHT)
-        for (; s + 7 * 16 < en.n_slabs; s += 8 * 16) {
-            float4 h[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) h[u] = *reinterpret_cast<const float4*>(en.g + (int64_t)(s + u * 16) * en.slab_stride + i);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { g.x += h[u].x; g.y += h[u].y; g.z += h[u].z; g.w += h[u].w; }
-        }
-#endif
-        for (; s + 3 * 16 < en.n_slabs; s += 4 * 16) {
-            float4 h[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) h[u] = *reinterpret_cast<const float4*>(en.g + (int64_t)(s + u * 16) * en.slab_stride + i);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { g.x += h[u].x; g.y += h[u].y; g.z += h[u].z; g.w += h[u].w; }
-        }
-        for (; s < en.n_slabs; s += 16) {
-            float4 h = *reinterpret_cast<const float4*>(en.g + (int64_t)s * en.slab_stride + i);
-            g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
-        }
-    }
+    if (on) g = adam_slab_lane_sum(en, i, sl);
     s_g[sl][pos] = g;
     __syncthreads();
     if (sl != 0 || !on) return;
-    g = s_g[0][pos];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const float4 h = s_g[k][pos];
-        g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
-    }
+    g = adam_slab_combine(s_g, pos);
     if (grad_out != nullptr) *reinterpret_cast<float4*>(grad_out + o) = g;
     if (!update) return;  // gradient only (isdqn_net_grad_on_batch)
     float* gp = &g.x; float* mp = &pm.x; float* vp = &pv.x; float* xp = &pp.x;
@@ -1118,6 +1128,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab, float* _
     *reinterpret_cast<float4*>(p + o) = pp;
     s8_store_quad(mirror, (int)o, pp.x, pp.y, pp.z, pp.w);  // S8 mirror of the updated parameters (read by the next step's MFMA stages)
 }
+
+#include "grad_clip.h"  // (inside namespace isdqn, behind the Adam table and the slab reduction it shares)
 
 // shift_params (isdqn.py:111-125): rows [0, nha-A) <- rows [A, nha) of the last Dense ([out][in] layout).  (Histogram heads: called
 // with the logit width and A * n_bins, so that whole histograms move.)
@@ -1761,18 +1773,23 @@ struct AdamList {
     void add(int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
         e.push_back(AdamEntry{p_off, size, stride, g, n_slabs, 0});
     }
+    // entries [e0, e0 + ADAM_MAX_ENTRIES) as one launch's table; `per_block`: elements a workgroup of the launch covers
+    AdamTable table(size_t e0, int per_block = 64) const {
+        AdamTable tab;
+        tab.n = 0;
+        tab.total_blocks = 0;
+        for (size_t k = e0; k < e.size() && k < e0 + ADAM_MAX_ENTRIES; ++k) {
+            AdamEntry& t = tab.e[tab.n++];
+            t = e[k];
+            t.block_start = tab.total_blocks;
+            tab.total_blocks += (int)((t.size + per_block - 1) / per_block);
+        }
+        return tab;
+    }
     int launch(hipStream_t st, const Plan& P, const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, float* ws, float* grad_out,
                bool update) const {
         for (size_t e0 = 0; e0 < e.size(); e0 += ADAM_MAX_ENTRIES) {
-            AdamTable tab;
-            tab.n = 0;
-            tab.total_blocks = 0;
-            for (size_t k = e0; k < e.size() && k < e0 + ADAM_MAX_ENTRIES; ++k) {
-                AdamEntry& t = tab.e[tab.n++];
-                t = e[k];
-                t.block_start = tab.total_blocks;
-                tab.total_blocks += (int)((t.size + 63) / 64);
-            }
+            const AdamTable tab = table(e0);
             hipLaunchKernelGGL(adam_kernel, dim3(tab.total_blocks), dim3(256), 0, st, tab, params, adam_m, adam_v, ws + P.adam_tab_off, cfg->learning_rate,
                                cfg->adam_b1, cfg->adam_b2, cfg->adam_eps, grad_out, ws + P.wsplit_off, update ? 1 : 0);
             ISDQN_HIP_CHECK(hipGetLastError());
@@ -2370,7 +2387,8 @@ static int weight_gradient(const LearnCtx& c, const WgradJob& j, AdamList* adam)
         if (rc) return rc;
     } else {
         w_slabs = effective_splits(c.B, l.gw_slabs);
-        if (w_slabs == 1 && !l.in_unpadded_ld) return dense_wgrad_fused_adam(c, l, act_in, j);
+        // (gradient clipping: no parameter may move before the norm of the whole gradient is known -- the one slab goes to "gw/")
+        if (w_slabs == 1 && !l.in_unpadded_ld && !c.P.grad_clip) return dense_wgrad_fused_adam(c, l, act_in, j);
         rc = dense_wgrad(l, c.x3, c.in, act_in, j.dz, j.dz_ld, ws + l.gw_off, c.B, j.stream);
         if (rc) return rc;
     }
@@ -2433,7 +2451,8 @@ struct BackwardSchedule {
     bool forks_after_dgrad(int i) const { return wgrad_on_side(i) && c.P.L[i].kind == 1 && i > 0; }
     // dz of the layer is final on the main stream (layer 0 with the tail swap: chain_layer0() already forked)
     bool forks_before_dgrad(int i) const { return wgrad_on_side(i) && !forks_after_dgrad(i) && !(i == 0 && layer0_chained); }
-    bool adam_on_side() const { return c.ss && forked && tail_swap; }
+    // (gradient clipping: never -- both streams join in front of the norm, learn_optimizer)
+    bool adam_on_side() const { return c.ss && forked && tail_swap && !c.P.grad_clip; }
 
     int signal_priorities() {
         if (prio_pending) {
@@ -2636,6 +2655,47 @@ static int learn_backward(const LearnCtx& c, BackwardSchedule& sched, AdamList* 
     return sched.finish();
 }
 
+// Gradient clipping (cfg->max_grad_norm > 0; grad_clip.h), on the caller's stream behind the join of both streams and behind
+// reduce_rows_kernel.  The entries of both lists in two tables: those with several slabs -> grad_reduce_sq_kernel (the reduced
+// gradient over slab 0, one float64 sum of squares per workgroup), those whose one slab IS the reduced gradient (the Dense kernels
+// that would have been fused into Adam, the reduced rows, the head bias) -> grad_flat_sq_kernel, 1024 elements per workgroup; the
+// dueling head's structural zeros leave the gradient in whichever of the two holds the head kernel.  Then grad_clip_finalize_kernel
+// (norm, scale, accumulators -> "grad_clip") and one adam_flat_kernel over every entry at its slab 0, multiplied by the scale.  A
+// gradient-only pass runs all of them: the Adam launch is what writes grad_out
+static int clipped_adam(const LearnCtx& c, const AdamList* adam) {
+    const Plan& P = c.P;
+    AdamList multi, single, all;
+    for (int k = 0; k < 2; ++k)
+        for (const AdamEntry& t : adam[k].e) {
+            (t.n_slabs > 1 ? multi : single).e.push_back(t);
+            all.add(t.p_off, t.size, t.g, 1, 0);
+        }
+    ISDQN_REQUIRE(all.e.size() <= (size_t)ADAM_MAX_ENTRIES, ISDQN_ERR_UNSUPPORTED, "gradient clipping: more tensors than one optimizer table holds");
+    const AdamTable tab_m = multi.table(0), tab_s = single.table(0, GC_FLAT_ELEMS), tab_a = all.table(0, GC_FLAT_ELEMS);
+    const int n_part = tab_m.total_blocks + tab_s.total_blocks;
+    ISDQN_REQUIRE(n_part <= P.gc_part_cap, ISDQN_ERR_SHAPE, "gradient clipping: more workgroups than the partials region holds");
+    GradClipMask dm{-1, 0, 0, 0, 0, 0, 0};
+    if (P.dueling) dm = GradClipMask{c.head().w_off, c.head().in_p, P.raw, P.n_actions, P.head_nb > 0 ? P.head_nb : 1, P.duel_f2, P.duel_f};
+    double* partials = reinterpret_cast<double*>(c.ws + P.gc_part_off);
+    float* gc = c.ws + P.gc_off;
+    if (tab_m.total_blocks > 0) {
+        hipLaunchKernelGGL(grad_reduce_sq_kernel, dim3(tab_m.total_blocks), dim3(256), 0, c.st, tab_m, dm, partials);
+        ISDQN_HIP_CHECK(hipGetLastError());
+    }
+    if (tab_s.total_blocks > 0) {
+        hipLaunchKernelGGL(grad_flat_sq_kernel, dim3(tab_s.total_blocks), dim3(GC_FLAT_THREADS), 0, c.st, tab_s, dm, partials + tab_m.total_blocks);
+        ISDQN_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(GC_FIN_THREADS), 0, c.st, (const double*)partials, n_part, c.cfg->max_grad_norm, gc,
+                       c.update ? 1 : 0);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(adam_flat_kernel, dim3(tab_a.total_blocks), dim3(GC_FLAT_THREADS), 0, c.st, tab_a, c.params, c.adam_m, c.adam_v,
+                       (const float*)(c.ws + P.adam_tab_off), c.cfg->learning_rate, c.cfg->adam_b1, c.cfg->adam_b2, c.cfg->adam_eps, c.grad_out,
+                       c.ws + P.wsplit_off, c.update ? 1 : 0, (const float*)(gc + 1));
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
 // the partial-row reductions the fused data gradients left, and the optimizer launches of both streams; the call is complete on
 // the caller's stream behind it (and the next call may touch the workspace)
 static int learn_optimizer(const LearnCtx& c, const BackwardSchedule& sched, const AdamList* adam, const ReduceJobs& red) {
@@ -2654,9 +2714,13 @@ static int learn_optimizer(const LearnCtx& c, const BackwardSchedule& sched, con
         hipLaunchKernelGGL(reduce_rows_kernel, dim3(red.block_start[red.n]), dim3(256), 0, c.st, red);
         ISDQN_HIP_CHECK(hipGetLastError());
     }
-    rc = run_adam(adam[0], c.st);
-    if (rc) return rc;
-    rc = sched.adam_on_side() ? chain(c.ss, c.wst, c.st) : run_adam(adam[1], c.st);
+    if (c.P.grad_clip) {  // (adam_on_side() is false: the side stream was joined above, every gradient of the step is final here)
+        rc = clipped_adam(c, adam);
+    } else {
+        rc = run_adam(adam[0], c.st);
+        if (rc) return rc;
+        rc = sched.adam_on_side() ? chain(c.ss, c.wst, c.st) : run_adam(adam[1], c.st);
+    }
     if (rc || !c.P.dueling) return rc;
     // dueling heads: behind the head's Adam the structural zeros of the head kernel are written again (Adam is per element: this equals
     // a masked gradient exactly).  What orders the launch: without a head chain BackwardSchedule keeps the head's weight gradient --

@@ -114,6 +114,11 @@ struct Plan {
     // kernels' dout / dbh go through duel_backward_kernel into "dout_raw" / "dbh_raw", where the head's backward starts.  -1 without
     int dueling, raw, raw_p, duel_f, duel_f2;  // duel_f: width of the last hidden Dense, duel_f2: its half (the value stream)
     int64_t raw_off, raw_t_off, dout_raw_off, dbh_raw_off;
+    // Global-norm gradient clipping (cfg->max_grad_norm > 0; csrc/grad_clip.h): "grad_clip_partials" holds one float64 sum of squares
+    // per workgroup of grad_reduce_sq_kernel / grad_flat_sq_kernel (gc_part_cap of them: every tensor rounded up to whole workgroups of 64),
+    // "grad_clip" the four floats of include/isdqn_hip.h.  -1 without
+    bool grad_clip;
+    int64_t gc_part_off, gc_off, gc_part_cap;
     int64_t wsplit_off;  // S8 mirror of the parameter buffer (same offsets as the fp32 master; weights only are read from it)
     int64_t slab_floats, da_floats;
     int64_t ws_bytes;
@@ -138,6 +143,7 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     ISDQN_REQUIRE(cfg->precision == ISDQN_PRECISION_BF16X3 || cfg->precision == ISDQN_PRECISION_BF16, ISDQN_ERR_ARG,
                   "bad precision");
     ISDQN_REQUIRE(cfg->huber_delta >= 0.f, ISDQN_ERR_ARG, "huber_delta must be >= 0 (0 = squared error)");
+    ISDQN_REQUIRE(cfg->max_grad_norm >= 0.f, ISDQN_ERR_ARG, "max_grad_norm must be >= 0 (0 = off, inf = measure only)");  // (NaN fails too)
     ISDQN_REQUIRE(cfg->batch_norm == 0 || cfg->batch_norm == 1, ISDQN_ERR_ARG, "batch_norm must be 0 or 1");
     ISDQN_REQUIRE(cfg->double_q == 0 || cfg->double_q == 1, ISDQN_ERR_ARG, "double_q must be 0 or 1");
     ISDQN_REQUIRE(std::isfinite(cfg->munchausen_tau) && cfg->munchausen_tau >= 0.f, ISDQN_ERR_ARG, "munchausen_tau must be finite and >= 0 (0 = off)");
@@ -207,6 +213,11 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         P.duel_f = cfg->features[cfg->n_features - 1];
         ISDQN_REQUIRE(P.duel_f >= 2 && P.duel_f % 2 == 0, ISDQN_ERR_ARG, "dueling heads: the last hidden Dense must have an even width");
         P.duel_f2 = P.duel_f / 2;
+    }
+    P.grad_clip = cfg->max_grad_norm > 0.f;
+    if (P.grad_clip) {  // (their learn paths -- bn_learn_or_loss, impala_backward -- run optimizer launches of their own)
+        ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "gradient clipping is not built for BatchNorm networks");
+        ISDQN_REQUIRE(cfg->arch != ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED, "gradient clipping is not built for the impala torso");
     }
     int nl = 0;
     int n_conv = 0, n_dense = 0, n_ln = 0;
@@ -603,6 +614,11 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.raw_t_off = (P.dueling && P.qt_rows) ? region("head_raw_target", (int64_t)P.qt_rows * P.raw_p) : -1;
     P.dout_raw_off = P.dueling ? region("dout_raw", (int64_t)P.B * P.raw_p) : -1;
     P.dbh_raw_off = P.dueling ? region("dbh_raw", P.raw_p) : -1;
+    // (gradient clipping: likewise appended.  A workgroup of the reduction covers 64 elements of one tensor; a layer has at most four
+    // tensors -- kernel, bias, LayerNorm scale and bias -- each of which may end in a partly filled workgroup)
+    P.gc_part_cap = P.grad_clip ? (P.n_params + 63) / 64 + 4 * (int64_t)nl : 0;
+    P.gc_part_off = P.grad_clip ? region("grad_clip_partials", 2 * P.gc_part_cap) : -1;
+    P.gc_off = P.grad_clip ? region("grad_clip", 4) : -1;
     P.ws_bytes = off * 4;
     return ISDQN_OK;
 }

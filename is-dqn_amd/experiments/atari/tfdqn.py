@@ -16,7 +16,7 @@ import numpy as np
 from experiments.base.dqn import train
 from experiments.atari.common import make_environment, make_replay, seeds
 from experiments.base.utils import prepare_logs
-from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, quantile_kappa
+from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, quantile_kappa
 from slimdqn.networks.tfdqn import TFDQN
 
 
@@ -49,6 +49,7 @@ def run(argvs=sys.argv[1:], root=None):
         **munchausen_kwargs(p),
         **quantile_kwargs(p),
         **dueling_kwargs(p),
+        **grad_clip_kwargs(p),
         huber_delta=quantile_kappa(p),
     )
     try:

@@ -54,6 +54,7 @@ _ENGINE = [
     ("-qr", "--quantile_regression", dict(action="store_true", default=False, help="QR-DQN quantile-regression heads (Dabney et al. 2018): every action of every head predicts -nq quantile values, acting uses their means; -hd is kappa. Not with -hl, -mq or -bn.")),
     ("-nq", "--n_quantiles", dict(type=int, default=32, help="Number of quantiles per action. Means nothing without -qr.")),
     ("-duel", "--dueling", dict(action="store_true", default=False, help="Dueling value / advantage heads (Wang et al. 2016): the last hidden layer of -f splits into two equal streams (-f 32 64 64 1024: two 512-wide ones), combined on the device as Q = V + A - mean(A), per bin with -hl and per quantile with -qr. Needs a hidden Dense layer of even width; not with -bn or -at impala.")),
+    ("-gc", "--max_grad_norm", dict(type=float, default=0.0, help="Clip the gradient by its global norm in front of Adam (optax.clip_by_global_norm; the dueling, QR-DQN, C51 and Rainbow recipes use 10) and log grad_norm / grad_clipped_fraction at every target update; 0 = off, inf = measure and log only. Not with -bn or -at impala.")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
     ("-mq", "--munchausen", dict(action="store_true", default=False, help="Munchausen targets (Vieillard et al. 2020): soft-value bootstrap plus the scaled, clipped log-policy of the taken action (the three flags below). Not with -dq.")),
     ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
@@ -176,6 +177,19 @@ def check_dueling(p: dict) -> None:
 def dueling_kwargs(p) -> dict:
     """The agents' dueling keyword from parsed parameters; without -duel the keywords are the ones they were before the flag existed."""
     return dict(dueling=True) if p.get("dueling") else {}
+
+
+# (-gc stays out of parameters.json like -duel)
+def check_grad_clip(p: dict) -> None:
+    """-gc negative or NaN, or > 0 with -bn or -at impala, fails before anything is written, with the agents' own message."""
+    from slimdqn._engine import check_grad_clip as check
+
+    check(p.get("max_grad_norm", 0.0), p["architecture_type"], bool(p.get("batch_norm", False)))
+
+
+def grad_clip_kwargs(p) -> dict:
+    """The agents' max_grad_norm keyword from parsed parameters; without -gc the keywords are the ones they were before the flag existed."""
+    return dict(max_grad_norm=float(p["max_grad_norm"])) if p.get("max_grad_norm") else {}
 
 
 # (-redo and -redot stay out of parameters.json like -hl and -qr)

@@ -96,6 +96,23 @@ def check_dueling(dueling, architecture_type, features, batch_norm=False) -> Non
             raise ValueError(DUELING_ODD_WIDTH_REFUSED)
 
 
+GRAD_CLIP_IMPALA_REFUSED = "gradient clipping is not built for architecture_type 'impala': the torso's backward runs its own optimizer launches (ISDQN_ERR_UNSUPPORTED)"
+GRAD_CLIP_BATCH_NORM_REFUSED = "gradient clipping is not built for batch_norm: that learn path runs its own optimizer launches (ISDQN_ERR_UNSUPPORTED)"
+GRAD_CLIP_NEGATIVE_REFUSED = "max_grad_norm must be >= 0 (0 = off, inf = measure the gradient norm and never clip)"
+
+
+def check_grad_clip(max_grad_norm, architecture_type, batch_norm=False) -> None:
+    """The thresholds and the networks the library refuses to clip, said before anything is allocated or written."""
+    c = float(max_grad_norm)
+    if not c >= 0.0:  # (NaN too)
+        raise ValueError(GRAD_CLIP_NEGATIVE_REFUSED)
+    if c > 0.0:
+        if architecture_type == "impala":
+            raise ValueError(GRAD_CLIP_IMPALA_REFUSED)
+        if batch_norm:
+            raise ValueError(GRAD_CLIP_BATCH_NORM_REFUSED)
+
+
 def dueling_live_mask(n_hidden: int, n_heads: int, n_actions: int, width: int = 1) -> np.ndarray:
     """Which entries of the dueling head's Flax kernel (F, R) are weights (True) and which structural zeros (include/isdqn_hip.h,
     isdqn_net_config::dueling): column ((h * (A + 1)) + c) * width + j is a value column for c = A and reads the hidden units
@@ -136,8 +153,10 @@ class QNetEngine:
         n_quantiles: int = 0,
         categorical: bool = False,
         dueling: bool = False,
+        max_grad_norm: float = 0.0,
     ):
         check_dueling(dueling, architecture_type, features, batch_norm)
+        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
         check_munchausen(double_q, munchausen_tau)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
@@ -173,6 +192,11 @@ class QNetEngine:
         cfg.learning_rate = float(learning_rate)
         cfg.adam_b1, cfg.adam_b2 = 0.9, 0.999
         cfg.adam_eps = float(adam_eps)
+        # max_grad_norm > 0 (inf allowed): the gradient is clipped by its global norm in front of Adam and the norm is kept in region
+        # "grad_clip" (include/isdqn_hip.h, isdqn_net_config::max_grad_norm).  0 leaves the field at its 0
+        if float(max_grad_norm) > 0.0:
+            cfg.max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm = float(max_grad_norm)
         cfg.huber_delta = float(huber_delta)  # 0: the reference's squared TD error
         cfg.batch_norm = 1 if batch_norm else 0  # architectures/dqn.py:52-53, 59-60, 66-67, 73-74, 100-101 (csrc/batchnorm.h)
         self.batch_norm = bool(batch_norm)
@@ -419,6 +443,22 @@ class QNetEngine:
         off, size = ctypes.c_int64(), ctypes.c_int64()
         _hip.check(self.lib.isdqn_net_workspace_region(ctypes.byref(self.cfg), name.encode(), ctypes.byref(off), ctypes.byref(size)))
         return self.workspace[off.value // 4 : (off.value + size.value) // 4]
+
+    @property
+    def grad_clip(self) -> torch.Tensor:
+        """View of the workspace region "grad_clip" (max_grad_norm > 0 only): [0] the gradient norm of the last learn / gradient-only
+        step, [1] the factor its gradient was multiplied by, [2] the running sum of the norms of the update steps, [3] the running count
+        of update steps that were clipped.  The caller zeroes [2] and [3] (include/isdqn_hip.h, isdqn_net_config::max_grad_norm)."""
+        return self.region("grad_clip")[:4]
+
+    def set_max_grad_norm(self, max_grad_norm: float) -> None:
+        """Another threshold for the following steps of an engine built with clipping on (the workspace does not depend on the value:
+        any threshold > 0 has the same regions).  A step that is already captured keeps the threshold it was captured with."""
+        c = float(max_grad_norm)
+        if not (c > 0.0 and self.max_grad_norm > 0.0):
+            raise ValueError("set_max_grad_norm: the engine must have been built with max_grad_norm > 0 and the new threshold must be > 0")
+        self.cfg.max_grad_norm = c
+        self.max_grad_norm = c
 
     # ------------------------------------------------------------------ C-ABI calls
     def make_batch(self, *, frames=None, frame_stride=0, frame_ids=None, state=None, next_state=None, action=None, reward=None, terminal=None,

@@ -175,7 +175,11 @@ class GraphedUpdate:
         # warm-up on a side stream (lazy one-time setup inside the library must not happen during capture)
         side = torch.cuda.Stream(self.eng.device)
         side.wait_stream(torch.cuda.current_stream(self.eng.device))
-        state = [t.clone() for t in (self.eng.params, self.eng.adam_m, self.eng.adam_v, self.eng.adam_count, self.eng.losses_accum)]
+        # (with gradient clipping the warm-up steps also add to the gradient-norm accumulators, region "grad_clip"[2:4])
+        training = [self.eng.params, self.eng.adam_m, self.eng.adam_v, self.eng.adam_count, self.eng.losses_accum]
+        if getattr(self.eng, "max_grad_norm", 0.0) > 0.0:
+            training.append(self.eng.grad_clip[2:4])
+        state = [t.clone() for t in training]
         # (prioritized: the warm-up also writes priorities back -- with the zero-filled draw block -- so the whole tree
         # state is saved: nodes, max_recorded_priority, which every later add() reads, and the latched status word)
         tree = self.rb._sampling_distribution._sum_tree if self.prioritized else None
@@ -189,7 +193,7 @@ class GraphedUpdate:
         with torch.cuda.graph(g):
             self._steps()
         # the warm-up steps must not count: restore the training state
-        for dst, src in zip((self.eng.params, self.eng.adam_m, self.eng.adam_v, self.eng.adam_count, self.eng.losses_accum), state):
+        for dst, src in zip(training, state):
             dst.copy_(src)
         if tree is not None:
             for dst, src in zip((tree._nodes_dev, tree._max_dev, tree._status), tree_state):

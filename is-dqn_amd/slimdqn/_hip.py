@@ -43,6 +43,7 @@ class NetConfig(ctypes.Structure):
         ("adam_b1", c_float),
         ("adam_b2", c_float),
         ("adam_eps", c_float),
+        ("max_grad_norm", c_float),  # 0: off; > 0 (inf allowed): clip the gradient by its global norm in front of Adam (include/isdqn_hip.h)
         ("huber_delta", c_float),
         ("munchausen_tau", c_float),  # 0: off; > 0: Munchausen targets at this temperature (include/isdqn_hip.h)
         ("munchausen_alpha", c_float),

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
-from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_munchausen, check_quantiles, check_redo
+from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles, check_redo
 
 
 class DeviceParams:
@@ -112,9 +112,13 @@ class EngineAgent:
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
                            n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0, double_q=False,
-                           munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False, dueling=False):
+                           munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False, dueling=False,
+                           max_grad_norm=0.0):
         check_dueling(dueling, architecture_type, features, batch_norm)
         self.dueling = bool(dueling)
+        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
+        self.max_grad_norm = float(max_grad_norm)
+        self._grad_clip_count = 0  # Adam step count at the last read of the gradient-norm accumulators (_grad_clip_logs)
         check_munchausen(double_q, munchausen_tau)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         self.categorical = bool(categorical)
@@ -154,7 +158,7 @@ class EngineAgent:
             n_bins=self.n_bins, min_value=self.min_value, max_value=self.max_value, sigma=self.sigma,
             double_q=self.double_q,
             munchausen_tau=self.munchausen_tau, munchausen_alpha=self.munchausen_alpha, munchausen_clip=self.munchausen_clip,
-            n_quantiles=self.n_quantiles, categorical=self.categorical, dueling=self.dueling,
+            n_quantiles=self.n_quantiles, categorical=self.categorical, dueling=self.dueling, max_grad_norm=self.max_grad_norm,
         )
         if init:
             eng.init_params(self._seed)
@@ -164,6 +168,8 @@ class EngineAgent:
             eng.adam_v.copy_(old.adam_v)
             eng.adam_count.copy_(old.adam_count)
             eng.losses_accum.copy_(old.losses_accum)
+            if self.max_grad_norm > 0.0:
+                eng.grad_clip[2:4].copy_(old.grad_clip[2:4])
         self._drop_graph()  # captured against the old engine's buffers
         self._engine = eng
         if self._trust_mirror is not None:
@@ -187,6 +193,21 @@ class EngineAgent:
             self._ring = None   # (and so have the acting graphs)
         self._trust_mirror = value
         self._engine.trust_mirror = value
+
+    def _grad_clip_logs(self) -> dict:
+        """Read and zero the gradient-norm accumulators of the engine (region "grad_clip"[2:4], kept on the device by every update
+        step): the mean gradient norm and the fraction of clipped steps over the gradient steps since the last read.  {} when
+        ``max_grad_norm`` is off.  Called where ``update_target_params`` reads ``losses_accum``."""
+        if not self.max_grad_norm > 0.0:
+            return {}
+        eng = self._engine
+        acc = eng.grad_clip[2:4]
+        norm_sum, n_clipped = (float(x) for x in acc.cpu().numpy())
+        acc.zero_()
+        count = int(eng.adam_count.item())
+        steps = max(count - self._grad_clip_count, 1)
+        self._grad_clip_count = count
+        return {"grad_norm": norm_sum / steps, "grad_clipped_fraction": n_clipped / steps}
 
     def _engine_changed(self, old) -> None:
         """Hook: a new engine replaced ``old`` (subclasses re-home extra device state)."""

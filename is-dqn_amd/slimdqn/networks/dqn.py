@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import check_categorical, check_dueling, check_munchausen, check_quantiles
+from slimdqn._engine import check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles
 from slimdqn.networks._agent import DeviceParams, EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -46,8 +46,14 @@ class DQN(EngineAgent):
         huber_delta: float = 0.0,
         categorical: bool = False,
         dueling: bool = False,
+        max_grad_norm: float = 0.0,
     ):
-        """``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
+        """``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+        optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
+        the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
+        ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
+        torso: ValueError.
+        ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
         Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
         halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
         values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
@@ -67,6 +73,7 @@ class DQN(EngineAgent):
         ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
         check_munchausen(double_q, munchausen_tau)
         check_dueling(dueling, architecture_type, features, False)
+        check_grad_clip(max_grad_norm, architecture_type, False)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
@@ -78,7 +85,7 @@ class DQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
                                 max_value=max_value, sigma=sigma, double_q=double_q, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical, dueling=dueling)
+                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm)
         self.target_params = self.params.copy()  # dqn.py:34
         self.cumulated_loss = 0
 
@@ -111,6 +118,7 @@ class DQN(EngineAgent):
             eng.losses_accum.zero_()
             logs = {"loss": self.cumulated_loss / (self.target_update_frequency / self.data_to_update)}
             self.cumulated_loss = 0
+            logs.update(self._grad_clip_logs())
             return True, logs
         return False, {}
 

@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_munchausen, check_quantiles
+from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles
 from slimdqn.networks._agent import DeviceParams, EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -58,8 +58,14 @@ class iSDQN(EngineAgent):
         n_quantiles: int = 0,
         categorical: bool = False,
         dueling: bool = False,
+        max_grad_norm: float = 0.0,
     ):
-        """``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
+        """``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+        optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
+        the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
+        ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
+        torso: ValueError.
+        ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
         Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
         halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
         values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
@@ -78,6 +84,7 @@ class iSDQN(EngineAgent):
         ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
         cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
         check_dueling(dueling, architecture_type, features, batch_norm)
+        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
         check_munchausen(double_q, munchausen_tau)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
@@ -93,7 +100,8 @@ class iSDQN(EngineAgent):
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
-                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical, dueling)
+                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical, dueling,
+                                max_grad_norm)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 
@@ -147,6 +155,7 @@ class iSDQN(EngineAgent):
             for idx_network in range(min(self.n_bellman_iterations, 5)):
                 logs[f"networks/{idx_network}_loss"] = self.cumulated_losses[idx_network] / norm
             self.cumulated_losses = np.zeros_like(self.cumulated_losses)
+            logs.update(self._grad_clip_logs())
             return True, logs
         return False, {}
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from slimdqn._engine import check_categorical, check_dueling, check_quantiles
+from slimdqn._engine import check_categorical, check_dueling, check_grad_clip, check_quantiles
 from slimdqn.networks._agent import EngineAgent
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -51,8 +51,14 @@ class TFDQN(EngineAgent):
         huber_delta: float = 0.0,
         categorical: bool = False,
         dueling: bool = False,
+        max_grad_norm: float = 0.0,
     ):
-        """``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
+        """``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+        optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
+        the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
+        ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
+        torso: ValueError.
+        ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
         Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
         halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
         values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
@@ -70,6 +76,7 @@ class TFDQN(EngineAgent):
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
         check_dueling(dueling, architecture_type, features, batch_norm)
+        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
@@ -80,7 +87,7 @@ class TFDQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, batch_norm=batch_norm,
                                 n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical, dueling=dueling)
+                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54
@@ -100,6 +107,7 @@ class TFDQN(EngineAgent):
             eng.losses_accum.zero_()
             logs = {"loss": self.cumulated_loss / (self.target_update_frequency / self.data_to_update)}
             self.cumulated_loss = 0
+            logs.update(self._grad_clip_logs())
             return True, logs
         return False, {}
 

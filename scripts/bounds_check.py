@@ -53,10 +53,11 @@ def report(case, omit=None):
     print(json.dumps({"case": case, "bad": bad, "site": site, "addr": hex(addr), "omitted": omit}), flush=True)
 
 
-def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False, n_quantiles=0, categorical=False, dueling=False):
+def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False, n_quantiles=0, categorical=False, dueling=False, max_grad_norm=0.0):
     n_heads = 1 + K if K > 0 else 1
     eng = QNetEngine(obs, A, n_heads, feats, arch, ln, B, batch_norm=bn, double_q=double_q, n_bins=n_bins, min_value=-10.0, max_value=10.0, sigma=0.3,
-                     munchausen_tau=0.03 if munchausen else 0.0, n_quantiles=n_quantiles, huber_delta=1.0 if n_quantiles else 0.0, categorical=categorical, dueling=dueling)
+                     munchausen_tau=0.03 if munchausen else 0.0, n_quantiles=n_quantiles, huber_delta=1.0 if n_quantiles else 0.0, categorical=categorical, dueling=dueling,
+                     max_grad_norm=max_grad_norm)
     eng.init_params(0)
     rng = np.random.default_rng(0)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -184,6 +185,11 @@ if __name__ == "__main__":
         dict(name="duel-cat-cnn-one-head-dqn-nb65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=0, A=5, B=6, target=True, double_q=True, n_bins=65,
              categorical=True, dueling=True),
         dict(name="duel-quant-cnn-tiny-N65-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=3, A=5, B=6, n_quantiles=65, dueling=True),
+        # gradient clipping (sites 38 / 39: the slab loads of grad_reduce_sq_kernel / grad_flat_sq_kernel -- first and last slab of every position -- and the
+        # partial sums grad_clip_finalize_kernel reads; the regions "grad_clip_partials" and "grad_clip" lie inside the registered
+        # workspace): the headline plan (Dense_0 through its one slab, per-image conv slabs) and dueling heads (the live mask)
+        dict(name="gc-cnn-headline-B8", arch="cnn", obs=(84, 84, 4), feats=HL, K=9, A=9, B=8, max_grad_norm=10.0),
+        dict(name="gc-dueling-cnn-tiny-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=3, A=5, B=6, dueling=True, max_grad_norm=1e-3),
         # negative control: the checker must notice a tensor that was not registered
         dict(name="control-action-not-registered", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, omit="action"),
     ]
