@@ -1955,79 +1955,21 @@ extern "C" int isdqn_debug_bounds_get(int32_t* bad, int32_t* site, uint64_t* add
 // =============================================================================================
 extern "C" int isdqn_net_param_layout(const isdqn_net_config* cfg, int64_t* n_param_floats, isdqn_tensor_info* infos,
                                       int32_t max_infos, int32_t* n_infos) {
-    Plan P;
+    Plan P{};
     int rc = build_plan(cfg, P);
     if (rc) return rc;
     if (n_param_floats) *n_param_floats = P.n_params;
     int n = 0;
-    auto add = [&](const char* mod, const char* leaf, int64_t off, int64_t size, int kind, int layer, int ndim,
-                   int s0, int s1, int s2, int s3, int d0, int d1, int d2, int d3 = 0) {
-        if (infos && n < max_infos) {
-            isdqn_tensor_info& t = infos[n];
-            memset(&t, 0, sizeof(t));
-            snprintf(t.name, sizeof(t.name), "%s/%s", mod, leaf);
-            t.offset = off; t.size = size; t.kind = kind; t.layer = layer; t.ndim = ndim;
-            t.flax_shape[0] = s0; t.flax_shape[1] = s1; t.flax_shape[2] = s2; t.flax_shape[3] = s3;
-            t.dims[0] = d0; t.dims[1] = d1; t.dims[2] = d2; t.dims[3] = d3;
-        }
+    for_each_param_tensor(P, [&](const isdqn_tensor_info& t) {
+        if (infos && n < max_infos) memcpy(&infos[n], &t, sizeof(t));
         ++n;
-    };
-    for (int i = 0; i < P.n_layers; ++i) {
-        const Layer& l = P.L[i];
-        if (l.kind == 2) {  // impala torso: Stack_s / {Conv_k, LayerNorm_b} (Flax nests the Stack's modules: "Stack_0/Conv_1/kernel")
-            for (int s = 0; s < IMP_STACKS; ++s) {
-                const ImpalaStack& S = P.imp[s];
-                char mod[40];
-                for (int k = 0; k < IMP_CONVS; ++k) {
-                    const Layer& c = S.conv[k];
-                    if (k >= 1 && (k & 1) && S.ln_g[(k - 1) / 2] >= 0) {  // LayerNorm_b sits in front of Conv_{1+2b}
-                        const int b = (k - 1) / 2;
-                        snprintf(mod, sizeof(mod), "Stack_%d/LayerNorm_%d", s, b);
-                        add(mod, "scale", S.ln_g[b], S.C_p, 3, i, 1, S.C, 0, 0, 0, S.C_p, 0, 0);
-                        add(mod, "bias", S.ln_b[b], S.C_p, 4, i, 1, S.C, 0, 0, 0, S.C_p, 0, 0);
-                    }
-                    snprintf(mod, sizeof(mod), "Stack_%d/%s", s, c.name);
-                    add(mod, "kernel", c.w_off, c.w_size, 0, i, 4, 3, 3, c.cin, c.cout, c.cout_p, c.taps, c.cin_p);
-                    add(mod, "bias", c.b_off, c.out_p, 2, i, 1, c.cout, 0, 0, 0, c.out_p, 0, 0);
-                }
-            }
-            if (l.has_ln) {
-                add(l.ln_name, "scale", l.g_off, l.out_p, 3, i, 1, l.out_f, 0, 0, 0, l.out_p, 0, 0);
-                add(l.ln_name, "bias", l.be_off, l.out_p, 4, i, 1, l.out_f, 0, 0, 0, l.out_p, 0, 0);
-            }
-            continue;
-        }
-        if (l.kind == 0) {
-            add(l.name, "kernel", l.w_off, l.w_size, 0, i, 4, l.ksz, l.ksz, l.cin, l.cout, l.cout_p, l.is_u8 ? l.cin : l.taps,
-                l.is_u8 ? 64 : l.cin_p);
-        } else {
-            add(l.name, "kernel", l.w_off, l.w_size, 1, i, 2, l.in_f, l.out_f, 0, 0, l.out_p, l.in_p, 0);
-        }
-        add(l.name, "bias", l.b_off, l.out_p, 2, i, 1, l.out_f, 0, 0, 0, l.out_p, 0, 0);
-        if (l.has_ln) {
-            add(l.ln_name, "scale", l.g_off, l.out_p, 3, i, 1, l.out_f, 0, 0, 0, l.out_p, 0, 0);
-            add(l.ln_name, "bias", l.be_off, l.out_p, 4, i, 1, l.out_f, 0, 0, 0, l.out_p, 0, 0);
-        }
-    }
-    for (int s = 0; s < P.n_bn; ++s) {  // BatchNorm_s: scale / bias ("params"), mean / var ("batch_stats")
-        const BnSite& b = P.bns[s];
-        int H, W;
-        if (b.layer == -1) { H = P.L[0].hin; W = P.L[0].win; }
-        else if (b.layer <= -2) { H = P.imp[(-2 - b.layer) / 2].Hp; W = P.imp[(-2 - b.layer) / 2].Wp; }
-        else { H = P.L[b.layer].hout; W = P.L[b.layer].wout; }
-        const int64_t offs[4] = {b.scale_off, b.bias_off, b.mean_off, b.var_off};
-        static const char* const leaves[4] = {"scale", "bias", "mean", "var"};
-        for (int k = 0; k < 4; ++k) {
-            if (b.spatial) add(b.name, leaves[k], offs[k], b.G_p, 5 + k, b.layer, 2, H, W, 0, 0, b.G, b.P, b.C, b.Cp);
-            else add(b.name, leaves[k], offs[k], b.G_p, 5 + k, b.layer, 1, b.P * b.C, 0, 0, 0, b.G, b.P, b.C, b.Cp);
-        }
-    }
+    });
     if (n_infos) *n_infos = n;
     return ISDQN_OK;
 }
 
 extern "C" int isdqn_net_workspace_bytes(const isdqn_net_config* cfg, int64_t* bytes) {
-    Plan P;
+    Plan P{};
     int rc = build_plan(cfg, P);
     if (rc) return rc;
     ISDQN_REQUIRE(bytes != nullptr, ISDQN_ERR_ARG, "null pointer");
@@ -2037,7 +1979,7 @@ extern "C" int isdqn_net_workspace_bytes(const isdqn_net_config* cfg, int64_t* b
 
 extern "C" int isdqn_net_workspace_region(const isdqn_net_config* cfg, const char* name, int64_t* offset_bytes,
                                           int64_t* size_bytes) {
-    Plan P;
+    Plan P{};
     int rc = build_plan(cfg, P);
     if (rc) return rc;
     ISDQN_REQUIRE(name != nullptr, ISDQN_ERR_ARG, "null name");
@@ -2882,7 +2824,7 @@ extern "C" int isdqn_net_loss_on_batch_target(const isdqn_net_config* cfg, const
 }
 
 extern "C" int isdqn_net_shift_params(const isdqn_net_config* cfg, float* params, void* stream) {
-    Plan P;
+    Plan P{};
     int rc = build_plan(cfg, P);
     if (rc) return rc;
     ISDQN_REQUIRE(params != nullptr, ISDQN_ERR_ARG, "null pointer");

@@ -12,6 +12,16 @@
 
 #include "common.h"
 
+// Image-resident conv data gradient (plan_conv_dgrad_tiles): pixels of a class per workgroup, 128 or 64.
+// One four-wave workgroup per CU cannot hide its own latencies (round 4, stamps_dgrad.txt: a K step of 384 MFMA
+// cycles takes 1 080), and half tiles make the conv2 data gradient of c2 7 us shorter (26.2 -> 18.9) -- but they fill
+// the image and read the weight fragments twice, and in the step that CU time is taken from the kernels of the other
+// queue (ab_tile64_c2.txt: the step is 3.7 % SLOWER at B = 256; at B = 32, where the chip is
+// mostly empty either way, +0.2 %: noise).  Off in the product; -DISDQN_DGRAD_TILE64_BELOW=<workgroups> builds them.
+#if !defined(ISDQN_DGRAD_TILE64_BELOW)
+#define ISDQN_DGRAD_TILE64_BELOW 0
+#endif
+
 namespace isdqn {
 
 constexpr int MAX_LAYERS = 12;
@@ -132,7 +142,14 @@ static inline void same_padding(int size, int k, int s, int& out, int& lo) {
     lo = total / 2;
 }
 
-static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
+// ---------------------------------------------------------------------------------------------------------------------------------
+// build_plan, phase by phase.  Every phase is a free function of the configuration and of what the phases before it left in the
+// plan; the order of the checks -- which refusal answers when two are violated -- is part of the interface
+// (tests/test_plan_snapshot_host.py holds messages, codes, their order and every field to a recorded snapshot).
+// ---------------------------------------------------------------------------------------------------------------------------------
+
+// Phase 1: what the configuration alone decides.
+static inline int check_options(const isdqn_net_config* cfg) {
     ISDQN_REQUIRE(cfg != nullptr, ISDQN_ERR_ARG, "null config");
     ISDQN_REQUIRE(cfg->arch == ISDQN_ARCH_CNN || cfg->arch == ISDQN_ARCH_FC || cfg->arch == ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED,
                   "architecture_type must be cnn, impala or fc");
@@ -174,12 +191,15 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         ISDQN_REQUIRE(cfg->huber_delta == 0.f, ISDQN_ERR_ARG, "huber_delta and the histogram loss (n_bins > 0) exclude each other");
         ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "the histogram loss is not built for BatchNorm networks");
     }
-    P.regions.clear();
+    return ISDQN_OK;
+}
+
+// Phase 2: batch rows, head geometry and the limits that depend on it.  Runs in front of every torso check.
+static inline int plan_heads(const isdqn_net_config* cfg, Plan& P) {
     P.B = cfg->batch_size;
     P.N2 = 2 * P.B;
     P.bn = cfg->batch_norm;
     P.Bb = P.bn ? P.N2 : P.B;
-    P.n_bn = 0;
     P.x0_off = -1;
     P.n_heads = cfg->n_heads;
     P.K = cfg->n_heads >= 2 ? cfg->n_heads - 1 : 1;
@@ -202,7 +222,6 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.dueling = cfg->dueling;
     P.raw = P.dueling ? cfg->n_heads * (cfg->n_actions + 1) * (P.head_nb > 0 ? P.head_nb : 1) : 0;
     P.raw_p = round_up(P.raw, 8);
-    P.duel_f = P.duel_f2 = 0;
     if (P.dueling) {
         ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "dueling heads are not built for BatchNorm networks");
         ISDQN_REQUIRE(cfg->arch != ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED, "dueling heads are not built for the impala torso");
@@ -219,352 +238,369 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         ISDQN_REQUIRE(cfg->batch_norm == 0, ISDQN_ERR_UNSUPPORTED, "gradient clipping is not built for BatchNorm networks");
         ISDQN_REQUIRE(cfg->arch != ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED, "gradient clipping is not built for the impala torso");
     }
-    int nl = 0;
-    int n_conv = 0, n_dense = 0, n_ln = 0;
+    P.double_q = cfg->double_q;
+    P.munchausen = cfg->munchausen_tau > 0.f;
+    P.qt_rows = P.munchausen ? P.N2 : P.double_q ? P.B : 0;
+    return ISDQN_OK;
+}
+
+// Phase 3: torso and dense tail, layer by layer in Flax's order.  The only state the layers share: where the next parameter tensor
+// goes and how many modules of each class Flax has named so far.
+struct ParamCursor {
     int64_t poff = 0;
-    int in_elems_p = 0, in_f = 0, in_p = 0;
-    static const int KS[3] = {8, 4, 3}, ST[3] = {4, 2, 1};
-
-    auto finish_params = [&](Layer& l) {
-        l.w_off = poff;
-        poff += l.w_size;
-        l.b_off = poff;
-        poff += l.out_p;
-        if (l.has_ln) {
-            l.g_off = poff;
-            poff += l.out_p;
-            l.be_off = poff;
-            poff += l.out_p;
-            snprintf(l.ln_name, sizeof(l.ln_name), "LayerNorm_%d", n_ln++);
-        } else {
-            l.g_off = l.be_off = -1;
-            l.ln_name[0] = 0;
-        }
-    };
-
-    // BatchNorm_i in call order (Flax auto-names per class): scale and bias join the optimised parameters here, the running
-    // averages are placed behind all of them (below)
+    int n_conv = 0, n_dense = 0, n_ln = 0;
     int n_bn_top = 0;  // (Flax counts BatchNorm modules per parent: the Stacks' own ones are "Stack_s/BatchNorm_b")
-    auto add_bn = [&](int layer, int spatial, int Pn, int C, int Cp, const char* name = nullptr) {
-        BnSite& b = P.bns[P.n_bn];
-        memset(&b, 0, sizeof(b));
-        b.layer = layer; b.spatial = spatial; b.P = Pn; b.C = C; b.Cp = Cp;
-        b.G = spatial ? Pn : Pn * Cp;
-        b.G_p = round_up(b.G, 8);
-        b.scale_off = poff; poff += b.G_p;
-        b.bias_off = poff; poff += b.G_p;
-        if (name) snprintf(b.name, sizeof(b.name), "%s", name);
-        else snprintf(b.name, sizeof(b.name), "BatchNorm_%d", n_bn_top++);
-        ++P.n_bn;
-    };
+};
+// what the first Dense reads: true / internal width and per-image element count
+struct DenseInput { int f, p, elems_p; };
 
-    if (cfg->arch == ISDQN_ARCH_CNN) {
-        ISDQN_REQUIRE(cfg->obs_h >= 8 && cfg->obs_w >= 8 && cfg->obs_c >= 1 && cfg->obs_c <= 16, ISDQN_ERR_ARG,
-                      "bad observation shape");
-        int h = cfg->obs_h, w = cfg->obs_w, c = cfg->obs_c, c_p = cfg->obs_c;
-        if (P.bn) {  // dqn.py:52-53: the first convolution reads BatchNorm(x / 255): S8 rows of 8-padded channels, generic K order
-            ISDQN_REQUIRE(cfg->obs_c <= 8, ISDQN_ERR_UNSUPPORTED, "BatchNorm: at most 8 stacked frames");
-            c_p = 8;
-            add_bn(-1, 1, h * w, c, c_p);
-        }
-        for (int i = 0; i < 3; ++i) {
-            Layer& l = P.L[nl++];
-            memset(&l, 0, sizeof(l));
-            l.kind = 0;
-            l.has_ln = cfg->layer_norm ? 1 : 0;
-            l.has_relu = 1;
-            l.is_u8 = (i == 0) && !P.bn;
-            l.hin = h; l.win = w; l.cin = c; l.cin_p = c_p;
-            l.ksz = KS[i]; l.stride = ST[i]; l.taps = KS[i] * KS[i];
-            int pad_w;
-            same_padding(h, l.ksz, l.stride, l.hout, l.pad);
-            same_padding(w, l.ksz, l.stride, l.wout, pad_w);
-            ISDQN_REQUIRE(pad_w == l.pad, ISDQN_ERR_UNSUPPORTED, "non-square padding is not supported");
-            l.cout = cfg->features[i];
-            ISDQN_REQUIRE(l.cout >= 1 && l.cout <= 64, ISDQN_ERR_UNSUPPORTED,
-                          "conv widths above 64 channels are not supported by the fused LayerNorm epilogue");
-            l.cout_p = round_up(l.cout, 8);
-            l.npix = l.hout * l.wout;
-            l.out_f = l.cout; l.out_p = l.cout_p;
-            l.K = l.is_u8 ? l.cin * 64 : l.taps * l.cin_p;
-            l.in_elems_p = l.hin * l.win * l.cin_p;
-            l.out_elems_p = l.npix * l.cout_p;
-            l.w_size = (int64_t)l.cout_p * l.K;
-            snprintf(l.name, sizeof(l.name), "Conv_%d", n_conv++);
-            finish_params(l);
-            // dqn.py:59-60, 66-67: BatchNorm(axis=(1, 2)) behind the first two ReLUs; :72-74: behind the flatten (a 2-D tensor: per feature)
-            if (P.bn) add_bn(i, i < 2 ? 1 : 0, l.npix, l.cout, l.cout_p);
-            h = l.hout; w = l.wout; c = l.cout; c_p = l.cout_p;
-        }
-        in_elems_p = h * w * c_p;
-        in_f = h * w * c;
-        in_p = in_elems_p;
-    } else if (cfg->arch == ISDQN_ARCH_IMPALA) {
-        ISDQN_REQUIRE(cfg->obs_h >= 8 && cfg->obs_w >= 8 && cfg->obs_c >= 1 && cfg->obs_c <= 8, ISDQN_ERR_ARG, "bad observation shape");
-        int h = cfg->obs_h, w = cfg->obs_w, c = cfg->obs_c, c_p = 8;
-        if (P.bn) add_bn(-1, 1, h * w, c, c_p);  // dqn.py:78-79
-        auto conv3 = [&](Layer& l, int hh, int ww, int cin, int cin_p, int cout, const char* nm) {
-            memset(&l, 0, sizeof(l));
-            l.kind = 0; l.has_relu = 0; l.is_u8 = 0;
-            l.hin = hh; l.win = ww; l.cin = cin; l.cin_p = cin_p; l.ksz = 3; l.stride = 1; l.taps = 9;
-            int pad_w;
-            same_padding(hh, 3, 1, l.hout, l.pad);
-            same_padding(ww, 3, 1, l.wout, pad_w);
-            l.cout = cout; l.cout_p = round_up(cout, 8);
-            l.npix = l.hout * l.wout;
-            l.out_f = l.cout; l.out_p = l.cout_p;
-            l.K = l.taps * l.cin_p;
-            l.in_elems_p = hh * ww * cin_p;
-            l.out_elems_p = l.npix * l.cout_p;
-            l.w_size = (int64_t)l.cout_p * l.K;
-            snprintf(l.name, sizeof(l.name), "%s", nm);
-            l.w_off = poff; poff += l.w_size;
-            l.b_off = poff; poff += l.out_p;
-            l.g_off = l.be_off = -1;
-        };
-        for (int s = 0; s < IMP_STACKS; ++s) {
-            ImpalaStack& S = P.imp[s];
-            memset(&S, 0, sizeof(S));
-            S.H = h; S.W = w; S.cin = c; S.cin_p = c_p;
-            S.C = cfg->features[s];
-            ISDQN_REQUIRE(S.C >= 1 && S.C <= 64, ISDQN_ERR_UNSUPPORTED, "impala stack widths above 64 channels are not supported");
-            S.C_p = round_up(S.C, 8);
-            int pw;
-            same_padding(h, 3, 2, S.Hp, S.pool_pad);
-            same_padding(w, 3, 2, S.Wp, pw);
-            ISDQN_REQUIRE(pw == S.pool_pad, ISDQN_ERR_UNSUPPORTED, "non-square observations are not supported by the impala torso");
-            // parameters in Flax's order inside a Stack: Conv_0, then per block LayerNorm_b, Conv_{1+2b}, Conv_{2+2b} (dqn.py:17-34)
-            char nm[32];
-            snprintf(nm, sizeof(nm), "Conv_0");
-            conv3(S.conv[0], h, w, c, c_p, S.C, nm);
-            for (int b = 0; b < 2; ++b) {
-                if (cfg->layer_norm) {
-                    S.ln_g[b] = poff; poff += S.C_p;
-                    S.ln_b[b] = poff; poff += S.C_p;
-                } else {
-                    S.ln_g[b] = S.ln_b[b] = -1;
-                }
-                if (P.bn) {  // dqn.py:29-30: BatchNorm(axis=(1, 2)) behind the block's ReLU
-                    snprintf(nm, sizeof(nm), "Stack_%d/BatchNorm_%d", s, b);
-                    add_bn(-2 - (2 * s + b), 1, S.Hp * S.Wp, S.C, S.C_p, nm);
-                }
-                for (int k = 1 + 2 * b; k <= 2 + 2 * b; ++k) {
-                    snprintf(nm, sizeof(nm), "Conv_%d", k);
-                    conv3(S.conv[k], S.Hp, S.Wp, S.C, S.C_p, S.C, nm);
-                }
-            }
-            h = S.Hp; w = S.Wp; c = S.C; c_p = S.C_p;
-        }
-        // the torso as one pseudo-layer: output geometry of a conv layer, the LayerNorm behind the last Stack as its LayerNorm
-        Layer& l = P.L[nl++];
-        memset(&l, 0, sizeof(l));
-        l.kind = 2;
+static inline void place_kernel_bias(ParamCursor& cur, Layer& l) {
+    l.w_off = cur.poff; cur.poff += l.w_size;
+    l.b_off = cur.poff; cur.poff += l.out_p;
+}
+// LayerNorm scale and bias of `width` floats each (-1 without)
+static inline void place_layer_norm(ParamCursor& cur, bool has_ln, int width, int64_t& g_off, int64_t& be_off) {
+    g_off = be_off = -1;
+    if (!has_ln) return;
+    g_off = cur.poff; cur.poff += width;
+    be_off = cur.poff; cur.poff += width;
+}
+// a layer's own LayerNorm, a module of the network's top level: "LayerNorm_n"
+static inline void place_named_layer_norm(ParamCursor& cur, Layer& l) {
+    place_layer_norm(cur, l.has_ln, l.out_p, l.g_off, l.be_off);
+    if (l.has_ln) snprintf(l.ln_name, sizeof(l.ln_name), "LayerNorm_%d", cur.n_ln++);
+}
+
+// BatchNorm_i in call order (Flax auto-names per class): scale and bias join the optimised parameters here, the running
+// averages are placed behind all of them (place_batch_stats)
+static inline void add_bn(Plan& P, ParamCursor& cur, int layer, int spatial, int Pn, int C, int Cp, const char* name = nullptr) {
+    BnSite& b = P.bns[P.n_bn++];
+    b.layer = layer; b.spatial = spatial; b.P = Pn; b.C = C; b.Cp = Cp;
+    b.G = spatial ? Pn : Pn * Cp;
+    b.G_p = round_up(b.G, 8);
+    b.scale_off = cur.poff; cur.poff += b.G_p;
+    b.bias_off = cur.poff; cur.poff += b.G_p;
+    if (name) snprintf(b.name, sizeof(b.name), "%s", name);
+    else snprintf(b.name, sizeof(b.name), "BatchNorm_%d", cur.n_bn_top++);
+}
+static inline void place_batch_stats(Plan& P, ParamCursor& cur) {  // batch_stats (running mean / var): behind every optimised tensor
+    for (int s = 0; s < P.n_bn; ++s) {
+        P.bns[s].mean_off = cur.poff; cur.poff += P.bns[s].G_p;
+        P.bns[s].var_off = cur.poff; cur.poff += P.bns[s].G_p;
+    }
+    P.n_params = cur.poff;
+}
+
+// Geometry of a SAME convolution (cin -> cout channels at h x w, k x k taps): everything of the Layer that follows from the shape.
+// Returns the left padding along w; the callers refuse one that differs from l.pad.
+static inline int conv_geometry(Layer& l, int h, int w, int cin, int cin_p, int cout, int k, int stride, bool is_u8) {
+    l.kind = 0;
+    l.is_u8 = is_u8;
+    l.hin = h; l.win = w; l.cin = cin; l.cin_p = cin_p;
+    l.ksz = k; l.stride = stride; l.taps = k * k;
+    int pad_w;
+    same_padding(h, k, stride, l.hout, l.pad);
+    same_padding(w, k, stride, l.wout, pad_w);
+    l.cout = cout;
+    l.cout_p = round_up(cout, 8);
+    l.npix = l.hout * l.wout;
+    l.out_f = l.cout; l.out_p = l.cout_p;
+    l.K = is_u8 ? cin * 64 : l.taps * cin_p;
+    l.in_elems_p = h * w * cin_p;
+    l.out_elems_p = l.npix * l.cout_p;
+    l.w_size = (int64_t)l.cout_p * l.K;
+    return pad_w;
+}
+
+static inline int plan_cnn_torso(const isdqn_net_config* cfg, Plan& P, ParamCursor& cur, DenseInput& in) {
+    static const int KS[3] = {8, 4, 3}, ST[3] = {4, 2, 1};  // kernel / stride fixed by the reference (dqn.py:55-69)
+    ISDQN_REQUIRE(cfg->obs_h >= 8 && cfg->obs_w >= 8 && cfg->obs_c >= 1 && cfg->obs_c <= 16, ISDQN_ERR_ARG,
+                  "bad observation shape");
+    int h = cfg->obs_h, w = cfg->obs_w, c = cfg->obs_c, c_p = cfg->obs_c;
+    if (P.bn) {  // dqn.py:52-53: the first convolution reads BatchNorm(x / 255): S8 rows of 8-padded channels, generic K order
+        ISDQN_REQUIRE(cfg->obs_c <= 8, ISDQN_ERR_UNSUPPORTED, "BatchNorm: at most 8 stacked frames");
+        c_p = 8;
+        add_bn(P, cur, -1, 1, h * w, c, c_p);
+    }
+    for (int i = 0; i < 3; ++i) {
+        Layer& l = P.L[P.n_layers++];
         l.has_ln = cfg->layer_norm ? 1 : 0;
         l.has_relu = 1;
-        l.hin = cfg->obs_h; l.win = cfg->obs_w; l.cin = cfg->obs_c; l.cin_p = 8;
-        l.hout = h; l.wout = w; l.cout = c; l.cout_p = c_p; l.npix = h * w;
-        l.out_f = c; l.out_p = c_p;
-        l.in_elems_p = cfg->obs_h * cfg->obs_w * 8;
-        l.out_elems_p = l.npix * c_p;
-        l.w_size = 0; l.w_off = -1; l.b_off = -1;
-        snprintf(l.name, sizeof(l.name), "Impala");
-        if (l.has_ln) {
-            l.g_off = poff; poff += l.out_p;
-            l.be_off = poff; poff += l.out_p;
-            snprintf(l.ln_name, sizeof(l.ln_name), "LayerNorm_%d", n_ln++);
-        } else {
-            l.g_off = l.be_off = -1;
-        }
-        if (P.bn) add_bn(nl - 1, 0, l.npix, l.cout, l.cout_p);  // dqn.py:86-88: per feature behind the flatten
-        in_elems_p = h * w * c_p;
-        in_f = h * w * c;
-        in_p = in_elems_p;
-    } else {
-        ISDQN_REQUIRE(cfg->obs_c >= 1, ISDQN_ERR_ARG, "bad observation dim");
-        in_f = cfg->obs_c;
-        in_p = round_up(in_f, 8);
-        in_elems_p = in_p;
+        const int pad_w = conv_geometry(l, h, w, c, c_p, cfg->features[i], KS[i], ST[i], i == 0 && !P.bn);
+        ISDQN_REQUIRE(pad_w == l.pad, ISDQN_ERR_UNSUPPORTED, "non-square padding is not supported");
+        ISDQN_REQUIRE(l.cout >= 1 && l.cout <= 64, ISDQN_ERR_UNSUPPORTED,
+                      "conv widths above 64 channels are not supported by the fused LayerNorm epilogue");
+        snprintf(l.name, sizeof(l.name), "Conv_%d", cur.n_conv++);
+        place_kernel_bias(cur, l);
+        place_named_layer_norm(cur, l);
+        // dqn.py:59-60, 66-67: BatchNorm(axis=(1, 2)) behind the first two ReLUs; :72-74: behind the flatten (a 2-D tensor: per feature)
+        if (P.bn) add_bn(P, cur, i, i < 2 ? 1 : 0, l.npix, l.cout, l.cout_p);
+        h = l.hout; w = l.wout; c = l.cout; c_p = l.cout_p;
     }
+    in = {h * w * c, h * w * c_p, h * w * c_p};
+    return ISDQN_OK;
+}
+
+// one 3 x 3 convolution of a Stack: no LayerNorm or ReLU of its own (the Stack's row-wise kernels run them)
+static inline void plan_impala_conv(ParamCursor& cur, Layer& l, int h, int w, int cin, int cin_p, int cout, int index) {
+    conv_geometry(l, h, w, cin, cin_p, cout, 3, 1, false);
+    snprintf(l.name, sizeof(l.name), "Conv_%d", index);
+    place_kernel_bias(cur, l);
+    l.g_off = l.be_off = -1;
+}
+
+static inline int plan_impala_torso(const isdqn_net_config* cfg, Plan& P, ParamCursor& cur, DenseInput& in) {
+    ISDQN_REQUIRE(cfg->obs_h >= 8 && cfg->obs_w >= 8 && cfg->obs_c >= 1 && cfg->obs_c <= 8, ISDQN_ERR_ARG, "bad observation shape");
+    int h = cfg->obs_h, w = cfg->obs_w, c = cfg->obs_c, c_p = 8;
+    if (P.bn) add_bn(P, cur, -1, 1, h * w, c, c_p);  // dqn.py:78-79
+    for (int s = 0; s < IMP_STACKS; ++s) {
+        ImpalaStack& S = P.imp[s];
+        S.H = h; S.W = w; S.cin = c; S.cin_p = c_p;
+        S.C = cfg->features[s];
+        ISDQN_REQUIRE(S.C >= 1 && S.C <= 64, ISDQN_ERR_UNSUPPORTED, "impala stack widths above 64 channels are not supported");
+        S.C_p = round_up(S.C, 8);
+        int pw;
+        same_padding(h, 3, 2, S.Hp, S.pool_pad);
+        same_padding(w, 3, 2, S.Wp, pw);
+        ISDQN_REQUIRE(pw == S.pool_pad, ISDQN_ERR_UNSUPPORTED, "non-square observations are not supported by the impala torso");
+        // parameters in Flax's order inside a Stack: Conv_0, then per block LayerNorm_b, Conv_{1+2b}, Conv_{2+2b} (dqn.py:17-34)
+        plan_impala_conv(cur, S.conv[0], h, w, c, c_p, S.C, 0);
+        for (int b = 0; b < 2; ++b) {
+            place_layer_norm(cur, cfg->layer_norm != 0, S.C_p, S.ln_g[b], S.ln_b[b]);
+            if (P.bn) {  // dqn.py:29-30: BatchNorm(axis=(1, 2)) behind the block's ReLU
+                char nm[32];
+                snprintf(nm, sizeof(nm), "Stack_%d/BatchNorm_%d", s, b);
+                add_bn(P, cur, -2 - (2 * s + b), 1, S.Hp * S.Wp, S.C, S.C_p, nm);
+            }
+            for (int k = 1 + 2 * b; k <= 2 + 2 * b; ++k) plan_impala_conv(cur, S.conv[k], S.Hp, S.Wp, S.C, S.C_p, S.C, k);
+        }
+        h = S.Hp; w = S.Wp; c = S.C; c_p = S.C_p;
+    }
+    // the torso as one pseudo-layer: output geometry of a conv layer, the LayerNorm behind the last Stack as its LayerNorm
+    Layer& l = P.L[P.n_layers++];
+    l.kind = 2;
+    l.has_ln = cfg->layer_norm ? 1 : 0;
+    l.has_relu = 1;
+    l.hin = cfg->obs_h; l.win = cfg->obs_w; l.cin = cfg->obs_c; l.cin_p = 8;
+    l.hout = h; l.wout = w; l.cout = c; l.cout_p = c_p; l.npix = h * w;
+    l.out_f = c; l.out_p = c_p;
+    l.in_elems_p = cfg->obs_h * cfg->obs_w * 8;
+    l.out_elems_p = l.npix * c_p;
+    l.w_size = 0; l.w_off = -1; l.b_off = -1;
+    snprintf(l.name, sizeof(l.name), "Impala");
+    place_named_layer_norm(cur, l);
+    if (P.bn) add_bn(P, cur, P.n_layers - 1, 0, l.npix, l.cout, l.cout_p);  // dqn.py:86-88: per feature behind the flatten
+    in = {h * w * c, h * w * c_p, h * w * c_p};
+    return ISDQN_OK;
+}
+
+static inline int plan_fc_input(const isdqn_net_config* cfg, DenseInput& in) {
+    ISDQN_REQUIRE(cfg->obs_c >= 1, ISDQN_ERR_ARG, "bad observation dim");
+    in = {cfg->obs_c, round_up(cfg->obs_c, 8), round_up(cfg->obs_c, 8)};
+    return ISDQN_OK;
+}
+
+// the hidden Dense layers and the head
+static inline int plan_dense_tail(const isdqn_net_config* cfg, Plan& P, ParamCursor& cur, DenseInput in) {
     const int first_dense = cfg->arch == ISDQN_ARCH_FC ? 0 : 3;
     for (int i = first_dense; i <= cfg->n_features; ++i) {
-        ISDQN_REQUIRE(nl < MAX_LAYERS, ISDQN_ERR_ARG, "too many layers");
-        Layer& l = P.L[nl++];
-        memset(&l, 0, sizeof(l));
+        ISDQN_REQUIRE(P.n_layers < MAX_LAYERS, ISDQN_ERR_ARG, "too many layers");
+        Layer& l = P.L[P.n_layers++];
         l.kind = 1;
         l.is_head = (i == cfg->n_features);
         l.has_ln = (!l.is_head && cfg->layer_norm) ? 1 : 0;
         l.has_relu = l.is_head ? 0 : 1;
-        l.in_f = in_f; l.in_p = in_p;
-        l.in_unpadded_ld = (cfg->arch == ISDQN_ARCH_FC && i == 0) ? in_f : 0;
+        l.in_f = in.f; l.in_p = in.p;
+        l.in_unpadded_ld = (cfg->arch == ISDQN_ARCH_FC && i == 0) ? in.f : 0;
         l.out_f = l.is_head ? (P.dueling ? P.raw : P.nlog) : cfg->features[i];
         ISDQN_REQUIRE(l.out_f >= 1 && l.out_f <= 8192, ISDQN_ERR_ARG, "bad dense width");
         l.out_p = round_up(l.out_f, 8);
         l.K = l.in_p;
-        l.in_elems_p = in_elems_p;
+        l.in_elems_p = in.elems_p;
         l.out_elems_p = l.out_p;
         l.w_size = (int64_t)l.out_p * l.in_p;
-        snprintf(l.name, sizeof(l.name), "Dense_%d", n_dense++);
-        finish_params(l);
-        if (P.bn && !l.is_head) add_bn(nl - 1, 0, 1, l.out_f, l.out_p);  // dqn.py:100-101
-        in_f = l.out_f; in_p = l.out_p; in_elems_p = l.out_p;
+        snprintf(l.name, sizeof(l.name), "Dense_%d", cur.n_dense++);
+        place_kernel_bias(cur, l);
+        place_named_layer_norm(cur, l);
+        if (P.bn && !l.is_head) add_bn(P, cur, P.n_layers - 1, 0, 1, l.out_f, l.out_p);  // dqn.py:100-101
+        in = {l.out_f, l.out_p, l.out_p};
     }
-    P.n_layers = nl;
-    for (int s = 0; s < P.n_bn; ++s) {  // batch_stats (running mean / var): behind every optimised tensor
-        P.bns[s].mean_off = poff; poff += P.bns[s].G_p;
-        P.bns[s].var_off = poff; poff += P.bns[s].G_p;
-    }
-    P.n_params = poff;
+    return ISDQN_OK;
+}
 
-    // ---- workspace ----
+// Phase 4: the tiling decisions of the forward and backward pass -- pure functions of a layer and of B / Bb / N2.
+
+// conv weight gradient on the generic engine: split the contraction (online pixels) over about 256 workgroups
+static inline int conv_wgrad_split(const Layer& l, int Bb) {
+    int tiles_n = ceil_div(l.K, 64);
+    int ksteps = ceil_div(Bb * l.npix, 32);
+    int s = 256 / tiles_n;
+    if (s < 1) s = 1;
+    if (s > ksteps) s = ksteps;
+    return s;
+}
+
+// conv (layer >= 1): image-resident data gradient, dgi_tiles workgroups per image (0: generic engine + separate ln_bwd)
+static inline void plan_conv_dgrad_tiles(Layer& l, int Bb) {
+    if (l.ksz % l.stride != 0 || l.cout_p > 64 || l.cin_p > 64) return;
+    auto tiles_of = [&](int tile_pix) {
+        int tiles = 0;
+        for (int c = 0; c < l.stride * l.stride; ++c) {
+            int cy = c / l.stride, cx = c % l.stride;
+            int Ha = (l.hin - cy + l.stride - 1) / l.stride, Wb = (l.win - cx + l.stride - 1) / l.stride;
+            tiles += ceil_div(Ha * Wb, tile_pix);
+        }
+        return tiles;
+    };
+    l.dgi_tile_pix = Bb * tiles_of(128) < ISDQN_DGRAD_TILE64_BELOW ? 64 : 128;  // (the switch and its measurement: top of this file)
+    l.dgi_tiles = tiles_of(l.dgi_tile_pix);
+}
+
+// conv: image-resident weight gradient (conv_img.h): column groups of 64*NTW k' columns x groups of G images ~ 256 workgroups.
+// May raise gw_slabs: one slab per group of images.
+static inline void plan_conv_wgrad_image(Layer& l, int Bb) {
+    if (l.K % 64 != 0 || !(l.is_u8 || l.cin_p % 16 == 0)) return;
+    int ntw = (l.K % 256 == 0) ? 4 : (l.K % 192 == 0) ? 3 : (l.K % 128 == 0) ? 2 : 0;
+    if (l.K == 512) ntw = 2;
+    // 64 output channels and K <= 576: one workgroup owns every k' column (8 or 9 column tiles per
+    // wave), so each image pair is staged into LDS exactly once instead of once per column group
+    const bool wide = l.cout_p == 64 && !l.is_u8 && (l.K == 512 || l.K == 576);
+    if (wide) ntw = l.K / 64;
+    if (!ntw) return;
+    int ncg = l.K / (64 * ntw);
+    int G = (Bb * ncg + 255) / 256;
+    // two images per workgroup at the headline batch (measured best, 1: 2681, 2: 2806 steps/s: 128 workgroups share
+    // the CUs with the data-gradient chain); larger batches keep at least one workgroup per CU instead of 128
+    // workgroups of 8 images (c5: conv2 / conv1 weight gradients 74 / 66 us on half the chip)
+    if (wide) G = (Bb + 127) / 128;
+#if !defined(ISDQN_WGRAD_G128)
+    if (wide && G > 2) G = std::max(2, (Bb + 255) / 256);
+#endif
+    if (G < 1) G = 1;
+    l.wgi_ntw = ntw;
+    l.wgi_G = G;
+    l.wgi_groups = ceil_div(Bb, G);
+    if (l.wgi_groups > l.gw_slabs) l.gw_slabs = l.wgi_groups;
+}
+
+// dense: split-K slabs of the weight gradient (batch rows) and of the forward GEMM; returns the floats of forward slabs it needs
+static inline int64_t plan_dense_tiling(Layer& l, int Bb, int N2) {
+    int tiles = ceil_div(l.out_p, 128) * ceil_div(l.in_p, 128);
+    int ksteps = ceil_div(Bb, 32);
+    int s = tiles >= 128 ? 1 : 256 / tiles;
+    if (s > ksteps) s = ksteps;
+    if (s < 1) s = 1;
+    l.gw_slabs = s;
+    // forward split-K slabs
+    // ~512 workgroups (two per CU hide each other's operand latency).  A GEMM of few 128 x 128 tiles gets there with
+    // 128 x 64 tiles and half the split-K slabs: same time at the headline size, 32 MB less slab traffic per step.
+    int ft = ceil_div(N2, 128) * ceil_div(l.out_p, 128);
+    l.fwd_narrow = ft <= 64 && !l.in_unpadded_ld && l.out_p % 64 == 0;
+    if (l.fwd_narrow) ft = ceil_div(N2, 128) * ceil_div(l.out_p, 64);
+    int fs = ft >= 256 ? 1 : 512 / ft;
+    int fk = ceil_div(l.K, 32);
+#if defined(ISDQN_DEV)
+    if (const char* e = getenv("ISDQN_FWD_SPLITS")) fs = atoi(e);  // development: split-K factor of the forward GEMM
+#endif
+    if (fs > fk) fs = fk;
+    if (fs < 1) fs = 1;
+    l.fwd_splits = fs;
+    return (int64_t)fs * N2 * l.out_p;
+}
+
+// rows of a hidden layer's partial-sum region ("part/"): the most any kernel that reduces into it emits
+static inline int part_rows_of(const Plan& P, int i) {
+    const Layer& l = P.L[i];
+    int rows = LN_MAX_BLOCKS;
+    if (l.kind == 1 && P.B > rows) rows = P.B;  // head chain: one row per workgroup, as few as one transition each
+    if (i + 1 < P.n_layers && P.L[i + 1].dgi_tiles > 0 && P.B * P.L[i + 1].dgi_tiles > rows) rows = P.B * P.L[i + 1].dgi_tiles;
+    // conv layer under the first dense layer: the fused dense data-gradient + LN backward emits one partial
+    // row per (64-sample tile, pixel)
+    if (l.kind != 1 && i + 1 < P.n_layers && P.L[i + 1].kind == 1 && l.cout_p == 64 && ceil_div(P.B, 64) * l.npix > rows)
+        rows = ceil_div(P.B, 64) * l.npix;
+    return rows;
+}
+
+static inline void plan_tiling(const isdqn_net_config* cfg, Plan& P) {
+    for (int i = 0; i < P.n_layers; ++i) {
+        Layer& l = P.L[i];
+        // (BatchNorm: the first convolution's data gradient is needed too -- the input BatchNorm's scale / bias gradient)
+        if (i > 0 || (P.bn && l.kind == 0)) P.da_floats = std::max(P.da_floats, (int64_t)P.Bb * l.in_elems_p);
+        if (l.kind == 0) {
+            if (i > 0) plan_conv_dgrad_tiles(l, P.Bb);
+            l.gw_slabs = conv_wgrad_split(l, P.Bb);
+            plan_conv_wgrad_image(l, P.Bb);
+        } else if (l.kind == 1) {
+            P.slab_floats = std::max(P.slab_floats, plan_dense_tiling(l, P.Bb, P.N2));
+        }
+    }
+    for (int i = 0; i < P.n_layers; ++i)  // (behind the loop above: a layer's rows depend on the tiling of the layer that consumes it)
+        if (!P.L[i].is_head) P.L[i].part_rows = part_rows_of(P, i);
+    if (cfg->arch == ISDQN_ARCH_IMPALA)
+        for (int s = 0; s < IMP_STACKS; ++s)
+            for (int k = 0; k < IMP_CONVS; ++k) P.imp[s].conv[k].gw_slabs = conv_wgrad_split(P.imp[s].conv[k], P.Bb);
+}
+
+// Phase 5: the workspace map.  Placement only, and the order is the layout: every offset depends on it.
+struct RegionCursor {
+    Plan& P;
     int64_t off = 0;  // floats
-    auto region = [&](const std::string& name, int64_t floats) {
+    int64_t operator()(const std::string& name, int64_t floats) {
         int64_t o = off;
         floats = (floats + 63) / 64 * 64;  // 256-B granules
         P.regions.push_back({name, {o * 4, floats * 4}});
         off += floats;
         return o;
-    };
-    P.da_floats = 0;
-    P.slab_floats = 0;
-    for (int i = 0; i < nl; ++i) {
+    }
+};
+
+// per layer: act, z, dz, red, gw; then every hidden layer's partial sums
+static inline void place_layer_regions(Plan& P, RegionCursor& region) {
+    for (int i = 0; i < P.n_layers; ++i) {
         Layer& l = P.L[i];
         l.act_off = l.z_off = l.dz_off = l.part_off = -1;
-        l.dgi_tiles = 0;
-        if (l.kind == 0 && i > 0 && l.ksz % l.stride == 0 && l.cout_p <= 64 && l.cin_p <= 64) {
-            auto tiles_of = [&](int tile_pix) {
-                int tiles = 0;
-                for (int c = 0; c < l.stride * l.stride; ++c) {
-                    int cy = c / l.stride, cx = c % l.stride;
-                    int Ha = (l.hin - cy + l.stride - 1) / l.stride, Wb = (l.win - cx + l.stride - 1) / l.stride;
-                    tiles += ceil_div(Ha * Wb, tile_pix);
-                }
-                return tiles;
-            };
-            // One four-wave workgroup per CU cannot hide its own latencies (round 4, stamps_dgrad.txt: a K step of 384 MFMA
-            // cycles takes 1 080), and half tiles make the conv2 data gradient of c2 7 us shorter (26.2 -> 18.9) -- but they fill
-            // the image and read the weight fragments twice, and in the step that CU time is taken from the kernels of the other
-            // queue (ab_tile64_c2.txt: the step is 3.7 % SLOWER at B = 256; at B = 32, where the chip is
-            // mostly empty either way, +0.2 %: noise).  Off in the product; -DISDQN_DGRAD_TILE64_BELOW=<workgroups> builds them.
-#if !defined(ISDQN_DGRAD_TILE64_BELOW)
-#define ISDQN_DGRAD_TILE64_BELOW 0
-#endif
-            l.dgi_tile_pix = P.Bb * tiles_of(128) < ISDQN_DGRAD_TILE64_BELOW ? 64 : 128;
-            l.dgi_tiles = tiles_of(l.dgi_tile_pix);
-        }
         if (!l.is_head) {
             l.act_off = region(std::string("act/") + l.name, (int64_t)P.N2 * l.out_elems_p);
             l.z_off = region(std::string("z/") + l.name, (int64_t)P.Bb * l.out_elems_p);
             l.dz_off = region(std::string("dz/") + l.name, (int64_t)P.Bb * l.out_elems_p);
-            l.part_rows = LN_MAX_BLOCKS;
-            if (l.kind == 1 && P.B > l.part_rows) l.part_rows = P.B;  // head chain: one row per workgroup, as few as one transition each
-            l.part_off = -2;  // sized below, once the consumer layer's tiling is known
             l.red_off = region(std::string("red/") + l.name, 3 * (int64_t)l.out_p);
-        }
-        // (BatchNorm: the first convolution's data gradient is needed too -- the input BatchNorm's scale / bias gradient)
-        if ((i > 0 || (P.bn && l.kind == 0)) && (int64_t)P.Bb * l.in_elems_p > P.da_floats) P.da_floats = (int64_t)P.Bb * l.in_elems_p;
-        // weight-gradient slabs: split the contraction (online pixels / batch rows) over workgroups
-        if (l.kind == 0) {
-            int tiles_n = ceil_div(l.K, 64);
-            int ksteps = ceil_div(P.Bb * l.npix, 32);
-            int s = 256 / tiles_n;
-            if (s < 1) s = 1;
-            if (s > ksteps) s = ksteps;
-            l.gw_slabs = s;
-            // image-resident variant: column groups of 64*NTW k' columns x groups of G images ~ 256 workgroups
-            l.wgi_ntw = 0;
-            if (l.K % 64 == 0 && (l.is_u8 || l.cin_p % 16 == 0)) {
-                int ntw = (l.K % 256 == 0) ? 4 : (l.K % 192 == 0) ? 3 : (l.K % 128 == 0) ? 2 : 0;
-                if (l.K == 512) ntw = 2;
-                // 64 output channels and K <= 576: one workgroup owns every k' column (8 or 9 column tiles per
-                // wave), so each image pair is staged into LDS exactly once instead of once per column group
-                const bool wide = l.cout_p == 64 && !l.is_u8 && (l.K == 512 || l.K == 576);
-                if (wide) ntw = l.K / 64;
-                if (ntw) {
-                    int ncg = l.K / (64 * ntw);
-                    int G = (P.Bb * ncg + 255) / 256;
-                    // two images per workgroup at the headline batch (measured best, 1: 2681, 2: 2806 steps/s: 128 workgroups share
-                    // the CUs with the data-gradient chain); larger batches keep at least one workgroup per CU instead of 128
-                    // workgroups of 8 images (c5: conv2 / conv1 weight gradients 74 / 66 us on half the chip)
-                    if (wide) G = (P.Bb + 127) / 128;
-#if !defined(ISDQN_WGRAD_G128)
-                    if (wide && G > 2) G = std::max(2, (P.Bb + 255) / 256);
-#endif
-                    if (G < 1) G = 1;
-                    l.wgi_ntw = ntw;
-                    l.wgi_G = G;
-                    l.wgi_groups = ceil_div(P.Bb, G);
-                    if (l.wgi_groups > l.gw_slabs) l.gw_slabs = l.wgi_groups;
-                }
-            }
-        } else if (l.kind == 1) {
-            int tiles = ceil_div(l.out_p, 128) * ceil_div(l.in_p, 128);
-            int ksteps = ceil_div(P.Bb, 32);
-            int s = tiles >= 128 ? 1 : 256 / tiles;
-            if (s > ksteps) s = ksteps;
-            if (s < 1) s = 1;
-            l.gw_slabs = s;
-            // forward split-K slabs
-            // ~512 workgroups (two per CU hide each other's operand latency).  A GEMM of few 128 x 128 tiles gets there with
-            // 128 x 64 tiles and half the split-K slabs: same time at the headline size, 32 MB less slab traffic per step.
-            int ft = ceil_div(P.N2, 128) * ceil_div(l.out_p, 128);
-            l.fwd_narrow = ft <= 64 && !l.in_unpadded_ld && l.out_p % 64 == 0;
-            if (l.fwd_narrow) ft = ceil_div(P.N2, 128) * ceil_div(l.out_p, 64);
-            int fs = ft >= 256 ? 1 : 512 / ft;
-            int fk = ceil_div(l.K, 32);
-#if defined(ISDQN_DEV)
-            if (const char* e = getenv("ISDQN_FWD_SPLITS")) fs = atoi(e);  // development: split-K factor of the forward GEMM
-#endif
-            if (fs > fk) fs = fk;
-            if (fs < 1) fs = 1;
-            l.fwd_splits = fs;
-            int64_t need = (int64_t)fs * P.N2 * l.out_p;
-            if (need > P.slab_floats) P.slab_floats = need;
         }
         l.gw_off = region(std::string("gw/") + l.name, (int64_t)l.gw_slabs * l.w_size);
     }
-    for (int i = 0; i < nl; ++i) {
+    for (int i = 0; i < P.n_layers; ++i) {
         Layer& l = P.L[i];
-        if (l.is_head) continue;
-        if (i + 1 < nl && P.L[i + 1].dgi_tiles > 0 && P.B * P.L[i + 1].dgi_tiles > l.part_rows)
-            l.part_rows = P.B * P.L[i + 1].dgi_tiles;
-        // conv layer under the first dense layer: the fused dense data-gradient + LN backward emits one partial
-        // row per (64-sample tile, pixel)
-        if (l.kind != 1 && i + 1 < nl && P.L[i + 1].kind == 1 && l.cout_p == 64 && ceil_div(P.B, 64) * l.npix > l.part_rows)
-            l.part_rows = ceil_div(P.B, 64) * l.npix;
-        l.part_off = region(std::string("part/") + l.name, (int64_t)l.part_rows * 3 * l.out_p);
+        if (!l.is_head) l.part_off = region(std::string("part/") + l.name, (int64_t)l.part_rows * 3 * l.out_p);
     }
-    if (cfg->arch == ISDQN_ARCH_IMPALA) {
-        for (int s = 0; s < IMP_STACKS; ++s) {
-            ImpalaStack& S = P.imp[s];
-            const std::string pre = "imp/s" + std::to_string(s) + "/";
-            const int64_t big = (int64_t)S.H * S.W, small = (int64_t)S.Hp * S.Wp;
-            S.xin_off = region(pre + "xin", P.N2 * big * S.cin_p);
-            S.z0_off = region(pre + "z0", P.N2 * big * S.C_p);
-            S.arg_off = region(pre + "argmax", (P.N2 * small * S.C_p + 3) / 4);
-            for (int k = 0; k < 3; ++k) S.r_off[k] = region(pre + "r" + std::to_string(k), P.N2 * small * S.C_p);
-            for (int b = 0; b < 2; ++b) {
-                S.a1_off[b] = region(pre + "a1_" + std::to_string(b), P.N2 * small * S.C_p);
-                S.a2_off[b] = region(pre + "a2_" + std::to_string(b), P.N2 * small * S.C_p);
-                S.lnpart_off[b] = region(pre + "lnpart" + std::to_string(b), (int64_t)LN_MAX_BLOCKS * 2 * S.C_p);
-            }
-            S.zt_off = region(pre + "zt", P.N2 * small * S.C_p);
-            S.dr_off = region(pre + "dr", P.Bb * small * S.C_p);
-            S.da_off = region(pre + "da", P.Bb * std::max(big * S.cin_p, small * S.C_p));
-            S.dzs_off = region(pre + "dzs", P.Bb * big * S.C_p);
-            S.dz0_off = region(pre + "dz0", P.Bb * big * S.C_p);
-            for (int k = 0; k < IMP_CONVS; ++k) {
-                Layer& c = S.conv[k];
-                S.bpart_off[k] = region(pre + "bpart" + std::to_string(k), (int64_t)LN_MAX_BLOCKS * S.C_p);
-                int tiles_n = ceil_div(c.K, 64);
-                int ksteps = ceil_div(P.Bb * c.npix, 32);
-                int sp = 256 / tiles_n;
-                if (sp < 1) sp = 1;
-                if (sp > ksteps) sp = ksteps;
-                c.gw_slabs = sp;
-                c.gw_off = region(pre + "gw" + std::to_string(k), (int64_t)c.gw_slabs * c.w_size);
-            }
+}
+
+static inline void place_impala_regions(Plan& P, RegionCursor& region) {
+    for (int s = 0; s < IMP_STACKS; ++s) {
+        ImpalaStack& S = P.imp[s];
+        const std::string pre = "imp/s" + std::to_string(s) + "/";
+        const int64_t big = (int64_t)S.H * S.W, small = (int64_t)S.Hp * S.Wp;
+        S.xin_off = region(pre + "xin", P.N2 * big * S.cin_p);
+        S.z0_off = region(pre + "z0", P.N2 * big * S.C_p);
+        S.arg_off = region(pre + "argmax", (P.N2 * small * S.C_p + 3) / 4);
+        for (int k = 0; k < 3; ++k) S.r_off[k] = region(pre + "r" + std::to_string(k), P.N2 * small * S.C_p);
+        for (int b = 0; b < 2; ++b) {
+            S.a1_off[b] = region(pre + "a1_" + std::to_string(b), P.N2 * small * S.C_p);
+            S.a2_off[b] = region(pre + "a2_" + std::to_string(b), P.N2 * small * S.C_p);
+            S.lnpart_off[b] = region(pre + "lnpart" + std::to_string(b), (int64_t)LN_MAX_BLOCKS * 2 * S.C_p);
+        }
+        S.zt_off = region(pre + "zt", P.N2 * small * S.C_p);
+        S.dr_off = region(pre + "dr", P.Bb * small * S.C_p);
+        S.da_off = region(pre + "da", P.Bb * std::max(big * S.cin_p, small * S.C_p));
+        S.dzs_off = region(pre + "dzs", P.Bb * big * S.C_p);
+        S.dz0_off = region(pre + "dz0", P.Bb * big * S.C_p);
+        for (int k = 0; k < IMP_CONVS; ++k) {
+            Layer& c = S.conv[k];
+            S.bpart_off[k] = region(pre + "bpart" + std::to_string(k), (int64_t)LN_MAX_BLOCKS * S.C_p);
+            c.gw_off = region(pre + "gw" + std::to_string(k), (int64_t)c.gw_slabs * c.w_size);
         }
     }
+}
+
+static inline void place_bn_regions(Plan& P, RegionCursor& region) {
     for (int s = 0; s < P.n_bn; ++s) {
         BnSite& b = P.bns[s];
         const std::string pre = std::string("bn/") + b.name + "/";
@@ -584,6 +620,13 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
         b.s1_off = region(pre + "dbias", b.G_p);
         b.s2_off = region(pre + "dscale", b.G_p);
     }
+}
+
+static inline void plan_workspace(const isdqn_net_config* cfg, Plan& P) {
+    RegionCursor region{P};
+    place_layer_regions(P, region);
+    if (cfg->arch == ISDQN_ARCH_IMPALA) place_impala_regions(P, region);
+    place_bn_regions(P, region);
     if (P.bn && cfg->arch == ISDQN_ARCH_FC)  // concat(state, next_state) as one matrix (the first layer's weight gradient contracts over all 2B rows)
         P.x0_off = region("bn/x0", (int64_t)P.N2 * P.L[0].in_f);
     P.q_off = region("q", (int64_t)P.N2 * P.nha_p);
@@ -603,9 +646,6 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     // (appended: a configuration without the option keeps every offset and the total it had.  The plan does not know whether the
     // caller will pass target parameters, so the regions exist with the option whatever the form: only the *_target entry points
     // and grad_on_batch with target_params read them, iS-DQN / TF-DQN learn steps leave them untouched)
-    P.double_q = cfg->double_q;
-    P.munchausen = cfg->munchausen_tau > 0.f;
-    P.qt_rows = P.munchausen ? P.N2 : P.double_q ? P.B : 0;
     P.qt_off = P.qt_rows ? region("q_target", (int64_t)P.qt_rows * P.nha_p) : -1;
     P.logits_t_off = (P.qt_rows && P.head_nb > 0) ? region("logits_target", (int64_t)P.qt_rows * P.nlog_p) : -1;
     P.out_t_off = P.head_nb > 0 ? P.logits_t_off : P.qt_off;
@@ -616,10 +656,31 @@ static inline int build_plan_uncached(const isdqn_net_config* cfg, Plan& P) {
     P.dbh_raw_off = P.dueling ? region("dbh_raw", P.raw_p) : -1;
     // (gradient clipping: likewise appended.  A workgroup of the reduction covers 64 elements of one tensor; a layer has at most four
     // tensors -- kernel, bias, LayerNorm scale and bias -- each of which may end in a partly filled workgroup)
-    P.gc_part_cap = P.grad_clip ? (P.n_params + 63) / 64 + 4 * (int64_t)nl : 0;
+    P.gc_part_cap = P.grad_clip ? (P.n_params + 63) / 64 + 4 * (int64_t)P.n_layers : 0;
     P.gc_part_off = P.grad_clip ? region("grad_clip_partials", 2 * P.gc_part_cap) : -1;
     P.gc_off = P.grad_clip ? region("grad_clip", 4) : -1;
-    P.ws_bytes = off * 4;
+    P.ws_bytes = region.off * 4;
+}
+
+// The plan of a configuration: a pure function of *cfg.  P starts value-initialised, so a field the configuration does not use
+// holds 0 (-1 where its comment promises -1); on a refusal P is unspecified.
+static inline int build_plan(const isdqn_net_config* cfg, Plan& P) {
+    P = Plan{};
+    int rc = check_options(cfg);
+    if (rc) return rc;
+    rc = plan_heads(cfg, P);
+    if (rc) return rc;
+    ParamCursor cur;
+    DenseInput in{};
+    rc = cfg->arch == ISDQN_ARCH_CNN ? plan_cnn_torso(cfg, P, cur, in)
+         : cfg->arch == ISDQN_ARCH_IMPALA ? plan_impala_torso(cfg, P, cur, in)
+                                          : plan_fc_input(cfg, in);
+    if (rc) return rc;
+    rc = plan_dense_tail(cfg, P, cur, in);
+    if (rc) return rc;
+    place_batch_stats(P, cur);
+    plan_tiling(cfg, P);
+    plan_workspace(cfg, P);
     return ISDQN_OK;
 }
 
@@ -636,13 +697,73 @@ static inline const Plan* cached_plan(const isdqn_net_config* cfg, int* rc_out) 
     Slot& s = slots[next];
     next = (next + 1) % 4;
     s.used = false;
-    int rc = build_plan_uncached(cfg, s.plan);
+    int rc = build_plan(cfg, s.plan);
     if (rc) { *rc_out = rc; return nullptr; }
     memcpy(&s.cfg, cfg, sizeof(*cfg));
     s.used = true;
     return &s.plan;
 }
 
-static inline int build_plan(const isdqn_net_config* cfg, Plan& P) { return build_plan_uncached(cfg, P); }
+// Every tensor of the parameter buffer in the order of the layer list, then the BatchNorm sites: visit(const isdqn_tensor_info&).
+// ndim is the length of `flax_shape`; the rest of the two arrays stays 0.
+static inline isdqn_tensor_info tensor_info(const char* mod, const char* leaf, int64_t off, int64_t size, int kind, int layer,
+                                            std::initializer_list<int> flax_shape, std::initializer_list<int> dims) {
+    isdqn_tensor_info t;
+    memset(&t, 0, sizeof(t));
+    snprintf(t.name, sizeof(t.name), "%s/%s", mod, leaf);
+    t.offset = off; t.size = size; t.kind = kind; t.layer = layer; t.ndim = (int)flax_shape.size();
+    std::copy(flax_shape.begin(), flax_shape.end(), t.flax_shape);
+    std::copy(dims.begin(), dims.end(), t.dims);
+    return t;
+}
+
+template <class Visit>
+static inline void for_each_param_tensor(const Plan& P, Visit&& visit) {
+    auto layer_norm = [&](const char* mod, int64_t g_off, int64_t be_off, int width, int width_p, int layer) {
+        visit(tensor_info(mod, "scale", g_off, width_p, 3, layer, {width}, {width_p}));
+        visit(tensor_info(mod, "bias", be_off, width_p, 4, layer, {width}, {width_p}));
+    };
+    for (int i = 0; i < P.n_layers; ++i) {
+        const Layer& l = P.L[i];
+        if (l.kind == 2) {  // impala torso: Stack_s / {Conv_k, LayerNorm_b} (Flax nests the Stack's modules: "Stack_0/Conv_1/kernel")
+            for (int s = 0; s < IMP_STACKS; ++s) {
+                const ImpalaStack& S = P.imp[s];
+                char mod[40];
+                for (int k = 0; k < IMP_CONVS; ++k) {
+                    const Layer& c = S.conv[k];
+                    if (k >= 1 && (k & 1) && S.ln_g[(k - 1) / 2] >= 0) {  // LayerNorm_b sits in front of Conv_{1+2b}
+                        const int b = (k - 1) / 2;
+                        snprintf(mod, sizeof(mod), "Stack_%d/LayerNorm_%d", s, b);
+                        layer_norm(mod, S.ln_g[b], S.ln_b[b], S.C, S.C_p, i);
+                    }
+                    snprintf(mod, sizeof(mod), "Stack_%d/%s", s, c.name);
+                    visit(tensor_info(mod, "kernel", c.w_off, c.w_size, 0, i, {3, 3, c.cin, c.cout}, {c.cout_p, c.taps, c.cin_p}));
+                    visit(tensor_info(mod, "bias", c.b_off, c.out_p, 2, i, {c.cout}, {c.out_p}));
+                }
+            }
+        } else {
+            if (l.kind == 0)
+                visit(tensor_info(l.name, "kernel", l.w_off, l.w_size, 0, i, {l.ksz, l.ksz, l.cin, l.cout},
+                                  {l.cout_p, l.is_u8 ? l.cin : l.taps, l.is_u8 ? 64 : l.cin_p}));
+            else
+                visit(tensor_info(l.name, "kernel", l.w_off, l.w_size, 1, i, {l.in_f, l.out_f}, {l.out_p, l.in_p}));
+            visit(tensor_info(l.name, "bias", l.b_off, l.out_p, 2, i, {l.out_f}, {l.out_p}));
+        }
+        if (l.has_ln) layer_norm(l.ln_name, l.g_off, l.be_off, l.out_f, l.out_p, i);
+    }
+    for (int s = 0; s < P.n_bn; ++s) {  // BatchNorm_s: scale / bias ("params"), mean / var ("batch_stats")
+        const BnSite& b = P.bns[s];
+        int H, W;
+        if (b.layer == -1) { H = P.L[0].hin; W = P.L[0].win; }
+        else if (b.layer <= -2) { H = P.imp[(-2 - b.layer) / 2].Hp; W = P.imp[(-2 - b.layer) / 2].Wp; }
+        else { H = P.L[b.layer].hout; W = P.L[b.layer].wout; }
+        const int64_t offs[4] = {b.scale_off, b.bias_off, b.mean_off, b.var_off};
+        static const char* const leaves[4] = {"scale", "bias", "mean", "var"};
+        for (int k = 0; k < 4; ++k) {
+            if (b.spatial) visit(tensor_info(b.name, leaves[k], offs[k], b.G_p, 5 + k, b.layer, {H, W}, {b.G, b.P, b.C, b.Cp}));
+            else visit(tensor_info(b.name, leaves[k], offs[k], b.G_p, 5 + k, b.layer, {b.P * b.C}, {b.G, b.P, b.C, b.Cp}));
+        }
+    }
+}
 
 }  // namespace isdqn
