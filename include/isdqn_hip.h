@@ -599,6 +599,69 @@ int isdqn_net_redo(const isdqn_net_config* cfg, float* params, float* adam_m, fl
                    const uint8_t* frames, int64_t frame_stride, const int32_t* frame_ids, const float* obs, int32_t n_rows,
                    float tau, float* scores_out, int32_t* mask_out, int32_t* n_recycled_out, void* workspace, void* stream);
 
+/* NoisyNet exploration: factorised noisy Dense layers (Fortunato et al., "Noisy Networks for Exploration", ICLR 2018; the reference has
+ * no counterpart -- it explores with the epsilon schedule).  Built BESIDE the plan: no field of isdqn_net_config, no workspace region and no
+ * launch of any existing entry point belongs to it; the caller owns the new buffers, and forward / loss / gradient run unchanged on a
+ * composed "effective" parameter buffer.  On the device, stream-ordered, without a host synchronisation and without atomics.  The cost
+ * of the extra passes over the parameters (one compose, one write and one read of the reduced gradient, one optimizer pass) is recorded
+ * in docs/NOTEBOOK.md, not here.  THE definition:
+ * Noisy layers: every Dense layer of the network, the hidden ones and the head (Fortunato's and Rainbow's choice).  Convolutions, LayerNorm
+ * scale and bias are not noisy.
+ * Buffers (device, caller-owned; "same layout" = isdqn_net_param_layout's, n_param_floats floats):
+ *   mu       the ordinary parameter buffer;
+ *   sigma    same layout.  Only the positions of Dense kernels and Dense biases mean anything; every other position is +0.0f and stays
+ *            +0.0f, so that isdqn_net_shift_params and the tensor table work on sigma as they do on mu;
+ *   m_sigma, v_sigma   Adam moments of sigma, same layout;     eff   the composed parameters, same layout;
+ *   grad     n_param_floats floats: the reduced gradient of the step (the caller zeroes it once);
+ *   noise    for noisy layer l in network order ein_l[in_p] then eout_l[out_p] -- the plan's internal widths, both multiples of 8 -- already
+ *            transformed by f, the layers concatenated; isdqn_noisy_layout returns offsets[l] (of ein_l; eout_l follows at + in_widths[l]),
+ *            the widths and the total.  ein is indexed by the INTERNAL input column (behind a conv torso: pixel * c_pad + channel);
+ *   noise_count   one device int64.
+ * Noise: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; round: (hi0, lo0) = M0 * c0,
+ * (hi1, lo1) = M1 * c2, c <- {hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0}, then the key is bumped).  Element j of vector v (0 = in, 1 = out) of
+ * noisy layer l: x = Philox(ctr = {j, (stream_id << 16) | (2 l + v), lo32(count), hi32(count)}, key = {lo32(seed), hi32(seed)}), count the
+ * value of *noise_count when the kernel runs, stream_id 0 = online, 1 = target.  u1 = ((x0 >> 8) + 1/2) 2^-24 in (0, 1), u2 = (x1 >> 8) 2^-24;
+ * z = sqrtf(-2 ln u1) * cospif(2 u2) with the full-precision device functions; the stored value is f(z) = copysignf(sqrtf(fabsf(z)), z).
+ * u2 is exact in fp32; u1 has 25 significant bits from 1/2 on, so there ln u1 is evaluated as log1pf(-(1 - u1)), whose argument is exact
+ * (below 1/2: logf(u1), exact argument).  A value depends on (seed, count, stream_id, l, v, j) alone, never on another layer's width.
+ * isdqn_noisy_sample is one launch over all vectors and ends by storing count + 1: one thread, an ordinary store, in a launch of its
+ * own behind the one that read the counter -- a captured graph advances the noise without a second capture.
+ * Compose (isdqn_noisy_compose: one pass over the parameters), in fp32, in this order, uncontracted:
+ *   Dense kernel element [o][i] at w_off + o * in_p + i:   n = eout[o] * ein[i],  t = sigma * n,  eff = mu + t
+ *   Dense bias [o]:                                        eff = mu + sigma_b[o] * eout[o]
+ *   every other element:                                   eff = mu, bit for bit
+ * With `noise` all zero eff == mu bit for bit wherever sigma is finite: the evaluation network, selected by zeroing the noise buffer.
+ * With a workspace the call also writes the weight mirror of eff, so that a following call on eff may pass ISDQN_BATCH_MIRROR_CURRENT
+ * (acting: sample, compose with the workspace, isdqn_net_best_actions(..., eff, ..., ISDQN_BATCH_MIRROR_CURRENT, ...)).  NULL: eff alone.
+ * Learn step (isdqn_noisy_learn_on_batch): compose eff and its mirror; the full gradient pass of isdqn_net_grad_on_batch on eff (n_pairs
+ * = 0; eff_target != NULL: the DQN form, a second composed buffer the caller built from the target's mu, sigma and a stream_id = 1 draw)
+ * -> grad = g, the reduced gradient w.r.t. eff exactly as a plain network holding eff would have fed it to Adam, masked under dueling as
+ * grad_on_batch masks it; then one optimizer pass:
+ *     g_mu = g;    g_sigma = fl32(g * n) on Dense kernels (n as in compose),  fl32(g * eout[o]) on Dense biases;  none elsewhere
+ * Adam (the element update of learn_on_batch, the same learning_rate / adam_b1 / adam_b2 / adam_eps and the ONE shared adam_count,
+ * incremented once) updates mu from g_mu everywhere and sigma from g_sigma on the Dense positions.  One draw serves both halves of the
+ * concat(state, next_state) forward: iS-DQN and TF-DQN run one forward on one set of parameters -- a deviation from Fortunato's DQN,
+ * which draws separate noise for the target forward (the *_target form does).  losses, losses_accum, q_values, targets, priorities,
+ * priorities_ready, loss_weights and every target / loss option of cfg behave exactly as in isdqn_net_learn_on_batch on the composed
+ * network.  Padding lanes and the structural zeros of a dueling head carry g = 0: their sigma stays +0.0f when it starts there.  The
+ * weight mirror is NOT current for mu afterwards (every noisy call composes first).
+ * ISDQN_ERR_UNSUPPORTED from all four entry points, behind the plan's own checks and in this order: batch_norm (running statistics
+ * would be committed into eff), arch impala, max_grad_norm > 0 (the norm must cover g_sigma too: a follow-up).  ISDQN_ERR_ARG: a NULL
+ * pointer other than workspace (compose) / eff_target / the optional outputs of learn_on_batch; stream_id outside {0, 1}.
+ * isdqn_noisy_layout: host arithmetic on the plan.  *n_layers and *n_noise_floats are always written; offsets / in_widths / out_widths may
+ * all be NULL (a query of the count and the total), otherwise max_layers must be at least *n_layers -- a smaller one is ISDQN_ERR_ARG,
+ * nothing is truncated silently.  It refuses what the other three refuse, max_grad_norm > 0 included: a layout is handed out only for a
+ * configuration the noisy step runs. */
+int isdqn_noisy_layout(const isdqn_net_config* cfg, int32_t* n_layers, int64_t* offsets, int32_t* in_widths, int32_t* out_widths,
+                       int32_t max_layers, int64_t* n_noise_floats);
+int isdqn_noisy_sample(const isdqn_net_config* cfg, uint64_t seed, int32_t stream_id, int64_t* noise_count, float* noise, void* stream);
+int isdqn_noisy_compose(const isdqn_net_config* cfg, const float* mu, const float* sigma, const float* noise, float* eff, void* workspace,
+                        void* stream);
+int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu, float* sigma, float* m_mu, float* v_mu, float* m_sigma,
+                               float* v_sigma, int32_t* adam_count, const float* noise, float* eff, const float* eff_target, float* grad,
+                               const isdqn_batch* batch, float* losses, float* losses_accum, float* q_values, float* targets,
+                               double* priorities, void* workspace, void* stream);
+
 /* Engine self-test: C[M][N] = A . B on the MFMA tile engine for every operand-layout
  * combination (a_tr/b_tr: 0 = operand stored [rows][K], 1 = stored [K][rows]).  Test hook. */
 int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int32_t a_tr,

@@ -2264,7 +2264,9 @@ static int learn_loss(const LearnCtx& c) {
     // the target network's own head output ("q_target" / "logits_target": next states; Munchausen: states, then next states)
     const bool tnet = (c.double_q || c.munchausen) && c.target_params != nullptr;
     if (!c.hc_S) {
-        int rc = loss_and_finalize(c.P, c.cfg, c.ws, c.batch, c.K, c.on0, c.tg0, c.learn, (c.learn && c.update) ? c.adam_count : nullptr, c.qv, c.tg,
+        // (adam_count in a gradient-only pass: null from grad_on_batch; the noisy learn step hands its own, because its optimizer
+        // launch follows the pass and reads the step count's bias corrections from the same place)
+        int rc = loss_and_finalize(c.P, c.cfg, c.ws, c.batch, c.K, c.on0, c.tg0, c.learn, c.learn ? c.adam_count : nullptr, c.qv, c.tg,
                                    c.priorities, c.losses, c.loss_accum, c.st, c.double_q,
                                    tnet ? c.ws + c.P.out_t_off + (c.munchausen ? (int64_t)c.B * c.P.nlog_p : 0) : nullptr,
                                    (tnet && c.munchausen) ? c.ws + c.P.out_t_off : nullptr);
@@ -3051,6 +3053,152 @@ extern "C" int isdqn_net_redo(const isdqn_net_config* cfg, float* params, float*
         off += l.out_f;
     }
     return refresh_mirror(P, params, ws, st);
+}
+
+// ---- noisy Dense layers (noisy.h; include/isdqn_hip.h, isdqn_noisy_layout) ----
+namespace isdqn {
+#include "noisy.h"  // (behind every kernel of the learn step)
+}  // namespace isdqn
+// the plan behind its own checks, then the three refusals of the noisy entry points in their documented order
+static const Plan* noisy_plan(const isdqn_net_config* cfg, int* rc) {
+    const Plan* Pp = cached_plan(cfg, rc);
+    if (!Pp) return nullptr;
+    auto refuse = [&](const char* msg) -> const Plan* {
+        set_last_error("%s", msg);
+        *rc = ISDQN_ERR_UNSUPPORTED;
+        return nullptr;
+    };
+    if (cfg->batch_norm) return refuse("noisy layers are not built for BatchNorm networks: running statistics would be committed into the composed parameters");
+    if (cfg->arch == ISDQN_ARCH_IMPALA) return refuse("noisy layers are not built for the impala torso");
+    if (cfg->max_grad_norm > 0.f)
+        return refuse("noisy layers with max_grad_norm > 0 are a follow-up: the global norm must cover the gradient of sigma too");
+    return Pp;
+}
+// noise layout: per noisy layer ein[in_p] then eout[out_p], the layers concatenated in network order
+static int64_t noisy_tables(const Plan& P, NoisyTable* tab, NoisyVecTable* vecs) {
+    int64_t off = 0;
+    int l_noisy = 0;
+    if (tab) tab->n = 0;
+    if (vecs) { vecs->n = 0; vecs->total_blocks = 0; }
+    for (int i = 0; i < P.n_layers; ++i) {
+        const Layer& l = P.L[i];
+        if (l.kind != 1) continue;
+        const int64_t ein = off, eout = off + l.in_p;
+        if (tab) {
+            tab->e[tab->n++] = NoisyEntry{l.w_off, l.w_size, ein, eout, l.in_p, FastDiv((uint32_t)l.in_p)};
+            tab->e[tab->n++] = NoisyEntry{l.b_off, (int64_t)l.out_p, ein, eout, 0, FastDiv()};
+        }
+        if (vecs) {
+            const int widths[2] = {l.in_p, l.out_p};
+            const int64_t offs[2] = {ein, eout};
+            for (int v = 0; v < 2; ++v) {
+                vecs->v[vecs->n++] = NoisyVec{offs[v], widths[v], 2 * l_noisy + v, vecs->total_blocks, 0};
+                vecs->total_blocks += ceil_div(widths[v], NOISY_THREADS);
+            }
+        }
+        off += l.in_p + l.out_p;
+        ++l_noisy;
+    }
+    return off;
+}
+
+extern "C" int isdqn_noisy_layout(const isdqn_net_config* cfg, int32_t* n_layers, int64_t* offsets, int32_t* in_widths, int32_t* out_widths,
+                                  int32_t max_layers, int64_t* n_noise_floats) {
+    int rc;
+    const Plan* Pp = noisy_plan(cfg, &rc);
+    if (!Pp) return rc;
+    int n = 0;
+    int64_t total = 0;
+    for (int i = 0; i < Pp->n_layers; ++i)
+        if (Pp->L[i].kind == 1) {
+            ++n;
+            total += Pp->L[i].in_p + Pp->L[i].out_p;
+        }
+    if (n_layers) *n_layers = n;
+    if (n_noise_floats) *n_noise_floats = total;
+    if (!offsets && !in_widths && !out_widths) return ISDQN_OK;  // a query of the count and the total
+    // (the arrays must hold every layer: nothing is truncated silently)
+    ISDQN_REQUIRE(max_layers >= n, ISDQN_ERR_ARG, "isdqn_noisy_layout: max_layers is smaller than the number of noisy layers (returned in *n_layers)");
+    int k = 0;
+    int64_t off = 0;
+    for (int i = 0; i < Pp->n_layers; ++i) {
+        const Layer& l = Pp->L[i];
+        if (l.kind != 1) continue;
+        if (offsets) offsets[k] = off;
+        if (in_widths) in_widths[k] = l.in_p;
+        if (out_widths) out_widths[k] = l.out_p;
+        off += l.in_p + l.out_p;
+        ++k;
+    }
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_noisy_sample(const isdqn_net_config* cfg, uint64_t seed, int32_t stream_id, int64_t* noise_count, float* noise, void* stream) {
+    int rc;
+    const Plan* Pp = noisy_plan(cfg, &rc);
+    if (!Pp) return rc;
+    ISDQN_REQUIRE(noise_count != nullptr && noise != nullptr, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(stream_id == 0 || stream_id == 1, ISDQN_ERR_ARG, "stream_id must be 0 (online) or 1 (target)");
+    NoisyVecTable vecs;
+    noisy_tables(*Pp, nullptr, &vecs);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(noisy_sample_kernel, dim3(vecs.total_blocks), dim3(NOISY_THREADS), 0, st, vecs, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       (uint32_t)stream_id, (const int64_t*)noise_count, noise);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(noisy_advance_kernel, dim3(1), dim3(64), 0, st, noise_count);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
+static int noisy_compose(const Plan& P, const NoisyTable& tab, const float* mu, const float* sigma, const float* noise, float* eff, float* ws,
+                         hipStream_t st) {
+    const int64_t quads = P.n_params / 4;  // (every tensor size is a multiple of 8)
+    hipLaunchKernelGGL(noisy_compose_kernel, dim3((unsigned)((quads + NOISY_THREADS - 1) / NOISY_THREADS)), dim3(NOISY_THREADS), 0, st, tab, mu, sigma,
+                       noise, eff, ws ? ws + P.wsplit_off : nullptr, P.n_params);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_noisy_compose(const isdqn_net_config* cfg, const float* mu, const float* sigma, const float* noise, float* eff,
+                                   void* workspace, void* stream) {
+    int rc;
+    const Plan* Pp = noisy_plan(cfg, &rc);
+    if (!Pp) return rc;
+    ISDQN_REQUIRE(mu && sigma && noise && eff, ISDQN_ERR_ARG, "null pointer");
+    NoisyTable tab;
+    noisy_tables(*Pp, &tab, nullptr);
+    return noisy_compose(*Pp, tab, mu, sigma, noise, eff, (float*)workspace, (hipStream_t)stream);
+}
+
+extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu, float* sigma, float* m_mu, float* v_mu, float* m_sigma,
+                                          float* v_sigma, int32_t* adam_count, const float* noise, float* eff, const float* eff_target,
+                                          float* grad, const isdqn_batch* batch, float* losses, float* losses_accum, float* q_values,
+                                          float* targets, double* priorities, void* workspace, void* stream) {
+    int rc;
+    const Plan* Pp = noisy_plan(cfg, &rc);
+    if (!Pp) return rc;
+    const Plan& P = *Pp;
+    ISDQN_REQUIRE(mu && sigma && m_mu && v_mu && m_sigma && v_sigma && adam_count && noise && eff && grad && batch && workspace, ISDQN_ERR_ARG,
+                  "null pointer");
+    NoisyTable tab;
+    noisy_tables(P, &tab, nullptr);
+    float* ws = (float*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    rc = noisy_compose(P, tab, mu, sigma, noise, eff, ws, st);
+    if (rc) return rc;
+    // the full two-stream gradient pass on eff: its optimizer launches write the reduced gradient (masked under dueling) and update
+    // nothing; loss_finalize_kernel advances adam_count and leaves the bias corrections in the workspace, as in a plain learn step
+    isdqn_batch b = *batch;
+    b.flags |= ISDQN_BATCH_MIRROR_CURRENT;  // (compose wrote the mirror of eff; the *_target form rebuilds both mirrors itself)
+    rc = learn_or_loss(cfg, eff, nullptr, nullptr, adam_count, &b, losses, losses_accum, q_values, targets, priorities, workspace, stream, true, grad,
+                       eff_target, nullptr, false);
+    if (rc) return rc;
+    const int64_t quads = P.n_params / 4;
+    hipLaunchKernelGGL(noisy_adam_kernel, dim3((unsigned)((quads + NOISY_THREADS - 1) / NOISY_THREADS)), dim3(NOISY_THREADS), 0, st, tab, (const float*)grad,
+                       noise, mu, m_mu, v_mu, sigma, m_sigma, v_sigma, (const float*)(ws + P.adam_tab_off), cfg->learning_rate, cfg->adam_b1, cfg->adam_b2,
+                       cfg->adam_eps, P.n_params);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
 }
 
 extern "C" int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K,

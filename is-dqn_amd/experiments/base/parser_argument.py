@@ -55,6 +55,8 @@ _ENGINE = [
     ("-nq", "--n_quantiles", dict(type=int, default=32, help="Number of quantiles per action. Means nothing without -qr.")),
     ("-duel", "--dueling", dict(action="store_true", default=False, help="Dueling value / advantage heads (Wang et al. 2016): the last hidden layer of -f splits into two equal streams (-f 32 64 64 1024: two 512-wide ones), combined on the device as Q = V + A - mean(A), per bin with -hl and per quantile with -qr. Needs a hidden Dense layer of even width; not with -bn or -at impala.")),
     ("-gc", "--max_grad_norm", dict(type=float, default=0.0, help="Clip the gradient by its global norm in front of Adam (optax.clip_by_global_norm; the dueling, QR-DQN, C51 and Rainbow recipes use 10) and log grad_norm / grad_clipped_fraction at every target update; 0 = off, inf = measure and log only. Not with -bn or -at impala.")),
+    ("-noisy", "--noisy_nets", dict(action="store_true", default=False, help="NoisyNet exploration (Fortunato et al. 2018): every Dense layer, the head included, carries factorised Gaussian noise with a learned scale; acting and every learn step draw on the device. The epsilon flags keep their meaning: -ee 0 -ed 1 explores by noise alone, as Rainbow does. Not with -bn, -at impala, -gc > 0 or -redo.")),
+    ("-noisys", "--noisy_sigma0", dict(type=float, default=0.5, help="sigma_0 of the noisy layers: sigma starts at sigma_0 / sqrt(fan-in). Means nothing without -noisy.")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
     ("-mq", "--munchausen", dict(action="store_true", default=False, help="Munchausen targets (Vieillard et al. 2020): soft-value bootstrap plus the scaled, clipped log-policy of the taken action (the three flags below). Not with -dq.")),
     ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
@@ -190,6 +192,20 @@ def check_grad_clip(p: dict) -> None:
 def grad_clip_kwargs(p) -> dict:
     """The agents' max_grad_norm keyword from parsed parameters; without -gc the keywords are the ones they were before the flag existed."""
     return dict(max_grad_norm=float(p["max_grad_norm"])) if p.get("max_grad_norm") else {}
+
+
+# (-noisy and -noisys stay out of parameters.json like -duel)
+def check_noisy(p: dict) -> None:
+    """-noisy with -bn, -at impala, -gc > 0 or -redo fails before anything is written, with the agents' own message."""
+    if p.get("noisy_nets"):
+        from slimdqn._engine import check_noisy as check
+
+        check(True, p["architecture_type"], bool(p.get("batch_norm", False)), p.get("max_grad_norm", 0.0), p.get("redo_frequency", 0) != 0)
+
+
+def noisy_kwargs(p) -> dict:
+    """The agents' noisy keywords from parsed parameters; without -noisy the keywords are the ones they were before the flag existed."""
+    return dict(noisy=True, noisy_sigma0=float(p["noisy_sigma0"])) if p.get("noisy_nets") else {}
 
 
 # (-redo and -redot stay out of parameters.json like -hl and -qr)

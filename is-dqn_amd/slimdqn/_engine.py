@@ -113,6 +113,25 @@ def check_grad_clip(max_grad_norm, architecture_type, batch_norm=False) -> None:
             raise ValueError(GRAD_CLIP_BATCH_NORM_REFUSED)
 
 
+NOISY_BATCH_NORM_REFUSED = "noisy layers are not built for batch_norm: running statistics would be committed into the composed parameters (ISDQN_ERR_UNSUPPORTED)"
+NOISY_IMPALA_REFUSED = "noisy layers are not built for architecture_type 'impala' (ISDQN_ERR_UNSUPPORTED)"
+NOISY_GRAD_CLIP_REFUSED = "noisy layers with max_grad_norm > 0 are a follow-up: the global norm must cover the gradient of sigma too (ISDQN_ERR_UNSUPPORTED)"
+NOISY_REDO_REFUSED = "noisy layers and ReDo exclude each other: a recycled neuron would keep the sigma it had"
+
+
+def check_noisy(noisy, architecture_type, batch_norm=False, max_grad_norm=0.0, redo=False) -> None:
+    """The networks and options the library refuses to make noisy (in the library's order), said before anything is allocated or written."""
+    if noisy:
+        if batch_norm:
+            raise ValueError(NOISY_BATCH_NORM_REFUSED)
+        if architecture_type == "impala":
+            raise ValueError(NOISY_IMPALA_REFUSED)
+        if float(max_grad_norm) > 0.0:
+            raise ValueError(NOISY_GRAD_CLIP_REFUSED)
+        if redo:
+            raise ValueError(NOISY_REDO_REFUSED)
+
+
 def dueling_live_mask(n_hidden: int, n_heads: int, n_actions: int, width: int = 1) -> np.ndarray:
     """Which entries of the dueling head's Flax kernel (F, R) are weights (True) and which structural zeros (include/isdqn_hip.h,
     isdqn_net_config::dueling): column ((h * (A + 1)) + c) * width + j is a value column for c = A and reads the hidden units
@@ -154,7 +173,16 @@ class QNetEngine:
         categorical: bool = False,
         dueling: bool = False,
         max_grad_norm: float = 0.0,
+        noisy: bool = False,
+        noisy_sigma0: float = 0.5,
+        noisy_seed: int = 0,
     ):
+        """``noisy``: every Dense layer is a factorised noisy layer (include/isdqn_hip.h, isdqn_noisy_layout).  The engine then owns
+        ``sigma``, ``sigma_m``, ``sigma_v``, ``noise``, ``eff``, ``grad`` and ``noise_count``; ``init_params`` writes sigma =
+        noisy_sigma0 / sqrt(in_f) on the real elements of the Dense kernels and biases (in_f: the true fan-in; the live fan-in F / 2 on
+        a dueling head) and 0 elsewhere.  ``mu`` keeps the existing initialiser -- a deviation from the paper, which draws mu uniformly
+        from +-1 / sqrt(in_f).  Without ``noisy`` nothing new is allocated and every call takes exactly the code path it had."""
+        check_noisy(noisy, architecture_type, batch_norm, max_grad_norm)
         check_dueling(dueling, architecture_type, features, batch_norm)
         check_grad_clip(max_grad_norm, architecture_type, batch_norm)
         check_munchausen(double_q, munchausen_tau)
@@ -258,6 +286,113 @@ class QNetEngine:
             self.targets = torch.zeros(batch_size, K, dtype=torch.float32, device=self.device)
             self.priorities = torch.zeros(batch_size, dtype=torch.float64, device=self.device)
             self.action_out = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.noisy = bool(noisy)
+        if self.noisy:
+            self.noisy_sigma0, self.noisy_seed = float(noisy_sigma0), int(noisy_seed) & (2**64 - 1)
+            nl, total = ctypes.c_int32(), ctypes.c_int64()
+            offs, wi, wo = (ctypes.c_int64 * 16)(), (ctypes.c_int32 * 16)(), (ctypes.c_int32 * 16)()
+            _hip.check(self.lib.isdqn_noisy_layout(ctypes.byref(cfg), ctypes.byref(nl), offs, wi, wo, 16, ctypes.byref(total)), "isdqn_noisy_layout")
+            self.noise_layout = [(int(offs[i]), int(wi[i]), int(wo[i])) for i in range(nl.value)]  # (offset of ein, in_p, out_p) per Dense
+            with torch.cuda.device(self.device):
+                self.sigma = torch.zeros_like(self.params)
+                self.sigma_m = torch.zeros_like(self.params)
+                self.sigma_v = torch.zeros_like(self.params)
+                self.eff = torch.zeros_like(self.params)
+                self.grad = torch.zeros_like(self.params)
+                self.noise = torch.zeros(int(total.value), dtype=torch.float32, device=self.device)
+                self.noise_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+                # the DQN form's second draw (stream_id = 1) and the target's composed parameters
+                self.noise_target = torch.zeros_like(self.noise)
+                self.eff_target = torch.zeros_like(self.params)
+            self._noise_zero = True  # the buffers above: zero noise, the mean network
+
+    # ------------------------------------------------------------------ noisy Dense layers
+    noisy = False  # (class default: an engine built without the option, or a host-side stand-in for the layout)
+    resample_on_learn = False  # True (the agents set it): every learn call draws new noise first, so that a captured step does too
+
+    def _dense_leaf(self, info) -> bool:
+        return info.kind == 1 or (info.kind == 2 and info.name.decode().split("/")[-2].startswith("Dense_"))
+
+    def _sigma_tree(self) -> Dict[str, Dict[str, np.ndarray]]:
+        """sigma0 / sqrt(in_f) on the real elements of every Dense kernel and bias, in Flax shapes."""
+        head = self.head_kernel_info()
+        fan_in, tree = {}, {}
+        for info in self.infos:
+            if info.kind == 1:
+                fan_in[info.name.decode().rsplit("/", 1)[0]] = int(info.flax_shape[0]) // (2 if self.dueling and info.layer == head.layer else 1)
+        for info in self.infos:
+            if not self._dense_leaf(info):
+                continue
+            mod, leaf = info.name.decode().rsplit("/", 1)
+            v = np.full(tuple(info.flax_shape[: info.ndim]), self.noisy_sigma0 / math.sqrt(fan_in[mod]), np.float32)
+            if self.dueling and info.kind == 1 and info.layer == head.layer:
+                v = np.where(self.dueling_live_mask(), v, np.float32(0))
+            tree.setdefault(mod, {})["sigma_" + leaf] = v
+        return tree
+
+    def _import_sigma(self, tree, target: torch.Tensor) -> None:
+        flat = np.zeros(self.n_param_floats, np.float32)
+        for info in self.infos:
+            if self._dense_leaf(info):
+                mod, leaf = info.name.decode().rsplit("/", 1)
+                flat[info.offset : info.offset + info.size] = self._to_internal(info, tree[mod]["sigma_" + leaf])
+        target.copy_(torch.from_numpy(flat))
+
+    def export_sigma(self, source: torch.Tensor | None = None) -> Dict[str, Dict[str, np.ndarray]]:
+        """{"Dense_i": {"sigma_kernel", "sigma_bias"}} in Flax shapes from ``sigma`` (or another buffer of its layout)."""
+        flat = (self.sigma if source is None else source).detach().cpu().numpy()
+        out: Dict[str, Dict[str, np.ndarray]] = {}
+        for info in self.infos:
+            if self._dense_leaf(info):
+                mod, leaf = info.name.decode().rsplit("/", 1)
+                out.setdefault(mod, {})["sigma_" + leaf] = self._from_internal(info, flat[info.offset : info.offset + info.size])
+        return out
+
+    def resample_noise(self, stream_id: int = 0, noise: torch.Tensor | None = None) -> None:
+        """A new factorised draw into ``noise`` on the current stream; the device counter advances by one (nothing is read back)."""
+        _hip.check(self.lib.isdqn_noisy_sample(ctypes.byref(self.cfg), self.noisy_seed, int(stream_id), _hip.ptr(self.noise_count),
+                                               _hip.ptr(self.noise if noise is None else noise), _hip.stream_ptr(self.device)), "isdqn_noisy_sample")
+        if noise is None:
+            self._noise_zero = False
+
+    def zero_noise(self) -> None:
+        """The mean (evaluation) network: compose then returns mu bit for bit; the DQN form's target draw is zero too until the next resample."""
+        self.noise.zero_()
+        self.noise_target.zero_()
+        self._noise_zero = True
+
+    def compose(self, mu: torch.Tensor | None = None, sigma: torch.Tensor | None = None, noise: torch.Tensor | None = None,
+                eff: torch.Tensor | None = None, mirror: bool = True) -> torch.Tensor:
+        """eff = mu + sigma * noise on the Dense layers (defaults: the engine's own buffers); ``mirror``: also the workspace's weight
+        mirror of eff, so that the next call on eff may trust it."""
+        eff = self.eff if eff is None else eff
+        _hip.check(self.lib.isdqn_noisy_compose(ctypes.byref(self.cfg), _hip.ptr(self.params if mu is None else mu),
+                                                _hip.ptr(self.sigma if sigma is None else sigma), _hip.ptr(self.noise if noise is None else noise),
+                                                _hip.ptr(eff), _hip.ptr(self.workspace) if mirror else 0, _hip.stream_ptr(self.device)),
+                   "isdqn_noisy_compose")
+        if mirror:
+            self._mirror_version = None  # (the mirror now holds eff, not params)
+        return eff
+
+    def _acting_params(self, params):
+        """What a forward / loss / gradient-only call reads: the caller's buffer, or -- noisy, on the engine's own parameters -- eff after a
+        compose with the current noise."""
+        if params is None and self.noisy:
+            return self.compose()
+        return self.params if params is None else params
+
+    def _noisy_learn(self, batch: _hip.Batch, eff_target: torch.Tensor | None) -> torch.Tensor:
+        _hip.check(
+            self.lib.isdqn_noisy_learn_on_batch(
+                ctypes.byref(self.cfg), _hip.ptr(self.params), _hip.ptr(self.sigma), _hip.ptr(self.adam_m), _hip.ptr(self.adam_v),
+                _hip.ptr(self.sigma_m), _hip.ptr(self.sigma_v), _hip.ptr(self.adam_count), _hip.ptr(self.noise), _hip.ptr(self.eff),
+                _hip.ptr(eff_target), _hip.ptr(self.grad), ctypes.byref(batch), _hip.ptr(self.losses), _hip.ptr(self.losses_accum),
+                _hip.ptr(self.q_values), _hip.ptr(self.targets), _hip.ptr(self.priorities), _hip.ptr(self.workspace), _hip.stream_ptr(self.device),
+            ),
+            "isdqn_noisy_learn_on_batch",
+        )
+        self._mirror_version = None  # (the mirror holds eff of this step)
+        return self.losses
 
     # ------------------------------------------------------------------ parameter layout
     def _first_dense_after_conv(self, info) -> bool:
@@ -361,6 +496,9 @@ class QNetEngine:
             assert v.size == info.size, (info.name, v.size, info.size)
             flat[info.offset : info.offset + info.size] = v
         (self.params if target is None else target).copy_(torch.from_numpy(flat))
+        # noisy engines: "Dense_i/sigma_kernel" and "Dense_i/sigma_bias" next to kernel / bias load sigma (a tree without them leaves it)
+        if getattr(self, "noisy", False) and target is None and any("sigma_kernel" in leaves for leaves in params.values()):
+            self._import_sigma(params, self.sigma)
 
     def export_flax(self, source: torch.Tensor | None = None) -> Dict[str, Dict[str, np.ndarray]]:
         flat = (self.params if source is None else source).detach().cpu().numpy()
@@ -370,6 +508,9 @@ class QNetEngine:
                 continue
             mod, leaf = info.name.decode().rsplit("/", 1)  # (impala: "Stack_0/Conv_1" / "kernel")
             out.setdefault(mod, {})[leaf] = self._from_internal(info, flat[info.offset : info.offset + info.size])
+        if getattr(self, "noisy", False) and source is None:  # (the engine's own parameters: mu with the sigma leaves beside it)
+            for mod, leaves in self.export_sigma().items():
+                out[mod].update(leaves)
         return out
 
     def export_batch_stats(self, source: torch.Tensor | None = None) -> Dict[str, Dict[str, np.ndarray]]:
@@ -386,6 +527,12 @@ class QNetEngine:
         """Flax defaults (dqn.py:49, 90): xavier_uniform for cnn, lecun_normal for fc; biases 0, LN scale 1.
         Draws come from numpy PCG64 (JAX threefry streams are not reproducible offline)."""
         self.import_flax(self._init_tree(seed))
+        if getattr(self, "noisy", False):
+            self.init_sigma()
+
+    def init_sigma(self) -> None:
+        """sigma = noisy_sigma0 / sqrt(in_f) on the real elements of the Dense kernels and biases, +0 everywhere else."""
+        self._import_sigma(self._sigma_tree(), self.sigma)
 
     def fresh_params(self, seed) -> torch.Tensor:
         """A new device tensor in the internal layout holding what ``init_params(seed)`` would leave in ``params`` (the engine's own
@@ -489,7 +636,7 @@ class QNetEngine:
 
     def forward(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, n_rows: int, params=None) -> torch.Tensor:
         q = torch.empty(n_rows, self.n_heads * self.n_actions, dtype=torch.float32, device=self.device)
-        p = self.params if params is None else params
+        p = self._acting_params(params)
         _hip.check(
             self.lib.isdqn_net_forward(
                 ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(frames), int(frame_stride), _hip.ptr(frame_ids),
@@ -501,7 +648,15 @@ class QNetEngine:
         return q
 
     def learn_on_batch(self, batch: _hip.Batch, grad_out: torch.Tensor | None = None) -> torch.Tensor:
-        """One gradient step in place; returns the device tensor of per-head losses (no sync)."""
+        """One gradient step in place; returns the device tensor of per-head losses (no sync).  Noisy engines: the noisy learn step
+        on the current ``noise`` (the caller resamples); ``grad_out`` then receives a copy of the step's reduced gradient."""
+        if self.noisy:
+            if self.resample_on_learn:
+                self.resample_noise()
+            self._noisy_learn(batch, None)
+            if grad_out is not None:
+                grad_out.copy_(self.grad)
+            return self.losses
         args = [
             ctypes.byref(self.cfg), _hip.ptr(self.params), _hip.ptr(self.adam_m), _hip.ptr(self.adam_v),
             _hip.ptr(self.adam_count), ctypes.byref(batch), _hip.ptr(self.losses), _hip.ptr(self.losses_accum), _hip.ptr(self.q_values),
@@ -520,7 +675,7 @@ class QNetEngine:
         """Gradient of a TD loss into ``grad_out`` (internal layout), nothing updated (analysisdqn.py:156-219): the
         configuration's own loss (n_pairs = 0) or online heads online_head + k on target heads target_head + k; next states
         through ``target_params`` when given.  Returns the device tensor of the loss per pair (the first n_pairs / K entries)."""
-        p = self.params if params is None else params
+        p = self._acting_params(params)
         _hip.check(
             self.lib.isdqn_net_grad_on_batch(
                 ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(target_params), ctypes.byref(batch), int(online_head), int(target_head),
@@ -532,8 +687,17 @@ class QNetEngine:
         self._mirror_holds(params)
         return self.losses
 
-    def learn_on_batch_target(self, batch: _hip.Batch, target_params: torch.Tensor) -> torch.Tensor:
-        """DQN step (dqn.py:59-72): next states through `target_params`, in-place update of the online parameters."""
+    def learn_on_batch_target(self, batch: _hip.Batch, target_params: torch.Tensor, target_sigma: torch.Tensor | None = None) -> torch.Tensor:
+        """DQN step (dqn.py:59-72): next states through `target_params`, in-place update of the online parameters.  Noisy engines:
+        the target is composed from ``target_params``, ``target_sigma`` (default: the online sigma) and a draw of its own (stream_id = 1;
+        zero while the engine's noise is zeroed)."""
+        if self.noisy:
+            if self.resample_on_learn:
+                self.resample_noise()
+            if not self._noise_zero:
+                self.resample_noise(1, self.noise_target)
+            self.compose(target_params, target_sigma, self.noise_target, self.eff_target, mirror=False)
+            return self._noisy_learn(batch, self.eff_target)
         _hip.check(
             self.lib.isdqn_net_learn_on_batch_target(
                 ctypes.byref(self.cfg), _hip.ptr(self.params), _hip.ptr(target_params), _hip.ptr(self.adam_m), _hip.ptr(self.adam_v),
@@ -547,7 +711,7 @@ class QNetEngine:
         return self.losses
 
     def loss_on_batch_target(self, batch: _hip.Batch, target_params: torch.Tensor, params=None) -> torch.Tensor:
-        p = self.params if params is None else params
+        p = self._acting_params(params)
         _hip.check(
             self.lib.isdqn_net_loss_on_batch_target(
                 ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(target_params), ctypes.byref(batch), _hip.ptr(self.losses),
@@ -559,7 +723,7 @@ class QNetEngine:
         return self.losses
 
     def loss_on_batch(self, batch: _hip.Batch, params=None) -> torch.Tensor:
-        p = self.params if params is None else params
+        p = self._acting_params(params)
         _hip.check(
             self.lib.isdqn_net_loss_on_batch(
                 ctypes.byref(self.cfg), _hip.ptr(p), ctypes.byref(batch), _hip.ptr(self.losses),
@@ -586,10 +750,12 @@ class QNetEngine:
     def shift_params(self, params=None) -> None:
         p = self.params if params is None else params
         _hip.check(self.lib.isdqn_net_shift_params(ctypes.byref(self.cfg), _hip.ptr(p), _hip.stream_ptr(self.device)))
+        if self.noisy and params is None:  # the head blocks of sigma move exactly as those of mu (same layout)
+            _hip.check(self.lib.isdqn_net_shift_params(ctypes.byref(self.cfg), _hip.ptr(self.sigma), _hip.stream_ptr(self.device)))
         self._mirror_version = None  # the head rows moved in the master only
 
     def best_action(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, idx_network: int, params=None) -> torch.Tensor:
-        p = self.params if params is None else params
+        p = self._acting_params(params)
         _hip.check(
             self.lib.isdqn_net_best_action(
                 ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(frames), int(frame_stride), _hip.ptr(frame_ids),
@@ -633,6 +799,8 @@ class QNetEngine:
         """ReDo (Sokar et al. 2023; include/isdqn_hip.h, isdqn_net_redo) on the engine's own params / adam_m / adam_v: score the hidden
         neurons on n_rows observations, recycle the dormant ones from ``fresh`` (internal layout: ``fresh_params``).  Returns device
         tensors, split per layer like ``analysis``: (scores, mask (int32 0 / 1), n_recycled int32 [n_layers]); nothing is read back."""
+        if self.noisy:
+            raise ValueError(NOISY_REDO_REFUSED)
         assert fresh.dtype == torch.float32 and fresh.numel() == self.n_param_floats and fresh.is_contiguous() and fresh.device == self.params.device
         widths = self.redo_layout()
         scores = torch.empty(sum(widths), dtype=torch.float32, device=self.device)
@@ -689,7 +857,7 @@ class QNetEngine:
 
     def _mirror_holds(self, params) -> None:
         """The call just enqueued rebuilt the mirror from `params` (None = the engine's own buffer)."""
-        self._mirror_version = self.params._version if params is None else None
+        self._mirror_version = self.params._version if params is None and not self.noisy else None  # (noisy: the mirror holds eff)
         self._mirror_ptr = self.params.data_ptr()
 
     def best_actions(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, idx_networks: torch.Tensor, params=None,
@@ -702,6 +870,8 @@ class QNetEngine:
         p = self.params if params is None else params
         if mirror_current is None:
             mirror_current = self._mirror_is_current(params)
+        if self.noisy and params is None:  # one draw serves all rows; compose leaves the mirror of eff in the workspace
+            p, mirror_current = self.compose(), True
         flags = _hip.BATCH_MIRROR_CURRENT if mirror_current else 0
         _hip.check(
             self.lib.isdqn_net_best_actions(

@@ -179,6 +179,10 @@ class GraphedUpdate:
         training = [self.eng.params, self.eng.adam_m, self.eng.adam_v, self.eng.adam_count, self.eng.losses_accum]
         if getattr(self.eng, "max_grad_norm", 0.0) > 0.0:
             training.append(self.eng.grad_clip[2:4])
+        # (noisy engines: every captured step holds the resample -- the device counter makes each replay draw anew -- and the noisy
+        # learn; the warm-up's draws and sigma updates must not count either)
+        if getattr(self.eng, "noisy", False):
+            training += [self.eng.sigma, self.eng.sigma_m, self.eng.sigma_v, self.eng.noise_count]
         state = [t.clone() for t in training]
         # (prioritized: the warm-up also writes priorities back -- with the zero-filled draw block -- so the whole tree
         # state is saved: nodes, max_recorded_priority, which every later add() reads, and the latched status word)
@@ -224,4 +228,8 @@ class GraphedUpdate:
         if self.eng.trust_mirror:
             self.eng.refresh_mirror()  # (trusted engines only: one eager launch when the bookkeeping says the mirror is stale)
         self.graph.replay()
-        self.eng._mirror_made_current()  # the last step's optimizer wrote both forms of the weights
+        if getattr(self.eng, "noisy", False):
+            self.eng.invalidate_mirror()  # (the mirror holds the last step's composed parameters, not mu)
+            self.eng._noise_zero = False
+        else:
+            self.eng._mirror_made_current()  # the last step's optimizer wrote both forms of the weights

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p
+from ctypes import POINTER, c_char, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ISDQN_HIP_LIB: development override (A/B timing of two builds inside one gpurun call); still a HIP build, never a fallback
@@ -180,6 +180,18 @@ _SIGNATURES = {
         c_int32,
         [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_float,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    # noisy Dense layers (include/isdqn_hip.h, isdqn_noisy_layout): layout, sample, compose, learn
+    "isdqn_noisy_layout": (
+        c_int32,
+        [POINTER(NetConfig), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_int64)],
+    ),
+    "isdqn_noisy_sample": (c_int32, [POINTER(NetConfig), c_uint64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "isdqn_noisy_compose": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isdqn_noisy_learn_on_batch": (
+        c_int32,
+        [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         POINTER(Batch), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "isdqn_selftest_gemm": (
         c_int32,

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
-from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles, check_redo
+from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_noisy, check_quantiles, check_redo
 
 
 class DeviceParams:
@@ -28,7 +28,8 @@ class DeviceParams:
 
     def to_flax(self):
         """The reference's ``params["params"]`` pytree; nested modules (the impala Stacks) as nested dicts like Flax's."""
-        return self._nest(self._engine.export_flax(self.tensor))
+        # (the engine's own buffer of a noisy engine: the sigma leaves "sigma_kernel" / "sigma_bias" ride beside kernel / bias)
+        return self._nest(self._engine.export_flax(None if self.tensor is self._engine.params else self.tensor))
 
     def batch_stats(self):
         """Flax's second collection of a BatchNorm network (isdqn.py:87-88): {"BatchNorm_i": {"mean", "var"}} (the impala Stacks'
@@ -113,7 +114,11 @@ class EngineAgent:
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
                            n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0, double_q=False,
                            munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False, dueling=False,
-                           max_grad_norm=0.0):
+                           max_grad_norm=0.0, noisy=False, noisy_sigma0=0.5):
+        check_noisy(noisy, architecture_type, batch_norm, max_grad_norm)
+        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
+        self.noisy_eval = False  # True: acting calls run the mean network (zero noise) instead of drawing
+        self._bound_sigma = None
         check_dueling(dueling, architecture_type, features, batch_norm)
         self.dueling = bool(dueling)
         check_grad_clip(max_grad_norm, architecture_type, batch_norm)
@@ -159,7 +164,10 @@ class EngineAgent:
             double_q=self.double_q,
             munchausen_tau=self.munchausen_tau, munchausen_alpha=self.munchausen_alpha, munchausen_clip=self.munchausen_clip,
             n_quantiles=self.n_quantiles, categorical=self.categorical, dueling=self.dueling, max_grad_norm=self.max_grad_norm,
+            **(dict(noisy=True, noisy_sigma0=self.noisy_sigma0, noisy_seed=self._seed) if self.noisy else {}),
         )
+        if self.noisy:
+            eng.resample_on_learn = True  # every learn step of an agent draws first (eager and captured alike)
         if init:
             eng.init_params(self._seed)
         else:  # a batch of another size arrived: same parameter layout, new workspace
@@ -168,6 +176,9 @@ class EngineAgent:
             eng.adam_v.copy_(old.adam_v)
             eng.adam_count.copy_(old.adam_count)
             eng.losses_accum.copy_(old.losses_accum)
+            if self.noisy:
+                for name in ("sigma", "sigma_m", "sigma_v", "noise_count"):
+                    getattr(eng, name).copy_(getattr(old, name))
             if self.max_grad_norm > 0.0:
                 eng.grad_clip[2:4].copy_(old.grad_clip[2:4])
         self._drop_graph()  # captured against the old engine's buffers
@@ -270,6 +281,12 @@ class EngineAgent:
             params = params["params"]
         tree = flatten(params["params"] if "params" in params else params)
         t = torch.empty_like(self._engine.params)
+        # noisy agents: the sigma leaves of the tree, kept beside the returned mu (a learn call loads both; acting on a foreign model
+        # runs its mean network)
+        self._bound_sigma = None
+        if self.noisy and any("sigma_kernel" in leaves for leaves in tree.values()):
+            self._bound_sigma = torch.empty_like(self._engine.params)
+            self._engine._import_sigma(tree, self._bound_sigma)
         self._engine.import_flax(tree, target=t, batch_stats=flatten(params.get("batch_stats")) if "params" in params else None)
         return t
 
@@ -405,6 +422,7 @@ class EngineAgent:
         """One observation: newest frame up, one forward (weight mirror reused when nothing wrote the parameters since the
         last learn step), one 4-byte read back."""
         eng = self._engine
+        self._noisy_act(params)
         if self._bind(params) is None and self.architecture_type != "fc" and getattr(self, "act_graph", True):
             ring = self._ring
             s = np.asarray(state)
@@ -419,8 +437,9 @@ class EngineAgent:
         return int(out.item())
 
     def _best_actions(self, params, states, idx_networks) -> np.ndarray:
-        """Greedy actions of n observations in one forward and one device->host copy."""
+        """Greedy actions of n observations in one forward and one device->host copy.  Noisy agents: ONE draw serves all n rows."""
         eng = self._engine
+        self._noisy_act(params)
         idx = torch.as_tensor(np.array(idx_networks, dtype=np.int32)).to(eng.device)
         out = eng.best_actions(idx_networks=idx, params=self._bind(params), **self._states_to_device(states))
         return out.cpu().numpy()
@@ -430,6 +449,7 @@ class EngineAgent:
         (planar stacks, oldest .. newest; pinned when the runtime registered the mapping).  ONE host-to-device copy of the
         block, one small copy of (plane ids, head indices), one forward over len(rows) observations, one read-back."""
         eng = self._engine
+        self._noisy_act(params)  # (one draw serves all rows of the round)
         n, stack, hw = planes.shape
         v = getattr(self, "_vec", None)
         if v is None or v["dev"].shape != (n * stack, hw) or v["dev"].device != eng.device:
@@ -459,6 +479,56 @@ class EngineAgent:
 
         return result() if wait else result
 
+    # ------------------------------------------------------------------ noisy Dense layers
+    def _noisy_act(self, params) -> None:
+        """In front of every acting call on the agent's own parameters: a new draw, or zero noise with ``noisy_eval``."""
+        if getattr(self, "noisy", False) and (params is None or params is self.params):
+            if self.noisy_eval:
+                self._engine.zero_noise()
+            else:
+                self._engine.resample_noise()
+
+    def noisy_evaluation(self):
+        """Context: acting calls inside run the mean network (``noisy_eval`` = True), the previous setting returns behind it."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            old, self.noisy_eval = self.noisy_eval, True
+            try:
+                yield self
+            finally:
+                self.noisy_eval = old
+
+        return ctx()
+
+    def _one_draw(self, eng):
+        """Context for an update that makes several passes over one batch (the analysis agents): noisy engines draw ONCE in front and
+        every pass inside -- gradient-only passes, the learn step, the loss passes behind it -- runs under that draw; the step's own
+        draw is switched off for the duration.  Other engines: nothing."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            if not getattr(eng, "noisy", False):
+                yield
+                return
+            eng.resample_noise()
+            keep, eng.resample_on_learn = eng.resample_on_learn, False
+            try:
+                yield
+            finally:
+                eng.resample_on_learn = keep
+
+        return ctx()
+
+    def _load_bound(self, eng, bound) -> None:
+        """A learn call on foreign parameters: they become the engine's (noisy: their sigma leaves with them)."""
+        if bound is not None:
+            eng.params.copy_(bound)
+            if getattr(self, "noisy", False) and self._bound_sigma is not None:
+                eng.sigma.copy_(self._bound_sigma)
+
     # ------------------------------------------------------------------ ReDo
     _recycles = 0  # recycles done so far: selects the seed of the next fresh parameters
 
@@ -468,6 +538,7 @@ class EngineAgent:
         online parameters only: a DQN's target parameters keep their bits.  Pointers do not move and the weight mirror is left
         current, so a captured update stays valid.  Returns the recycled neurons per hidden layer -- the only host read."""
         check_redo(self.architecture_type, self.batch_norm)
+        check_noisy(getattr(self, "noisy", False), self.architecture_type, redo=True)
         eng = self._engine
         n = 2 * eng.batch_size
         samples = replay_buffer.sample(size=n)
@@ -493,7 +564,9 @@ class EngineAgent:
             self.update_online_params(0, replay_buffer)
 
     def _q_row(self, params, state) -> torch.Tensor:
-        """network.apply on one observation: device row of n_heads * n_actions values."""
+        """network.apply on one observation: device row of n_heads * n_actions values (noisy agents: under a new draw, or the mean
+        network with ``noisy_eval``)."""
+        self._noisy_act(params)
         return self._engine.forward(n_rows=1, params=self._bind(params), **self._obs_to_device(state))
 
     def get_model(self):

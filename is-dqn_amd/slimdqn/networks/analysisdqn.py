@@ -118,10 +118,16 @@ class AnalysisDQN(iSDQN):
         return torch.dot(a, b) / (torch.linalg.norm(a) * torch.linalg.norm(b) + 1e-9)
 
     def learn_on_batch(self, params, params_target, optimizer_state, batch_samples, batch_samples_eval):
+        """The iS-DQN step with its diagnostics.  With ``noisy`` ONE draw serves the whole update: the three gradients are taken on
+        the same composed online network (so the cosines compare losses, not draws), the step trains under it and the churn is the
+        change of the targets under it.  The target-based gradient reads the target copy's mean network (mu: the copy has no sigma
+        of its own)."""
         eng = self._engine_for(self._batch_len(batch_samples))
-        bound = self._bind(params)
-        if bound is not None:
-            eng.params.copy_(bound)
+        with self._one_draw(eng):
+            return self._learn_with_diagnostics(eng, params, params_target, batch_samples, batch_samples_eval)
+
+    def _learn_with_diagnostics(self, eng, params, params_target, batch_samples, batch_samples_eval):
+        self._load_bound(eng, self._bind(params))
         cb, cb_eval = self._c_batch(eng, batch_samples), self._c_batch(eng, batch_samples_eval)
         tp = self._bind(params_target)
         tp = eng.params if tp is None else tp

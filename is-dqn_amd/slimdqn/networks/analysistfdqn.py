@@ -36,9 +36,11 @@ class AnalysisTFDQN(TFDQN):
         if batch_samples_eval is None:
             return super().learn_on_batch(params, optimizer_state, batch_samples)
         eng = self._engine_for(self._batch_len(batch_samples))
-        bound = self._bind(params)
-        if bound is not None:
-            eng.params.copy_(bound)
+        with self._one_draw(eng):  # (noisy: the step and the churn passes around it run under one draw)
+            return self._learn_with_churn(eng, params, batch_samples, batch_samples_eval)
+
+    def _learn_with_churn(self, eng, params, batch_samples, batch_samples_eval):
+        self._load_bound(eng, self._bind(params))
         cb, cb_eval = self._c_batch(eng, batch_samples), self._c_batch(eng, batch_samples_eval)
         eng.loss_on_batch(cb_eval)
         eval_pre = eng.targets.clone()

@@ -47,8 +47,18 @@ class DQN(EngineAgent):
         categorical: bool = False,
         dueling: bool = False,
         max_grad_norm: float = 0.0,
+        noisy: bool = False,
+        noisy_sigma0: float = 0.5,
     ):
-        """``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+        """``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
+        included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
+        call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
+        ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
+        "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise alone.
+        Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError).
+        The target network has a sigma of its own (copied with the parameters at every target update) and, in every learn step, a draw
+        of its own (stream 1), as in Fortunato's DQN.
+        ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
         optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
         the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
         ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
@@ -85,8 +95,10 @@ class DQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
                                 max_value=max_value, sigma=sigma, double_q=double_q, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm)
+                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm,
+                                noisy=noisy, noisy_sigma0=noisy_sigma0)
         self.target_params = self.params.copy()  # dqn.py:34
+        self.target_sigma = self._engine.sigma.clone() if self.noisy else None  # (one persistent buffer, refreshed in place like the target)
         self.cumulated_loss = 0
 
     def _engine_changed(self, old) -> None:
@@ -98,7 +110,7 @@ class DQN(EngineAgent):
         if step % self.data_to_update == 0:
             target = self._target_tensor(self.target_params)
             eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
-            g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target), key=target.data_ptr())
+            g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw()), key=target.data_ptr())
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
                 g.run(self._next_betas(g.S))
                 return
@@ -113,6 +125,8 @@ class DQN(EngineAgent):
             # `self.target_params = self.params.copy()` (dqn.py:50) as an in-place refresh of ONE persistent buffer: the captured
             # step reads the target through a fixed pointer, so a target update neither re-captures nor re-instantiates a graph
             self.target_params.tensor.copy_(self.params.tensor)
+            if self.noisy:
+                self.target_sigma.copy_(self._engine.sigma)
             eng = self._engine
             self.cumulated_loss = self.cumulated_loss + float(eng.losses_accum.cpu().numpy()[0])
             eng.losses_accum.zero_()
@@ -123,6 +137,9 @@ class DQN(EngineAgent):
         return False, {}
 
     # ------------------------------------------------------------------ dqn.py:59-88
+    def _target_sigma_kw(self) -> dict:
+        return dict(target_sigma=self.target_sigma) if self.noisy else {}
+
     def _target_tensor(self, params_target) -> torch.Tensor:
         t = self._bind(params_target)
         return self._engine.params if t is None else t
@@ -130,10 +147,8 @@ class DQN(EngineAgent):
     def learn_on_batch(self, params, params_target, optimizer_state, batch_samples):
         """In-place gradient step; returns (params, optimizer_state, loss) like the reference (loss: device scalar)."""
         eng = self._engine_for(self._batch_len(batch_samples))
-        bound = self._bind(params)
-        if bound is not None:
-            eng.params.copy_(bound)
-        losses = eng.learn_on_batch_target(self._c_batch(eng, batch_samples), self._target_tensor(params_target))
+        self._load_bound(eng, self._bind(params))
+        losses = eng.learn_on_batch_target(self._c_batch(eng, batch_samples), self._target_tensor(params_target), **self._target_sigma_kw())
         return self.params, self.optimizer_state, losses[0]
 
     def loss_on_batch(self, params, params_target, samples):

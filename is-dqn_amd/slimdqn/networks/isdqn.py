@@ -59,8 +59,16 @@ class iSDQN(EngineAgent):
         categorical: bool = False,
         dueling: bool = False,
         max_grad_norm: float = 0.0,
+        noisy: bool = False,
+        noisy_sigma0: float = 0.5,
     ):
-        """``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+        """``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
+        included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
+        call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
+        ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
+        "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise alone.
+        Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError).
+        ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
         optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
         the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
         ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
@@ -101,7 +109,7 @@ class iSDQN(EngineAgent):
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
                                 n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical, dueling,
-                                max_grad_norm)
+                                max_grad_norm, noisy, noisy_sigma0)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 
@@ -164,9 +172,7 @@ class iSDQN(EngineAgent):
         """In-place gradient step; returns (params, optimizer_state, losses[K]) like the reference.
         ``losses`` is a device tensor (reading it synchronises)."""
         eng = self._engine_for(self._batch_len(batch_samples))
-        bound = self._bind(params)
-        if bound is not None:
-            eng.params.copy_(bound)
+        self._load_bound(eng, self._bind(params))
         losses = eng.learn_on_batch(self._c_batch(eng, batch_samples))
         return self.params, self.optimizer_state, losses
 

@@ -52,8 +52,16 @@ class TFDQN(EngineAgent):
         categorical: bool = False,
         dueling: bool = False,
         max_grad_norm: float = 0.0,
+        noisy: bool = False,
+        noisy_sigma0: float = 0.5,
     ):
-        """``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+        """``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
+        included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
+        call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
+        ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
+        "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise alone.
+        Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError).
+        ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
         optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
         the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
         ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
@@ -87,7 +95,8 @@ class TFDQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, batch_norm=batch_norm,
                                 n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm)
+                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm,
+                                noisy=noisy, noisy_sigma0=noisy_sigma0)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54
@@ -114,9 +123,7 @@ class TFDQN(EngineAgent):
     # ------------------------------------------------------------------ tfdqn.py:56-86
     def learn_on_batch(self, params, optimizer_state, batch_samples):
         eng = self._engine_for(self._batch_len(batch_samples))
-        bound = self._bind(params)
-        if bound is not None:
-            eng.params.copy_(bound)
+        self._load_bound(eng, self._bind(params))
         losses = eng.learn_on_batch(self._c_batch(eng, batch_samples))
         return self.params, self.optimizer_state, losses[0]
 
