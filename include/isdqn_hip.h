@@ -146,6 +146,40 @@ int isdqn_replay_materialize(const uint8_t* frames, int64_t frame_stride, int32_
 int isdqn_replay_deinterleave(const uint8_t* state, const uint8_t* next_state, int32_t h, int32_t w, int32_t stack,
                               int32_t B, uint8_t* out_frames, int32_t* out_frame_ids, void* stream);
 
+/* DrQ random-shift augmentation of the frame stacks of `n_rows` sampled transitions (Kostrikov, Yarats and Fergus 2020, K = M = 1;
+ * DrQ(eps) of Agarwal et al. 2021; also what DER, SPR and BBF apply), on the device.  The learn step reads frames + frame_stride +
+ * frame_ids and never the replay itself, so the option is built beside it: this call writes the shifted copies of the batch's frames
+ * into the scratch pool `out_frames` and a table `out_frame_ids` that points into the pool; hand those two to isdqn_batch in place of
+ * the store and the gathered table.  No kernel of the learn step knows of it, and every torso that reads frames takes it.
+ * THE definition.  frame_ids is [n_rows][2*stack] as isdqn_replay_gather_rows wrote it: ids [0, stack) the state stack of the row,
+ * [stack, 2*stack) its next-state stack.
+ *   Which draw.  Row r belongs to step t = *aug_count + r / rows_per_step and is row b = r % rows_per_step of that step; half = 0 for
+ *     the state stack, 1 for the next-state stack.
+ *   The draw.  (x0, x1) = the first two output words of Philox4x32-10 (the function of the noisy layers) at counter
+ *     (b, 0x80000000 | half, lo32(t), hi32(t)) under key (lo32(seed), hi32(seed)); bit 31 of counter word 1 keeps these draws disjoint
+ *     from the noisy layers' (their word 1 is (stream_id << 16) | vector id) under the same seed.
+ *     dx = (int)(((uint64_t)x0 * (2*pad+1)) >> 32) - pad, dy the same from x1: each uniform on [-pad, pad] up to 2^-32 * (2*pad+1).
+ *     ONE draw serves all `stack` frames of a half; the two halves draw independently.
+ *   The pixels.  out[y][x] = in[clamp(y + dy, 0, h-1)][clamp(x + dx, 0, w-1)]: replicate-pad the frame by `pad` on every side and
+ *     crop h x w at offset (pad + dy, pad + dx).
+ *   The id table.  An input id >= 0 at row r, position k: out_frame_ids[r][k] = r * 2*stack + k, and that frame of the pool (h*w bytes
+ *     at out_frames + (r * 2*stack + k) * frame_stride) is written; the bytes between h*w and frame_stride are not.  An input id -1
+ *     (the all-zero frame of the leading padding) stays -1 and its frame of the pool is NOT written.
+ *   The counter.  A one-thread launch behind the shift stores *aug_count + n_rows / rows_per_step with an ordinary store (no atomics
+ *     anywhere).  So one call over the S*B rows of S steps with rows_per_step = B is bit for bit S calls over B rows each, and a
+ *     captured graph that holds the call draws anew at every replay.
+ * pad = 0 is the identity copy (the counter still advances); pad >= h or pad >= w is legal, the clamp handles it.
+ * ISDQN_ERR_ARG, and nothing is launched: pad < 0 or pad > 127; h, w, stack or n_rows < 1; rows_per_step < 1 or no divisor of n_rows;
+ * frame_stride < h*w; a NULL pointer; out_frames overlapping frames -- the store's extent is no argument, so what is refused is the
+ * store's base inside the pool and the pool's base inside the store's first frame; out_frame_ids overlapping frame_ids; an id table
+ * that is not 4-byte or a counter that is not 8-byte aligned; more than 2^31 - 1 output frames.
+ * When h*w, frame_stride and both frame bases are multiples of 16 (84 x 84 = 441 * 16) the copy moves 16-byte pieces through LDS;
+ * any other geometry takes a byte path with the same result. */
+int isdqn_replay_augment_shift(const uint8_t* frames, int64_t frame_stride, int32_t h, int32_t w, int32_t stack,
+                               const int32_t* frame_ids /* [n_rows][2*stack] */, int32_t n_rows, int32_t rows_per_step,
+                               int32_t pad, uint64_t seed, int64_t* aug_count,
+                               uint8_t* out_frames /* [n_rows*2*stack][frame_stride] */, int32_t* out_frame_ids, void* stream);
+
 /* ========================================================================== */
 /* Q-network + iS-DQN update  (slimdqn/networks/architectures/dqn.py, isdqn.py) */
 /* ========================================================================== */

@@ -36,17 +36,7 @@ struct NoisyVecTable {
     int n, total_blocks;
 };
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t& x0,
-                                              uint32_t& x1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    x0 = c0; x1 = c1;
-}
+#include "philox.h"  // philox4x32_10, shared with augment.h
 
 // f(z) of one standard normal from two Philox words.  u1 = (k + 1/2) 2^-24 with k = x0 >> 8 has 25 significant bits from k = 2^23 on:
 // there -ln u1 is taken as -log1p(-(1 - u1)), whose argument (2^24 - k - 1/2) 2^-24 is exact in fp32; below, u1 itself is exact

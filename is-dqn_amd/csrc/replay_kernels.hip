@@ -174,3 +174,63 @@ extern "C" int isdqn_replay_deinterleave(const uint8_t* state, const uint8_t* ne
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }
+
+// The random-shift augmentation, behind every kernel this code object had: they keep their places in it.
+namespace isdqn {
+#include "augment.h"
+}  // namespace isdqn
+
+#if defined(ISDQN_BOUNDS)
+// Bounds-checked development build (augment.h: this code object's own table): register the byte extents [lo[i], hi[i]) of every buffer
+// the caller hands to the augmentation and clear the record; read back the first load that fell outside all of them (synchronises).
+extern "C" int isdqn_debug_replay_bounds_set(const uint64_t* lo, const uint64_t* hi, int32_t n) {
+    ISDQN_REQUIRE(n >= 0 && n <= 16, ISDQN_ERR_ARG, "at most 16 regions");
+    isdqn::ReplayBoundsTable t{};
+    t.n = n;
+    for (int i = 0; i < n; ++i) { t.lo[i] = lo[i]; t.hi[i] = hi[i]; }
+    ISDQN_HIP_CHECK(hipDeviceSynchronize());
+    ISDQN_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(isdqn::replay_bounds), &t, sizeof(t)));
+    return ISDQN_OK;
+}
+extern "C" int isdqn_debug_replay_bounds_get(int32_t* bad, int32_t* site, uint64_t* addr) {
+    isdqn::ReplayBoundsTable t;
+    ISDQN_HIP_CHECK(hipDeviceSynchronize());
+    ISDQN_HIP_CHECK(hipMemcpyFromSymbol(&t, HIP_SYMBOL(isdqn::replay_bounds), sizeof(t)));
+    *bad = t.bad; *site = t.bad_site; *addr = t.bad_addr;
+    return ISDQN_OK;
+}
+#endif
+
+// Random-shift augmentation of the frame stacks of n_rows sampled transitions into a scratch pool (include/isdqn_hip.h holds THE
+// definition; augment.h the kernels).  Two launches: the shift, then the one-thread counter advance.
+extern "C" int isdqn_replay_augment_shift(const uint8_t* frames, int64_t frame_stride, int32_t h, int32_t w, int32_t stack,
+                                          const int32_t* frame_ids, int32_t n_rows, int32_t rows_per_step, int32_t pad, uint64_t seed,
+                                          int64_t* aug_count, uint8_t* out_frames, int32_t* out_frame_ids, void* stream) {
+    ISDQN_REQUIRE(frames && frame_ids && aug_count && out_frames && out_frame_ids, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(pad >= 0 && pad <= 127, ISDQN_ERR_ARG, "pad outside [0, 127]");
+    ISDQN_REQUIRE(h >= 1 && w >= 1 && stack >= 1 && n_rows >= 1, ISDQN_ERR_ARG, "h, w, stack and n_rows must be positive");
+    ISDQN_REQUIRE(rows_per_step >= 1 && n_rows % rows_per_step == 0, ISDQN_ERR_ARG, "rows_per_step must divide n_rows");
+    ISDQN_REQUIRE((int64_t)h * w <= INT32_MAX && frame_stride >= (int64_t)h * w, ISDQN_ERR_ARG, "frame_stride < h * w");
+    const int64_t n_out = (int64_t)n_rows * 2 * stack;
+    ISDQN_REQUIRE(n_out <= INT32_MAX, ISDQN_ERR_ARG, "more than 2^31 - 1 output frames");
+    ISDQN_REQUIRE((reinterpret_cast<uintptr_t>(frame_ids) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_frame_ids) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(aug_count) & 7) == 0, ISDQN_ERR_ARG, "misaligned id table or counter");
+    // the pool must not overlap the store (a shifted frame would be read back as a source).  The store's extent is no argument: what the
+    // call can tell is the store's base inside the pool, and the pool's base inside the store's first frame
+    const uintptr_t fr = reinterpret_cast<uintptr_t>(frames), po = reinterpret_cast<uintptr_t>(out_frames);
+    const uintptr_t pool_bytes = (uintptr_t)(n_out - 1) * (uintptr_t)frame_stride + (uintptr_t)h * w;
+    ISDQN_REQUIRE(!(fr >= po && fr < po + pool_bytes) && !(po >= fr && po < fr + (uintptr_t)h * w), ISDQN_ERR_ARG,
+                  "out_frames overlaps frames");
+    // every workgroup reads its id and writes its output id: the two tables must be different memory
+    const uintptr_t ti = reinterpret_cast<uintptr_t>(frame_ids), to = reinterpret_cast<uintptr_t>(out_frame_ids), tb = (uintptr_t)n_out * 4;
+    ISDQN_REQUIRE(ti + tb <= to || to + tb <= ti, ISDQN_ERR_ARG, "out_frame_ids overlaps frame_ids");
+    const int hw = h * w;
+    const int wide = (hw & 15) == 0 && (frame_stride & 15) == 0 && ((fr | po) & 15) == 0 && hw <= AUG_MAX_LDS;
+    hipLaunchKernelGGL(augment_shift_kernel, dim3((unsigned)n_out), dim3(AUG_THREADS), wide ? hw : 0, (hipStream_t)stream, frames, frame_stride,
+                       h, w, FastDiv((uint32_t)w), stack, frame_ids, rows_per_step, pad, (uint32_t)seed, (uint32_t)(seed >> 32), aug_count,
+                       out_frames, out_frame_ids, wide);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(augment_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, aug_count, (int64_t)(n_rows / rows_per_step));
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}

@@ -57,6 +57,8 @@ _ENGINE = [
     ("-gc", "--max_grad_norm", dict(type=float, default=0.0, help="Clip the gradient by its global norm in front of Adam (optax.clip_by_global_norm; the dueling, QR-DQN, C51 and Rainbow recipes use 10) and log grad_norm / grad_clipped_fraction at every target update; 0 = off, inf = measure and log only. Not with -bn or -at impala.")),
     ("-noisy", "--noisy_nets", dict(action="store_true", default=False, help="NoisyNet exploration (Fortunato et al. 2018): every Dense layer, the head included, carries factorised Gaussian noise with a learned scale; acting and every learn step draw on the device. The epsilon flags keep their meaning: -ee 0 -ed 1 explores by noise alone, as Rainbow does. Not with -bn, -at impala, -gc > 0 or -redo.")),
     ("-noisys", "--noisy_sigma0", dict(type=float, default=0.5, help="sigma_0 of the noisy layers: sigma starts at sigma_0 / sqrt(fan-in). Means nothing without -noisy.")),
+    ("-aug", "--augment", dict(action="store_true", default=False, help="DrQ random-shift augmentation (Kostrikov et al. 2020; the DrQ(eps), DER, SPR and BBF recipes): every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in [-augp, augp]^2, borders replicated, on the device. With every image torso (-at cnn, -at impala, -ln, -bn) and every loss and target flag; not with -at fc.")),
+    ("-augp", "--augment_pad", dict(type=int, default=4, help="Largest shift in pixels of -aug (DrQ: 4 on 84 x 84 frames), 0..127. Means nothing without -aug.")),
     ("-dq", "--double_q", dict(action="store_true", default=False, help="Double Q-learning targets: the online head (DQN: the online network) picks the next action, the target values it. Not for the target-free agents.")),
     ("-mq", "--munchausen", dict(action="store_true", default=False, help="Munchausen targets (Vieillard et al. 2020): soft-value bootstrap plus the scaled, clipped log-policy of the taken action (the three flags below). Not with -dq.")),
     ("-mqt", "--munchausen_tau", dict(type=float, default=0.03, help="Temperature tau of the soft value and of the policy softmax(Q / tau). Means nothing without -mq.")),
@@ -206,6 +208,21 @@ def check_noisy(p: dict) -> None:
 def noisy_kwargs(p) -> dict:
     """The agents' noisy keywords from parsed parameters; without -noisy the keywords are the ones they were before the flag existed."""
     return dict(noisy=True, noisy_sigma0=float(p["noisy_sigma0"])) if p.get("noisy_nets") else {}
+
+
+# (-aug and -augp stay out of parameters.json like -noisy)
+def check_augment(p: dict, architecture_type=None) -> None:
+    """-aug with -at fc, or with an -augp outside 0..127, fails before anything is written, with the agents' own message.
+    ``architecture_type``: the torso of an entry point that fixes it (LunarLander's agents are built with "fc" whatever -at says)."""
+    if p.get("augment"):
+        from slimdqn._engine import check_augment as check
+
+        check(p["augment_pad"], architecture_type or p["architecture_type"])
+
+
+def augment_kwargs(p) -> dict:
+    """The agents' augmentation keyword from parsed parameters; without -aug the keywords are the ones they were before the flag existed."""
+    return dict(augment_pad=int(p["augment_pad"])) if p.get("augment") else {}
 
 
 # (-redo and -redot stay out of parameters.json like -hl and -qr)

@@ -42,6 +42,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     parser_argument.check_dueling(p)
     parser_argument.check_grad_clip(p)
     parser_argument.check_noisy(p)
+    parser_argument.check_augment(p, "fc" if env_name == "lunar_lander" else None)
     p["env_name"] = env_name
     if env_name == "atari":
         p["game_name"] = p["experiment_name"].split("_")[-1]

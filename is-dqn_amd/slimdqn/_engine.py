@@ -132,6 +132,19 @@ def check_noisy(noisy, architecture_type, batch_norm=False, max_grad_norm=0.0, r
             raise ValueError(NOISY_REDO_REFUSED)
 
 
+AUGMENT_FC_REFUSED = "random-shift augmentation shifts image frames: architecture_type 'fc' reads float32 vector observations"
+AUGMENT_PAD_REFUSED = "augment_pad must be an integer in [0, 127] (0: off; include/isdqn_hip.h, isdqn_replay_augment_shift)"
+
+
+def check_augment(pad, architecture_type) -> None:
+    """The pads and the torso the random-shift augmentation refuses, said before anything is allocated or written.  0 is off and goes
+    with every torso; every torso that reads frames (cnn, impala, with LayerNorm or BatchNorm) takes a pad > 0."""
+    if isinstance(pad, bool) or int(pad) != pad or not 0 <= int(pad) <= 127:
+        raise ValueError(AUGMENT_PAD_REFUSED)
+    if int(pad) > 0 and architecture_type == "fc":
+        raise ValueError(AUGMENT_FC_REFUSED)
+
+
 def dueling_live_mask(n_hidden: int, n_heads: int, n_actions: int, width: int = 1) -> np.ndarray:
     """Which entries of the dueling head's Flax kernel (F, R) are weights (True) and which structural zeros (include/isdqn_hip.h,
     isdqn_net_config::dueling): column ((h * (A + 1)) + c) * width + j is a value column for c = A and reads the hidden units

@@ -18,13 +18,18 @@ from slimdqn import _hip
 
 class GraphedUpdate:
     def __init__(self, rb, eng, prioritized: bool, steps_per_graph: int = 8, writeback: bool | None = None, learn=None,
-                 weighted: bool = False):
+                 weighted: bool = False, augment=None):
         """``prioritized``: the sampler is a sum tree (the query is part of the graph); ``writeback``: sqrt(mean_k td) of
         every step goes back into the tree (default: whenever prioritized); ``learn``: the learn call of one step on a C batch
         (default ``eng.learn_on_batch``; DQN passes its target-parameter form, dqn.py:59-72); ``weighted``: the query also writes
         the importance-sampling weights of its draws and the learn call applies them (prioritized only).  The betas are INPUT of
         a replay, like the draws: ``run(betas)`` stages one per step, the query kernel reads its step's from device memory -- a
-        replay with other betas is the same executable graph."""
+        replay with other betas is the same executable graph.  ``augment``: (pad, seed, device counter) of the random-shift augmentation
+        (include/isdqn_hip.h, isdqn_replay_augment_shift) or None -- the gathered rows' frames are shifted into a scratch pool inside the
+        graph and every step's batch reads the pool; the counter lives on the device, so every replay draws anew and lands on the
+        draws the eager steps would have taken."""
+        self.augment = augment
+        self.augment_pad = int(augment[0]) if augment else 0
         if weighted and not prioritized:
             raise ValueError("importance-sampling weights need the prioritized sampling distribution")
         self.rb, self.eng, self.prioritized, self.S = rb, eng, prioritized, steps_per_graph
@@ -59,6 +64,13 @@ class GraphedUpdate:
         # vector observations (the fc torso, LunarLander): the replay stores the bytes of every float32 observation as one 1 x 4d "frame";
         # the captured step materialises the B state / next-state rows of a batch into static buffers the engine reads as (B, d) float32
         self.fc = eng.architecture_type == "fc"
+        if self.augment:
+            if self.fc:
+                raise ValueError("random-shift augmentation shifts image frames: not with the fc torso")
+            # uniform: one pool over the S*B rows of a replay (one launch behind the single gather, rows_per_step = B); prioritized: one
+            # pool per batch slot, filled behind that slot's gather on the stream that gathered
+            self.aug_frames = torch.zeros(n_b, B * s2, rb._hw, dtype=torch.uint8, device=dev)
+            self.aug_ids = torch.full((n_b, B, s2), -1, dtype=torch.int32, device=dev)
         if self.fc:
             if not rb._obs_float or rb._stack_size != 1:
                 raise NotImplementedError("captured fc step: float32 vector observations with stack_size 1")
@@ -100,8 +112,16 @@ class GraphedUpdate:
                 for i in range(self.frame_ids.shape[0])
             ]
             return
+        # augmented: the batch reads the scratch pool through the table into it -- the one pool of the S*B-row launch (uniform: the ids
+        # of step i count from the pool's base), or the slot's own (prioritized)
+        if self.augment:
+            frames = lambda i: self.aug_frames[i] if self.prioritized else self.aug_frames
+            ids = lambda i: self.aug_ids[i]
+        else:
+            frames = lambda i: rb._frames
+            ids = lambda i: self.frame_ids[i]
         self.chained = [
-            eng.make_batch(frames=rb._frames, frame_stride=rb._hw, frame_ids=self.frame_ids[i], action=self.action[i],
+            eng.make_batch(frames=frames(i), frame_stride=rb._hw, frame_ids=ids(i), action=self.action[i],
                            reward=self.reward[i], terminal=self.terminal[i], mirror_current=True, priorities_ready=ev(i),
                            loss_weights=wt(i))
             for i in range(self.frame_ids.shape[0])
@@ -118,6 +138,12 @@ class GraphedUpdate:
             ),
             "isdqn_replay_gather_rows",
         )
+
+    def _augment(self, slot: int, n_rows: int) -> None:
+        """Shift the frames of ``n_rows`` gathered rows, from batch slot ``slot`` on, into the pool (current stream); nothing when off."""
+        if self.augment:
+            pad, seed, count = self.augment
+            self.rb.augment_into(self.frame_ids[slot], n_rows, self.B, pad, seed, count, self.aug_frames[slot], self.aug_ids[slot])
 
     def _materialize(self, slot: int, n_rows: int) -> None:
         """fc: the observation rows of ``n_rows`` gathered transitions, from batch slot ``slot`` on."""
@@ -149,6 +175,7 @@ class GraphedUpdate:
             main, sampling = torch.cuda.current_stream(eng.device), self._sampling_stream
             self._query(tree, 0, 0)
             self._gather(self.indices[0], self.B, 0)
+            self._augment(0, self.B)
             for s in range(self.S):
                 slot = s & 1
                 if self.fc:
@@ -163,9 +190,11 @@ class GraphedUpdate:
                     if s + 1 < self.S:
                         self._query(tree, s + 1, 1 - slot)
                         self._gather(self.indices[1 - slot], self.B, 1 - slot)
+                        self._augment(1 - slot, self.B)
                 main.wait_stream(sampling)
         else:
             self._gather(self.block, self.S * self.B, 0)  # rows of all S steps: the [S][B] buffers are contiguous
+            self._augment(0, self.S * self.B)  # (and so are the pool and its table: step s takes the draws of count + s)
             if self.fc:
                 self._materialize(0, self.S * self.B)
             for s in range(self.S):
@@ -183,6 +212,8 @@ class GraphedUpdate:
         # learn; the warm-up's draws and sigma updates must not count either)
         if getattr(self.eng, "noisy", False):
             training += [self.eng.sigma, self.eng.sigma_m, self.eng.sigma_v, self.eng.noise_count]
+        if self.augment:  # (the warm-up's draws must not count: the captured steps take the draws the eager steps would)
+            training.append(self.augment[2])
         state = [t.clone() for t in training]
         # (prioritized: the warm-up also writes priorities back -- with the zero-filled draw block -- so the whole tree
         # state is saved: nodes, max_recorded_priority, which every later add() reads, and the latched status word)

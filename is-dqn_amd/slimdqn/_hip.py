@@ -125,6 +125,11 @@ _SIGNATURES = {
         c_int32,
         [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     ),
+    # random-shift augmentation of a sampled batch's frames into a scratch pool (include/isdqn_hip.h, isdqn_replay_augment_shift)
+    "isdqn_replay_augment_shift": (
+        c_int32,
+        [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "isdqn_net_param_layout": (
         c_int32,
         [POINTER(NetConfig), POINTER(c_int64), POINTER(TensorInfo), c_int32, POINTER(c_int32)],

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
-from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_noisy, check_quantiles, check_redo
+from slimdqn._engine import QNetEngine, check_augment, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_noisy, check_quantiles, check_redo
 
 
 class DeviceParams:
@@ -77,6 +77,13 @@ def recycle_seed(seed: int, k: int) -> int:
     return int.from_bytes(state.tobytes(), "little")
 
 
+def augment_seed(seed: int) -> int:
+    """64-bit seed of the agent's random-shift draws: a child of the agent's seed in numpy's SeedSequence tree under a spawn key of its
+    own ((2,); ``recycle_seed`` has (1, k)), never the seed itself."""
+    state = np.random.SeedSequence(entropy=int(seed), spawn_key=(2,)).generate_state(2)
+    return int.from_bytes(state.tobytes(), "little")
+
+
 class EngineAgent:
     """Common state: ``n_heads`` network heads of ``n_actions`` outputs each on the HIP engine."""
 
@@ -108,13 +115,38 @@ class EngineAgent:
     def _sample(self, replay_buffer):
         """The training batch of one eager gradient step: with importance sampling on, drawn with this step's beta."""
         betas = self._next_betas()
-        return replay_buffer.sample() if betas is None else replay_buffer.sample(beta=float(betas[0]))
+        batch = replay_buffer.sample() if betas is None else replay_buffer.sample(beta=float(betas[0]))
+        return self._augment(replay_buffer, batch)
+
+    # ------------------------------------------------------------------ random-shift augmentation
+    augment_pad = 0   # 0: off
+    aug_count = None  # device int64 [1]: augmented gradient steps so far (selects the draws; the captured step advances it on the device)
+
+    def _augment(self, replay_buffer, batch):
+        """The training batch of one gradient step, shifted (``augment_pad`` > 0; include/isdqn_hip.h, isdqn_replay_augment_shift): once
+        per update -- the analysis agents make all their passes over the one augmented batch, and their evaluation batch stays as
+        sampled.  ``recycle_dormant``, acting and ``_q_row`` never come here."""
+        if not self.augment_pad:
+            return batch
+        if not hasattr(replay_buffer, "augment"):
+            raise ValueError("augment_pad > 0 needs the device replay (ReplayBuffer.augment): the shift runs on its frame store")
+        return replay_buffer.augment(batch, *self._aug_state())
+
+    def _aug_state(self):
+        """(pad, seed, device counter) of the augmentation.  The counter is made at first use: ``augment_pad`` may be switched on
+        behind the constructor (the live captured update is then captured again: _graphed_update)."""
+        check_augment(self.augment_pad, self.architecture_type)
+        if self.aug_count is None:
+            self._aug_seed = augment_seed(self._seed)
+            self.aug_count = torch.zeros(1, dtype=torch.int64, device=self._engine.device)
+        return int(self.augment_pad), self._aug_seed, self.aug_count
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
                            n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0, double_q=False,
                            munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False, dueling=False,
-                           max_grad_norm=0.0, noisy=False, noisy_sigma0=0.5):
+                           max_grad_norm=0.0, noisy=False, noisy_sigma0=0.5, augment_pad=0):
+        check_augment(augment_pad, architecture_type)
         check_noisy(noisy, architecture_type, batch_norm, max_grad_norm)
         self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
         self.noisy_eval = False  # True: acting calls run the mean network (zero noise) instead of drawing
@@ -152,6 +184,9 @@ class EngineAgent:
         self._trust_mirror = None  # None: the engine's default (_engine.py: rebuild in every call); see the property below
         self._ring = None  # device copy of the acting path's frame stack (see _obs_to_device)
         self._make_engine(batch_size, init=True)
+        self.augment_pad = int(augment_pad)
+        if self.augment_pad:  # (off: no buffer, no launch -- the agent is the one built without the argument)
+            self._aug_state()
 
     # ------------------------------------------------------------------ engine management
     def _make_engine(self, batch_size: int, init: bool = False) -> None:
@@ -248,12 +283,13 @@ class EngineAgent:
             raise ValueError("importance-sampling weights (set_importance_sampling) need the prioritized sampling distribution")
         g = self._graphed
         if (g is None or g.rb is not replay_buffer or g.eng is not eng or g.writeback != (writeback and prioritized)
-                or g.weighted != weighted or getattr(g, "key", None) != key or g.S != steps):
+                or g.weighted != weighted or getattr(g, "key", None) != key or g.S != steps or g.augment_pad != self.augment_pad):
             from slimdqn._graph import GraphedUpdate
 
             self._drop_graph()
             g = self._graphed = GraphedUpdate(replay_buffer, eng, prioritized, steps_per_graph=steps, writeback=writeback, learn=learn,
-                                              weighted=weighted)
+                                              weighted=weighted,
+                                              augment=self._aug_state() if self.augment_pad else None)
             g.key = key
             self._captures = getattr(self, "_captures", 0) + 1
         return g

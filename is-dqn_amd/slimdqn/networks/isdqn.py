@@ -61,8 +61,14 @@ class iSDQN(EngineAgent):
         max_grad_norm: float = 0.0,
         noisy: bool = False,
         noisy_sigma0: float = 0.5,
+        augment_pad: int = 0,
     ):
-        """``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
+        """``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
+        every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
+        [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
+        draws).  Acting, ``recycle_dormant`` and the evaluation passes see the frames as stored.  Every torso but 'fc' (ValueError);
+        needs the device replay.  0 is off.
+        ``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
         included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
         call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
         ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
@@ -109,7 +115,7 @@ class iSDQN(EngineAgent):
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
                                 n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical, dueling,
-                                max_grad_norm, noisy, noisy_sigma0)
+                                max_grad_norm, noisy, noisy_sigma0, augment_pad)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 

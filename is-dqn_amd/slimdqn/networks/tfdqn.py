@@ -54,8 +54,14 @@ class TFDQN(EngineAgent):
         max_grad_norm: float = 0.0,
         noisy: bool = False,
         noisy_sigma0: float = 0.5,
+        augment_pad: int = 0,
     ):
-        """``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
+        """``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
+        every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
+        [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
+        draws).  Acting and ``recycle_dormant`` see the frames as stored.  Every torso but 'fc' (ValueError); needs the device replay.
+        0 is off.
+        ``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
         included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
         call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
         ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
@@ -96,7 +102,7 @@ class TFDQN(EngineAgent):
                                 n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma, munchausen_tau=munchausen_tau,
                                 munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
                                 huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm,
-                                noisy=noisy, noisy_sigma0=noisy_sigma0)
+                                noisy=noisy, noisy_sigma0=noisy_sigma0, augment_pad=augment_pad)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54

@@ -61,7 +61,8 @@ class ReplayElement:
 class DeviceBatch:
     """A sampled batch (ReplayElement fields, replay_buffer.py:198-213) living on the GPU."""
 
-    def __init__(self, rb: "ReplayBuffer", indices, frame_ids, action, reward, is_terminal, weights=None):
+    def __init__(self, rb: "ReplayBuffer", indices, frame_ids, action, reward, is_terminal, weights=None, frames=None):
+        """``frames``: another frame pool than the replay's store that ``frame_ids`` point into, same stride (ReplayBuffer.augment)."""
         self._rb = rb
         self.weights = weights  # float32 [B] importance-sampling weights (prioritized sampling with a beta), else None
         self.indices = indices  # dense sampler indices (= sum-tree leaves), int32 [B]
@@ -69,7 +70,7 @@ class DeviceBatch:
         self.action = action  # int32 [B]
         self.reward = reward  # float32 [B]
         self.is_terminal = is_terminal  # uint8 [B]
-        self.frames = rb._frames
+        self.frames = rb._frames if frames is None else frames
         self.frame_stride = rb._hw
         self._stacks = None
 
@@ -193,6 +194,7 @@ class ReplayBuffer:
         self._frames = None
         self._obs_float = False
         self._h = self._w = self._hw = 0
+        self._aug_pools = {}  # n_rows -> (scratch frame pool, id table) of augmented batches (augment)
 
     # ------------------------------------------------------------------ storage
     def _allocate(self, obs_shape, floating: bool = False):
@@ -457,6 +459,46 @@ class ReplayBuffer:
             "isdqn_replay_gather_rows",
         )
         return DeviceBatch(self, indices, ids, action, reward, terminal, weights)
+
+    def _augment_pool(self, n_rows: int):
+        """The scratch frame pool and id table of an augmented batch of ``n_rows`` rows: allocated once per row count, then reused."""
+        pools = self._aug_pools
+        p = pools.get(n_rows)
+        if p is None or p[0].shape[1] != self._hw:
+            s2 = 2 * self._stack_size
+            p = pools[n_rows] = (torch.zeros(n_rows * s2, self._hw, dtype=torch.uint8, device=self.device),
+                                 torch.full((n_rows, s2), -1, dtype=torch.int32, device=self.device))
+        return p
+
+    def augment_into(self, frame_ids: torch.Tensor, n_rows: int, rows_per_step: int, pad: int, seed: int, count: torch.Tensor,
+                     out_frames: torch.Tensor, out_frame_ids: torch.Tensor) -> None:
+        """One isdqn_replay_augment_shift launch on the current stream: the frames that ``frame_ids`` [n_rows][2*stack] name in the
+        store, shifted, into ``out_frames``; the table into it in ``out_frame_ids``; ``count`` (device int64) advanced."""
+        if self._lib is None:
+            raise RuntimeError("ReplayBuffer.augment needs the HIP path (device='cuda:N'); there is no CPU fallback")
+        if self._obs_float:
+            raise ValueError("random-shift augmentation shifts uint8 image frames; this replay stores float32 vector observations")
+        _hip.check(
+            self._lib.isdqn_replay_augment_shift(
+                _hip.ptr(self._frames), self._hw, self._h, self._w, self._stack_size, _hip.ptr(frame_ids), n_rows, rows_per_step,
+                int(pad), int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(count), _hip.ptr(out_frames), _hip.ptr(out_frame_ids),
+                _hip.stream_ptr(self.device),
+            ),
+            "isdqn_replay_augment_shift",
+        )
+
+    def augment(self, batch: DeviceBatch, pad: int, seed: int, count: torch.Tensor) -> DeviceBatch:
+        """DrQ random-shift augmentation of a sampled batch (include/isdqn_hip.h, isdqn_replay_augment_shift): every state stack and
+        every next-state stack shifted by a draw of its own in [-pad, pad]^2 with replicated borders, keyed by ``seed`` and the device
+        counter ``count`` (int64 [1]), which the call advances by one step.  Returns a DeviceBatch whose ``frames`` / ``frame_ids`` are
+        the buffer's scratch pool and the table into it; action, reward, terminal, indices and weights are the sampled batch's own.
+        The pool belongs to the buffer, one per row count: the returned batch holds until the next ``augment`` of as many rows."""
+        if self._obs_float:
+            raise ValueError("random-shift augmentation shifts uint8 image frames; this replay stores float32 vector observations")
+        n_rows = len(batch)
+        pool, table = self._augment_pool(n_rows)
+        self.augment_into(batch.frame_ids, n_rows, n_rows, pad, seed, count, pool, table)
+        return DeviceBatch(self, batch.indices, table, batch.action, batch.reward, batch.is_terminal, batch.weights, frames=pool)
 
     def update(self, keys, **kwargs: Any) -> None:
         self._sampling_distribution.update(keys, **kwargs)
