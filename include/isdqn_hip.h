@@ -696,6 +696,49 @@ int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu, float* si
                                const isdqn_batch* batch, float* losses, float* losses_accum, float* q_values, float* targets,
                                double* priorities, void* workspace, void* stream);
 
+/* Periodic resets: re-initialise the top layers, shrink the rest towards a fresh initialisation, clear the optimizer state of what was
+ * touched (Nikishin et al. 2022, "The Primacy Bias in Deep RL"; shrink and perturb: Ash & Adams 2020; D'Oro et al. 2023, SR-SPR; Schwarzer
+ * et al. 2023, BBF).  The reference has no counterpart.  Built BESIDE the plan, like the noisy layers: no field of isdqn_net_config, no
+ * workspace region, no launch of any existing entry point.  On the device, in place, stream-ordered, capturable, without a host
+ * synchronisation, an allocation or an atomic.  Every configuration the plan accepts is accepted (cnn, impala, fc, layer_norm,
+ * batch_norm, every head): there is no ISDQN_ERR_UNSUPPORTED of its own.  THE definition:
+ * isdqn_net_reset_layout (host arithmetic on the plan, no GPU): *n_layers = the length of the layer list that isdqn_tensor_info::layer
+ * indexes (the impala torso is ONE entry of it); *first_dense_layer = the index of the first Dense layer (0 for fc).  Either may be NULL.
+ * isdqn_net_reset acts on every tensor isdqn_net_param_layout lists -- all kinds 0..8: kernels, biases, the LayerNorm tensors, the
+ * BatchNorm "params" tensors and the running mean / var -- over each tensor's whole internal (padded) size.  Floats of the buffer that
+ * belong to no tensor keep their bits.
+ *   Class: a tensor is UPPER iff info.layer >= split_layer, else LOWER (the BatchNorm sites in front of and inside the impala torso
+ *   carry negative layer numbers: always lower).  split_layer = 0: everything is upper; split_layer = n_layers: nothing is.
+ *   Each class has a factor pair (s, q) = (shrink, perturb).  With p the parameter and f the value at the same offset of fresh_params (a
+ *   buffer of the same layout, e.g. a new initialisation), fl32 the rounding to fp32:
+ *     s == 1 && q == 0   the class is not touched: parameters AND moments keep their bits, nothing is read or written;
+ *     s == 0             p' = fl32(q * f).  p is NOT read: a NaN or Inf parameter is replaced;
+ *     otherwise          p' = fl32(fl32(s * p) + fl32(q * f)) -- two products and one sum, each rounded on its own, never contracted
+ *                        into an FMA (a numpy float32 restatement gives the same bits).
+ *   In the two writing cases adam_m and adam_v (both NULL or both given) are set to +0.0f over the same elements.
+ *   With non-negative factors a position that is +0.0f in both params and fresh_params stays +0.0f: padding lanes and the structural
+ *   zeros of a dueling head survive a reset.
+ *   adam_count != NULL: *adam_count = 0, by an ordinary store in a launch of its own behind the element pass -- the next learn step runs
+ *   with the bias corrections of step 1.  NULL leaves the count alone.
+ *   workspace != NULL: the call ends by rebuilding the weight mirror from params (as isdqn_net_redo does): the mirror is current when
+ *   it returns.  NULL is for buffers that are no engine's `params`: a target copy, a noisy engine's sigma (fresh: the initial sigma).
+ *   Launches: one element launch over all written tensors through a table passed by value (at most 64 tensors per launch: the impala +
+ *   batch_norm table is split), 16 bytes per lane where the buffers are 16-byte aligned and the tensor's offset and size are multiples
+ *   of 4 floats, one element per lane otherwise; the grid is capped at 2048 workgroups and strides.
+ *   ISDQN_ERR_ARG, nothing launched: NULL params / fresh_params; exactly one of adam_m / adam_v NULL; a factor that is negative or not
+ *   finite; split_layer < 0 or > n_layers; fresh_params overlapping params (any byte of the two n_param_floats ranges).
+ * EMA (Polyak) target: isdqn_net_ema covers all n_param_floats elements of two buffers of the parameter layout (parameters, or a noisy
+ * engine's sigma buffers):    t' = fl32(fl32(omt * t) + fl32(tau * p)),   omt = fl32(1.0f - tau) computed once on the host
+ * (optax.incremental_update), the three operations rounded separately, never contracted.  tau == 0 launches nothing; tau == 1 copies
+ * the bits of `online` (a device-to-device copy: the sign of a zero and a non-finite target do not matter).  Plain loads and stores: the
+ * next step reads both buffers again.  16 bytes per lane when both pointers are 16-byte aligned, one element per lane otherwise.
+ * ISDQN_ERR_ARG: a NULL pointer, tau outside [0, 1] or NaN, target == online. */
+int isdqn_net_reset_layout(const isdqn_net_config* cfg, int32_t* n_layers, int32_t* first_dense_layer);
+int isdqn_net_reset(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, int32_t* adam_count,
+                    const float* fresh_params, int32_t split_layer, float shrink_lower, float perturb_lower, float shrink_upper,
+                    float perturb_upper, void* workspace, void* stream);
+int isdqn_net_ema(const isdqn_net_config* cfg, float* target, const float* online, float tau, void* stream);
+
 /* Engine self-test: C[M][N] = A . B on the MFMA tile engine for every operand-layout
  * combination (a_tr/b_tr: 0 = operand stored [rows][K], 1 = stored [K][rows]).  Test hook. */
 int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int32_t a_tr,

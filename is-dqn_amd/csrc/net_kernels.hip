@@ -3201,6 +3201,101 @@ extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu
     return ISDQN_OK;
 }
 
+// ---- periodic resets and EMA targets (reset.h; include/isdqn_hip.h, isdqn_net_reset / isdqn_net_ema) ----
+namespace isdqn {
+#include "reset.h"  // (behind every kernel the library had)
+}  // namespace isdqn
+
+extern "C" int isdqn_net_reset_layout(const isdqn_net_config* cfg, int32_t* n_layers, int32_t* first_dense_layer) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    int first = Pp->n_layers;
+    for (int i = Pp->n_layers - 1; i >= 0; --i)
+        if (Pp->L[i].kind == 1) first = i;
+    if (n_layers) *n_layers = Pp->n_layers;
+    if (first_dense_layer) *first_dense_layer = first;
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_reset(const isdqn_net_config* cfg, float* params, float* adam_m, float* adam_v, int32_t* adam_count,
+                               const float* fresh_params, int32_t split_layer, float shrink_lower, float perturb_lower, float shrink_upper,
+                               float perturb_upper, void* workspace, void* stream) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    const Plan& P = *Pp;
+    ISDQN_REQUIRE(params && fresh_params, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE((adam_m == nullptr) == (adam_v == nullptr), ISDQN_ERR_ARG, "adam_m and adam_v must be both null or both given");
+    const float fac[4] = {shrink_lower, perturb_lower, shrink_upper, perturb_upper};
+    for (float f : fac) ISDQN_REQUIRE(std::isfinite(f) && f >= 0.f, ISDQN_ERR_ARG, "every shrink / perturb factor must be finite and >= 0");
+    ISDQN_REQUIRE(split_layer >= 0 && split_layer <= P.n_layers, ISDQN_ERR_ARG, "split_layer must be in [0, n_layers]");
+    {
+        const uintptr_t a = (uintptr_t)params, b = (uintptr_t)fresh_params, bytes = (uintptr_t)P.n_params * 4;
+        ISDQN_REQUIRE(a + bytes <= b || b + bytes <= a, ISDQN_ERR_ARG, "fresh_params overlaps params");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool aligned = (((uintptr_t)params | (uintptr_t)fresh_params | (uintptr_t)adam_m | (uintptr_t)adam_v) & 15) == 0;
+    const bool touch[2] = {!(shrink_lower == 1.f && perturb_lower == 0.f), !(shrink_upper == 1.f && perturb_upper == 0.f)};
+    ResetTable tab;
+    tab.s[0] = shrink_lower; tab.q[0] = perturb_lower; tab.s[1] = shrink_upper; tab.q[1] = perturb_upper;
+    tab.n = 0;
+    tab.total_blocks = 0;
+    int launch_rc = ISDQN_OK;
+    auto flush = [&]() {
+        if (tab.n == 0 || launch_rc) return;
+        hipLaunchKernelGGL(reset_kernel, dim3(std::min(tab.total_blocks, RESET_MAX_BLOCKS)), dim3(RESET_THREADS), 0, st, tab, params, adam_m, adam_v,
+                           fresh_params);
+        if (hipGetLastError() != hipSuccess) {
+            set_last_error("isdqn_net_reset: kernel launch failed");
+            launch_rc = ISDQN_ERR_HIP;
+        }
+        tab.n = 0;
+        tab.total_blocks = 0;
+    };
+    for_each_param_tensor(P, [&](const isdqn_tensor_info& t) {
+        const int upper = t.layer >= split_layer ? 1 : 0;
+        if (!touch[upper] || t.size <= 0) return;
+        // one launch per tensor would do for a tensor of 2^31 * RESET_BLOCK_ELEMS elements; the plan's tensors hold fewer than 2^31
+        const int vec = (aligned && t.offset % 4 == 0 && t.size % 4 == 0) ? 2 : 0;
+        const int blocks = (int)((t.size + RESET_BLOCK_ELEMS - 1) / RESET_BLOCK_ELEMS);
+        if (tab.n == RESET_MAX_ENTRIES) flush();
+        tab.e[tab.n++] = ResetEntry{t.offset, t.size, tab.total_blocks, upper | vec};
+        tab.total_blocks += blocks;
+    });
+    flush();
+    if (launch_rc) return launch_rc;
+    if (adam_count != nullptr) {
+        hipLaunchKernelGGL(reset_count_kernel, dim3(1), dim3(64), 0, st, adam_count);
+        ISDQN_HIP_CHECK(hipGetLastError());
+    }
+    if (workspace != nullptr) return refresh_mirror(P, params, (float*)workspace, st);
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_ema(const isdqn_net_config* cfg, float* target, const float* online, float tau, void* stream) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    ISDQN_REQUIRE(target && online, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(tau >= 0.f && tau <= 1.f, ISDQN_ERR_ARG, "tau must be in [0, 1]");  // (NaN fails both comparisons)
+    ISDQN_REQUIRE(target != online, ISDQN_ERR_ARG, "target and online are the same buffer");
+    if (tau == 0.f) return ISDQN_OK;
+    const int64_t n = Pp->n_params;
+    hipStream_t st = (hipStream_t)stream;
+    if (tau == 1.f) {  // the bits of `online`, a NaN target and the sign of a zero included
+        ISDQN_HIP_CHECK(hipMemcpyAsync(target, online, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        return ISDQN_OK;
+    }
+    const bool aligned = (((uintptr_t)target | (uintptr_t)online) & 15) == 0;
+    const int64_t n4 = aligned ? n / 4 : 0;
+    const int64_t work = std::max<int64_t>(n4, n - 4 * n4);
+    const int64_t blocks = std::min<int64_t>((work + RESET_THREADS - 1) / RESET_THREADS, RESET_MAX_BLOCKS);
+    hipLaunchKernelGGL(ema_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(RESET_THREADS), 0, st, target, online, 1.0f - tau, tau, n4, n);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
 extern "C" int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K,
                                    int32_t a_tr, int32_t b_tr, int32_t precision, int32_t split_k, void* stream) {
     ISDQN_REQUIRE(A && B && C, ISDQN_ERR_ARG, "null pointer");

@@ -15,6 +15,7 @@ import time
 import numpy as np
 
 from experiments.base import dist as replicas
+from experiments.base.parser_argument import reset_kwargs
 from experiments.base.utils import save_data
 from slimdqn.sample_collection.utils import collect_single_sample, collect_vector_samples, linear_schedule
 
@@ -54,6 +55,10 @@ def train(key, p: dict, agent, env, rb):
             analysis_logs = {}
         analysis_logs["recycled_neurons"] = []
 
+    # Periodic resets (-reset, not in the reference): at every reset_frequency-th step, a target update, the agent's top layers are
+    # re-initialised and the rest shrunk towards a fresh initialisation on the device -- behind ReDo when both fall on the step
+    reset_frequency = p.get("reset_frequency", 0)
+
     def after_target_update(step, logs):
         if p.get("analysis"):  # dqn.py:54-58 of the reference
             from experiments.base.srank_and_dead_neurons import eval_srank_and_dead_neurons
@@ -66,6 +71,9 @@ def train(key, p: dict, agent, env, rb):
             recycled = agent.recycle_dormant(rb, p["redo_tau"])
             logs["recycled_neurons"] = recycled
             analysis_logs["recycled_neurons"].append(recycled)
+        if reset_frequency and step % reset_frequency == 0:
+            agent.reset_parameters(**reset_kwargs(p))
+            logs["reset"] = 1
         p["wandb"].log({"n_training_steps": step, **logs})
 
     def after_step():

@@ -66,6 +66,10 @@ _ENGINE = [
     ("-mqc", "--munchausen_clip", dict(type=float, default=-1.0, help="Lower clip l0 <= 0 of tau * ln pi(a|s). Means nothing without -mq.")),
     ("-redo", "--redo_frequency", dict(type=int, default=0, help="ReDo (Sokar et al. 2023): training steps between two recycles of the dormant neurons of the hidden layers (incoming weights re-initialised, outgoing weights and Adam moments zeroed, on the device); 0 = off. A positive multiple of -tuf. Not with -bn or -at impala.")),
     ("-redot", "--redo_tau", dict(type=float, default=0.1, help="ReDo threshold tau: a neuron is dormant when its mean activation is at most tau times its layer's mean. Means nothing without -redo.")),
+    ("-reset", "--reset_frequency", dict(type=int, default=0, help="Periodic resets (Nikishin et al. 2022; SR-SPR, BBF): training steps between two resets -- the top layers are re-initialised, the layers below shrunk towards a fresh initialisation (shrink and perturb), Adam's moments and step count cleared, on the device; a DQN's target network takes the same interpolation. 0 = off. A positive multiple of -tuf. With every torso and every agent.")),
+    ("-resets", "--reset_shrink", dict(type=float, default=0.5, help="Shrink factor in [0, 1] of the layers below the reset ones: p <- s * p + (1 - s) * fresh (BBF: 0.5; 1 keeps them). Means nothing without -reset.")),
+    ("-resetl", "--reset_top_layers", dict(type=int, default=0, help="Number of top layers that are re-initialised fully; 0 = every Dense layer (BBF, SR-SPR). Means nothing without -reset.")),
+    ("-ema", "--ema_tau", dict(type=float, default=0.0, help="EMA (Polyak) target network: target <- (1 - tau) * target + tau * online after every gradient step, on the device, instead of a copy every -tuf steps (BBF, SR-SPR: 0.005); 0 = off, in [0, 1]. DQN only: iS-DQN's target is a head of the online network, the target-free agents have none.")),
     ("-nenvs", "--n_envs", dict(type=int, default=1, help="Host environments stepped in lockstep with one batched best_actions forward (1 = the reference's loop).")),
     ("-nworkers", "--n_env_workers", dict(type=int, default=0, help="Host worker processes stepping the -nenvs environments in parallel (0 = in this process).")),
     ("-env", "--env_backend", dict(type=str, default="ale", choices=["ale", "synthetic"], help="'synthetic' replaces ALE by random frames (no ROMs needed).")),
@@ -242,6 +246,50 @@ def check_redo(p: dict) -> None:
         if not (math.isfinite(p["redo_tau"]) and p["redo_tau"] >= 0.0):
             raise ValueError("-redot / --redo_tau must be finite and >= 0")
         check(p["architecture_type"], bool(p.get("batch_norm", False)))
+
+
+# (-reset, -resets and -resetl stay out of parameters.json like -redo)
+RESET_FREQUENCY_REFUSED = "-reset / --reset_frequency must be a positive multiple of -tuf / --target_update_frequency (resets happen at target updates)"
+RESET_SHRINK_REFUSED = "-resets / --reset_shrink must be in [0, 1]"
+RESET_TOP_LAYERS_REFUSED = "-resetl / --reset_top_layers must be >= 0 (0: every Dense layer)"
+
+
+def check_reset(p: dict) -> None:
+    """-reset that is no positive multiple of -tuf, a shrink factor outside [0, 1] or a negative layer count fails before anything is
+    written.  Without -reset the other two flags mean nothing and are not looked at."""
+    if p.get("reset_frequency", 0) != 0:
+        if p["reset_frequency"] < 0 or p["reset_frequency"] % p["target_update_frequency"] != 0:
+            raise ValueError(RESET_FREQUENCY_REFUSED)
+        if not 0.0 <= p["reset_shrink"] <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(RESET_SHRINK_REFUSED)
+        if p["reset_top_layers"] < 0:
+            raise ValueError(RESET_TOP_LAYERS_REFUSED)
+
+
+def reset_kwargs(p) -> dict:
+    """The keywords of ``agent.reset_parameters`` from parsed parameters."""
+    return dict(shrink=float(p["reset_shrink"]), n_top_layers=int(p["reset_top_layers"]))
+
+
+# (-ema stays out of parameters.json like -redo)
+EMA_ALGOS = ("dqn",)
+EMA_TAU_REFUSED = "-ema / --ema_tau must be in [0, 1] (0 = off)"
+
+
+def check_ema(p: dict, algo_name: str) -> None:
+    """-ema outside [0, 1], or > 0 on any agent but DQN (the agents' own message), fails before anything is written."""
+    tau = p.get("ema_tau", 0.0)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError(EMA_TAU_REFUSED)
+    if tau > 0.0 and algo_name not in EMA_ALGOS:
+        from slimdqn.networks._agent import EMA_REFUSED
+
+        raise ValueError(EMA_REFUSED)
+
+
+def ema_kwargs(p) -> dict:
+    """The agents' EMA keyword from parsed parameters; without -ema the keywords are the ones they were before the flag existed."""
+    return dict(ema_tau=float(p["ema_tau"])) if p.get("ema_tau") else {}
 
 
 def check_engine_arguments(p: dict) -> None:

@@ -833,6 +833,61 @@ class QNetEngine:
         self._mirror_holds(None)
         return list(torch.split(scores, widths)), list(torch.split(mask, widths)), n_recycled
 
+    # ------------------------------------------------------------------ periodic resets, EMA targets
+    def reset_layout(self) -> tuple:
+        """(n_layers, first_dense_layer) of the layer list ``infos[i].layer`` indexes (include/isdqn_hip.h, isdqn_net_reset_layout)."""
+        n, first = ctypes.c_int32(), ctypes.c_int32()
+        _hip.check(self.lib.isdqn_net_reset_layout(ctypes.byref(self.cfg), ctypes.byref(n), ctypes.byref(first)), "isdqn_net_reset_layout")
+        return int(n.value), int(first.value)
+
+    def reset(self, fresh: torch.Tensor, split_layer: int | None = None, shrink_lower: float = 0.5, perturb_lower: float = 0.5,
+              shrink_upper: float = 0.0, perturb_upper: float = 1.0, params: torch.Tensor | None = None, moments: bool = True,
+              count: bool = True) -> None:
+        """Shrink-and-perturb reset (include/isdqn_hip.h, isdqn_net_reset) towards ``fresh`` (internal layout: ``fresh_params``): tensors of
+        layer >= ``split_layer`` (default: the first Dense layer) take the upper factor pair, the others the lower one.  ``params`` None:
+        the engine's own parameters, with ``adam_m`` / ``adam_v`` cleared where written (``moments``), ``adam_count`` zeroed (``count``)
+        and the weight mirror rebuilt.  Another buffer of the layout (a target copy, a sigma buffer): that buffer alone -- no moments, no
+        count, no mirror; a noisy engine's own ``sigma`` is recognised and takes ``sigma_m`` / ``sigma_v`` as its moments.  One
+        stream-ordered call; no pointer moves."""
+        assert fresh.dtype == torch.float32 and fresh.numel() == self.n_param_floats and fresh.is_contiguous() and fresh.device == self.params.device
+        if split_layer is None:
+            split_layer = self.reset_layout()[1]
+        own = params is None
+        m = v = cnt = None
+        if own:
+            params = self.params
+            if moments:
+                m, v = self.adam_m, self.adam_v
+            cnt = self.adam_count if count else None
+        elif self.noisy and params is self.sigma and moments:
+            m, v = self.sigma_m, self.sigma_v
+        _hip.check(
+            self.lib.isdqn_net_reset(
+                ctypes.byref(self.cfg), _hip.ptr(params), _hip.ptr(m), _hip.ptr(v), _hip.ptr(cnt), _hip.ptr(fresh), int(split_layer),
+                float(shrink_lower), float(perturb_lower), float(shrink_upper), float(perturb_upper),
+                _hip.ptr(self.workspace) if own else 0, _hip.stream_ptr(self.device),
+            ),
+            "isdqn_net_reset",
+        )
+        if own:
+            # as in redo: the raw-pointer write does not move torch's version counter and the call's last launch rebuilt the mirror from
+            # the new parameters (a noisy engine: the mirror no longer holds eff, and _mirror_holds marks it as not holding params)
+            self._mirror_holds(None)
+
+    def ema(self, target: torch.Tensor, tau: float, online: torch.Tensor | None = None) -> None:
+        """target <- (1 - tau) * target + tau * online (include/isdqn_hip.h, isdqn_net_ema; ``online`` None: the engine's parameters) over
+        two buffers of the parameter layout, one stream-ordered launch."""
+        online = self.params if online is None else online
+        assert target.dtype == torch.float32 and target.numel() == self.n_param_floats and online.numel() == self.n_param_floats
+        _hip.check(self.lib.isdqn_net_ema(ctypes.byref(self.cfg), _hip.ptr(target), _hip.ptr(online), float(tau), _hip.stream_ptr(self.device)),
+                   "isdqn_net_ema")
+
+    def fresh_sigma(self) -> torch.Tensor:
+        """A new device tensor holding what ``init_sigma`` writes into ``sigma``: the source of a reset of sigma."""
+        t = torch.empty_like(self.params)
+        self._import_sigma(self._sigma_tree(), t)
+        return t
+
     # ------------------------------------------------------------------ weight-mirror bookkeeping
     # The library keeps a pre-split mirror of the weights in the workspace and rebuilds it at the head of every call unless
     # told that it is current.  DEFAULT: never told -- every entry point outside a captured replay rebuilds (one 8 us launch),

@@ -18,7 +18,7 @@ from slimdqn import _hip
 
 class GraphedUpdate:
     def __init__(self, rb, eng, prioritized: bool, steps_per_graph: int = 8, writeback: bool | None = None, learn=None,
-                 weighted: bool = False, augment=None):
+                 weighted: bool = False, augment=None, state=()):
         """``prioritized``: the sampler is a sum tree (the query is part of the graph); ``writeback``: sqrt(mean_k td) of
         every step goes back into the tree (default: whenever prioritized); ``learn``: the learn call of one step on a C batch
         (default ``eng.learn_on_batch``; DQN passes its target-parameter form, dqn.py:59-72); ``weighted``: the query also writes
@@ -27,8 +27,10 @@ class GraphedUpdate:
         replay with other betas is the same executable graph.  ``augment``: (pad, seed, device counter) of the random-shift augmentation
         (include/isdqn_hip.h, isdqn_replay_augment_shift) or None -- the gathered rows' frames are shifted into a scratch pool inside the
         graph and every step's batch reads the pool; the counter lives on the device, so every replay draws anew and lands on the
-        draws the eager steps would have taken."""
+        draws the eager steps would have taken.  ``state``: device tensors besides the engine's own that ``learn`` writes (DQN with
+        ``ema_tau``: the target buffers) -- the warm-up steps of a capture must not count on them either."""
         self.augment = augment
+        self._learn_state = list(state)
         self.augment_pad = int(augment[0]) if augment else 0
         if weighted and not prioritized:
             raise ValueError("importance-sampling weights need the prioritized sampling distribution")
@@ -214,6 +216,7 @@ class GraphedUpdate:
             training += [self.eng.sigma, self.eng.sigma_m, self.eng.sigma_v, self.eng.noise_count]
         if self.augment:  # (the warm-up's draws must not count: the captured steps take the draws the eager steps would)
             training.append(self.augment[2])
+        training += self._learn_state
         state = [t.clone() for t in training]
         # (prioritized: the warm-up also writes priorities back -- with the zero-filled draw block -- so the whole tree
         # state is saved: nodes, max_recorded_priority, which every later add() reads, and the latched status word)

@@ -198,6 +198,13 @@ _SIGNATURES = {
         [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          POINTER(Batch), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    # periodic resets and EMA targets (include/isdqn_hip.h, isdqn_net_reset / isdqn_net_ema)
+    "isdqn_net_reset_layout": (c_int32, [POINTER(NetConfig), POINTER(c_int32), POINTER(c_int32)]),
+    "isdqn_net_reset": (
+        c_int32,
+        [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p],
+    ),
+    "isdqn_net_ema": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_float, c_void_p]),
     "isdqn_selftest_gemm": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],

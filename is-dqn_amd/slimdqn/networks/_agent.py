@@ -77,6 +77,28 @@ def recycle_seed(seed: int, k: int) -> int:
     return int.from_bytes(state.tobytes(), "little")
 
 
+def reset_seed(seed: int, k: int) -> int:
+    """Seed of the fresh parameters of the agent's k-th reset (0-based): a child of the agent's seed in numpy's SeedSequence tree under a
+    spawn key of its own ((3, k); ``recycle_seed`` has (1, k), ``augment_seed`` (2,)), never the seed itself."""
+    state = np.random.SeedSequence(entropy=int(seed), spawn_key=(3, int(k))).generate_state(4)
+    return int.from_bytes(state.tobytes(), "little")
+
+
+EMA_REFUSED = (
+    "ema_tau > 0 needs a target network held in a buffer of its own: only DQN has one (iS-DQN's target is a head of the online "
+    "parameters, moved by the head shift; the target-free agents have none)")
+
+
+def check_ema_tau(ema_tau, supported: bool = False) -> float:
+    """ema_tau of an agent's constructor: in [0, 1] (NaN refused), and 0 for every agent but DQN (EMA_REFUSED)."""
+    tau = float(ema_tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("ema_tau must be in [0, 1] (0 = off: hard target updates)")
+    if tau > 0.0 and not supported:
+        raise ValueError(EMA_REFUSED)
+    return tau
+
+
 def augment_seed(seed: int) -> int:
     """64-bit seed of the agent's random-shift draws: a child of the agent's seed in numpy's SeedSequence tree under a spawn key of its
     own ((2,); ``recycle_seed`` has (1, k)), never the seed itself."""
@@ -264,10 +286,11 @@ class EngineAgent:
         if g is not None:
             g.destroy()
 
-    def _graphed_update(self, replay_buffer, learn=None, key=None, steps: int = 1):
+    def _graphed_update(self, replay_buffer, learn=None, key=None, steps: int = 1, state=()):
         """The captured sample -> learn -> [write-back] update of ``steps`` consecutive steps for this (replay, engine) pair, or None
         when the replay is not the device replay of this GPU (reference-layout buffers take the eager path).  ``learn`` / ``key``:
-        another learn call than the engine's learn_on_batch and what it is bound to (DQN: the target parameters' buffer).  The agent
+        another learn call than the engine's learn_on_batch and what it is bound to (DQN: the target parameters' buffer); ``state``:
+        the device tensors that call writes besides the engine's own (GraphedUpdate).  The agent
         owns ONE executable graph at a time: a request that does not match the live one destroys it first, then captures."""
         if not getattr(self, "use_graph", True) or not hasattr(replay_buffer, "_d_elem_frames") or getattr(replay_buffer, "_lib", None) is None:
             return None
@@ -289,7 +312,7 @@ class EngineAgent:
             self._drop_graph()
             g = self._graphed = GraphedUpdate(replay_buffer, eng, prioritized, steps_per_graph=steps, writeback=writeback, learn=learn,
                                               weighted=weighted,
-                                              augment=self._aug_state() if self.augment_pad else None)
+                                              augment=self._aug_state() if self.augment_pad else None, state=state)
             g.key = key
             self._captures = getattr(self, "_captures", 0) + 1
         return g
@@ -590,6 +613,40 @@ class EngineAgent:
         self._recycles += 1
         _, _, n_recycled = eng.redo(n_rows=n, tau=float(tau), fresh=fresh, **inputs)
         return [int(c) for c in n_recycled.cpu().numpy()]
+
+    # ------------------------------------------------------------------ periodic resets
+    _resets = 0  # resets done so far: selects the seed of the next fresh parameters
+
+    def reset_parameters(self, shrink: float = 0.5, n_top_layers: int = 0) -> None:
+        """Periodic reset (Nikishin et al. 2022; SR-SPR, BBF; include/isdqn_hip.h, isdqn_net_reset) towards a new initialisation drawn
+        from ``reset_seed(seed, k)``: the top layers -- every Dense layer with ``n_top_layers`` = 0 (the whole fc network), else the
+        last ``n_top_layers`` entries of the layer list -- are re-initialised, the layers below are shrunk and perturbed, p <-
+        shrink * p + (1 - shrink) * fresh, and Adam's moments of everything written and its step count are cleared.  iS-DQN's
+        1 + K heads share the last Dense and are reset together, the target head included.  A target copy (DQN, AnalysisDQN)
+        takes the same interpolation towards the SAME fresh parameters (BBF), without moments.  Noisy agents: ``sigma`` (and DQN's
+        ``target_sigma``) takes the same rule towards its initial value, its moments cleared.  Everything runs on the device in
+        stream order; no pointer moves and the weight mirror is left current, so a live captured update stays valid."""
+        eng = self._engine
+        n_layers, first_dense = eng.reset_layout()
+        if not 0.0 <= float(shrink) <= 1.0:
+            raise ValueError("shrink must be in [0, 1]")
+        if not 0 <= int(n_top_layers) <= n_layers:
+            raise ValueError(f"n_top_layers must be in [0, {n_layers}] (the length of the layer list)")
+        s = np.float32(shrink)
+        factors = dict(split_layer=first_dense if int(n_top_layers) == 0 else n_layers - int(n_top_layers), shrink_lower=float(s),
+                       perturb_lower=float(np.float32(1.0) - s), shrink_upper=0.0, perturb_upper=1.0)
+        fresh = eng.fresh_params(reset_seed(self._seed, self._resets))
+        self._resets += 1
+        eng.reset(fresh, **factors)
+        self._grad_clip_count = 0  # (the step count _grad_clip_logs measures its interval with starts again)
+        target = getattr(self, "target_params", None)
+        if target is not None and target.tensor is not eng.params:
+            eng.reset(fresh, params=target.tensor, **factors)
+        if getattr(self, "noisy", False):
+            fresh_sigma = eng.fresh_sigma()
+            eng.reset(fresh_sigma, params=eng.sigma, **factors)
+            if getattr(self, "target_sigma", None) is not None:
+                eng.reset(fresh_sigma, params=self.target_sigma, **factors)
 
     # generic forms (one head, per-step replays); iSDQN overrides both
     def best_actions_planes(self, params, planes, rows, key=None, wait: bool = True):

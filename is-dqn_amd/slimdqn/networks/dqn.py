@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from slimdqn._engine import check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles
-from slimdqn.networks._agent import DeviceParams, EngineAgent
+from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -50,8 +50,13 @@ class DQN(EngineAgent):
         noisy: bool = False,
         noisy_sigma0: float = 0.5,
         augment_pad: int = 0,
+        ema_tau: float = 0.0,
     ):
-        """``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
+        """``ema_tau`` > 0: EMA (Polyak) target network (include/isdqn_hip.h, isdqn_net_ema; SR-SPR, BBF) -- every gradient step is
+        followed by target <- (1 - tau) * target + tau * online on the device (noisy: ``target_sigma`` likewise), in the eager step
+        and inside the captured one, on the step's own stream; ``update_target_params`` then copies nothing and only reports its
+        logs.  0 keeps the hard copy every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
+        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
         every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
         [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
         draws).  Acting and ``recycle_dormant`` see the frames as stored.  Every torso but 'fc' (ValueError); needs the device replay.
@@ -92,6 +97,7 @@ class DQN(EngineAgent):
         check_grad_clip(max_grad_norm, architecture_type, False)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
         check_quantiles(n_quantiles, n_bins, munchausen_tau)
+        self.ema_tau = check_ema_tau(ema_tau, supported=True)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
         self.data_to_update = data_to_update
@@ -116,23 +122,43 @@ class DQN(EngineAgent):
         if step % self.data_to_update == 0:
             target = self._target_tensor(self.target_params)
             eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
-            g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw()), key=target.data_ptr())
+            if self.ema_tau > 0.0:
+                # the learn call and the EMA of the target behind it, enqueued on one stream: the captured step gets no new branch.
+                # (the target buffers are state of the step now: a capture's warm-up must not move them)
+                def learn(cb):
+                    eng.learn_on_batch_target(cb, target, **self._target_sigma_kw())
+                    self._ema_target(eng, target)
+
+                g = self._graphed_update(replay_buffer, learn=learn, key=(target.data_ptr(), self.ema_tau),
+                                         state=[target] + ([self.target_sigma] if self.noisy else []))
+            else:
+                g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw()), key=target.data_ptr())
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
                 g.run(self._next_betas(g.S))
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.target_params, self.optimizer_state, batch_samples)
+            if self.ema_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
+                self._ema_target(self._engine, target)
             if getattr(self, "priority_writeback", False) and hasattr(replay_buffer, "update_device"):  # (as the captured step does)
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_loss += loss` (dqn.py:47) happens on the device inside the step
 
+    def _ema_target(self, eng, target: torch.Tensor) -> None:
+        """target <- (1 - ema_tau) * target + ema_tau * online behind a gradient step (noisy: the target's sigma likewise)."""
+        eng.ema(target, self.ema_tau)
+        if self.noisy:
+            eng.ema(self.target_sigma, self.ema_tau, online=eng.sigma)
+
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:
             # `self.target_params = self.params.copy()` (dqn.py:50) as an in-place refresh of ONE persistent buffer: the captured
-            # step reads the target through a fixed pointer, so a target update neither re-captures nor re-instantiates a graph
-            self.target_params.tensor.copy_(self.params.tensor)
-            if self.noisy:
-                self.target_sigma.copy_(self._engine.sigma)
+            # step reads the target through a fixed pointer, so a target update neither re-captures nor re-instantiates a graph.
+            # With ema_tau > 0 the target follows every gradient step instead: nothing is copied here
+            if not self.ema_tau > 0.0:
+                self.target_params.tensor.copy_(self.params.tensor)
+                if self.noisy:
+                    self.target_sigma.copy_(self._engine.sigma)
             eng = self._engine
             self.cumulated_loss = self.cumulated_loss + float(eng.losses_accum.cpu().numpy()[0])
             eng.losses_accum.zero_()

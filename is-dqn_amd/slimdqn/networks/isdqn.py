@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles
-from slimdqn.networks._agent import DeviceParams, EngineAgent
+from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -62,8 +62,10 @@ class iSDQN(EngineAgent):
         noisy: bool = False,
         noisy_sigma0: float = 0.5,
         augment_pad: int = 0,
+        ema_tau: float = 0.0,
     ):
-        """``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
+        """``ema_tau`` > 0 is refused (EMA_REFUSED): the target is head 0 of the online parameters.
+        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
         every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
         [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
         draws).  Acting, ``recycle_dormant`` and the evaluation passes see the frames as stored.  Every torso but 'fc' (ValueError);
@@ -97,6 +99,7 @@ class iSDQN(EngineAgent):
         ``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss.
         ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
         cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
+        check_ema_tau(ema_tau)
         check_dueling(dueling, architecture_type, features, batch_norm)
         check_grad_clip(max_grad_norm, architecture_type, batch_norm)
         check_munchausen(double_q, munchausen_tau)

@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from slimdqn._engine import check_categorical, check_dueling, check_grad_clip, check_quantiles
-from slimdqn.networks._agent import EngineAgent
+from slimdqn.networks._agent import EngineAgent, check_ema_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -55,8 +55,10 @@ class TFDQN(EngineAgent):
         noisy: bool = False,
         noisy_sigma0: float = 0.5,
         augment_pad: int = 0,
+        ema_tau: float = 0.0,
     ):
-        """``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
+        """``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.
+        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
         every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
         [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
         draws).  Acting and ``recycle_dormant`` see the frames as stored.  Every torso but 'fc' (ValueError); needs the device replay.
@@ -89,6 +91,7 @@ class TFDQN(EngineAgent):
         ``double_q`` is refused: see DOUBLE_Q_REFUSED."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
+        check_ema_tau(ema_tau)
         check_dueling(dueling, architecture_type, features, batch_norm)
         check_grad_clip(max_grad_norm, architecture_type, batch_norm)
         check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
