@@ -180,6 +180,48 @@ int isdqn_replay_augment_shift(const uint8_t* frames, int64_t frame_stride, int3
                                int32_t pad, uint64_t seed, int64_t* aug_count,
                                uint8_t* out_frames /* [n_rows*2*stack][frame_stride] */, int32_t* out_frame_ids, void* stream);
 
+/* Horizon windows: an annealed update horizon and discount (SR-SPR, BBF: n 10 -> 3, gamma 0.97 -> 0.997 after every reset).
+ * The tables above fix an element's n-step return and next-state stack on the host when the element is added.  A replay built
+ * with horizon windows keeps three more tables per element slot, for the largest horizon n_max (1..128) it will serve.  For an
+ * element whose state ends at position s of a trajectory of L steps:
+ *   elem_window [C][stack + n_max] int32  the frame ids at positions s - stack + 1 .. s + n_max, -1 where the reference has a zero
+ *                                         frame (in front of the trajectory, or behind its end);
+ *   elem_steps  [C][n_max] float          the per-step rewards from s on (after reward clipping, where set), 0 behind the end;
+ *   elem_len    [C] int32                 min(s + n_max, L) - s: how many of those steps lie inside the trajectory;
+ * and elem_terminal is the element's terminal flag at n_max.  For any horizon m <= n_max that gives the element the reference builds
+ * at update_horizon = m: next state = window[m : m + stack], return = the discounted sum of the first min(m, len) rewards, terminal =
+ * terminal_nmax && m >= len.  (The states within n_max - m steps in front of a truncation, which a buffer at m emits and one at n_max
+ * never does, are not in it.)
+ *
+ * The scatter of the three tables' staged rows, beside isdqn_replay_apply_staged and from the same staged buffer: byte offsets into
+ * `staged` of rows int32 [n_rows] (the element slots), window int32 [n_rows][stack + n_max], steps float [n_rows][n_max] and len
+ * int32 [n_rows].  ISDQN_ERR_ARG: a NULL pointer, n_rows < 0, stack < 1, n_max outside 1..128, a negative or misaligned offset.
+ * n_rows == 0 launches nothing. */
+int isdqn_replay_apply_staged_horizon(const uint8_t* staged, int32_t n_rows, int64_t off_rows, int64_t off_window, int64_t off_steps,
+                                      int64_t off_len, int32_t stack, int32_t n_max, int32_t* elem_window, float* elem_steps,
+                                      int32_t* elem_len, void* stream);
+
+/* The gather of a horizon-window replay: B sampled rows, cut at a horizon and discounted at a rate that the kernel READS FROM DEVICE
+ * MEMORY (`horizon`: one int32, `gamma`: one float), so a captured graph follows a schedule without a second capture, as it does the
+ * importance-sampling exponent.  `slots` and `index_to_slot` as in isdqn_replay_gather_rows.
+ * THE definition, for row b with element slot e:
+ *   m = clamp(*horizon, 1, n_max), me = min(m, elem_len[e]);
+ *   out_frame_ids[b][0 .. stack)       = elem_window[e][0 .. stack);
+ *   out_frame_ids[b][stack .. 2 stack) = elem_window[e][m .. m + stack);
+ *   in float64 with G = (double)*gamma: g_0 = 1, g_{t+1} = g_t * G, acc_0 = 0, acc_{t+1} = acc_t + (double)elem_steps[e][t] * g_t, t
+ *     ascending, every operation rounded on its own (no fused multiply-add);
+ *   out_reward[b]   = (float)acc_me;
+ *   out_discount[b] = (float)g_m -- m, not me: the two differ only on terminal rows, whose bootstrap is masked.  It is what
+ *     isdqn_batch_discount::discount takes;
+ *   out_terminal[b] = elem_terminal[e] && m >= elem_len[e];
+ *   out_action[b]   = elem_action[e].
+ * One launch, plain loads and stores, no atomics; a row's sum runs sequentially in one lane, the id copy goes over lanes.
+ * ISDQN_ERR_ARG, and nothing is launched: a NULL pointer (index_to_slot may be NULL), B < 1, stack < 1, n_max outside 1..128. */
+int isdqn_replay_gather_horizon(const int32_t* elem_window, const float* elem_steps, const int32_t* elem_len, const int32_t* elem_action,
+                                const uint8_t* elem_terminal, int32_t stack, int32_t n_max, const int32_t* index_to_slot,
+                                const int32_t* slots, int32_t B, const int32_t* horizon, const float* gamma, int32_t* out_frame_ids,
+                                int32_t* out_action, float* out_reward, uint8_t* out_terminal, float* out_discount, void* stream);
+
 /* ========================================================================== */
 /* Q-network + iS-DQN update  (slimdqn/networks/architectures/dqn.py, isdqn.py) */
 /* ========================================================================== */
@@ -500,12 +542,27 @@ typedef struct isdqn_batch {
                                * learn / loss / their _target forms / grad_on_batch */
 } isdqn_batch;
 
+/* Per-transition discounts (an annealed update horizon: isdqn_replay_gather_horizon's out_discount, gamma ** m at the step's horizon).
+ * isdqn_batch keeps its size and its fields: a caller that has discounts hands every entry point that takes a batch the address of
+ * the `batch` member of an isdqn_batch_discount and sets ISDQN_BATCH_DISCOUNT in batch.flags, which tells the library that the
+ * discount pointer follows the batch.  Without the flag nothing behind the batch is read and every result keeps its bits.
+ * discount: [B] device floats, finite and >= 0 (the caller's contract, as for the weights), or NULL (= no flag).  Otherwise discount[b]
+ * stands wherever cfg->gamma_n stands for row b -- the scalar TD target, the head chain, the HL-Gauss, quantile and categorical targets,
+ * and the Munchausen and double-Q forms of each -- and cfg->gamma_n is ignored.  Honoured by learn / loss / their _target and debug
+ * forms / grad_on_batch / isdqn_noisy_learn_on_batch, every torso. */
+typedef struct isdqn_batch_discount {
+    isdqn_batch batch;     /* flags carries ISDQN_BATCH_DISCOUNT */
+    const float* discount; /* [B] */
+} isdqn_batch_discount;
+
 /* The workspace keeps a pre-split (bf16 hi + lo) mirror of the weights that the MFMA stages copy from.  Every entry point
  * rebuilds it from `params` first -- `params` is caller-owned memory -- unless the caller passes this flag, promising that
  * the previous call on this workspace was isdqn_net_learn_on_batch with the same `params` and that nothing has written
  * `params` since (learn_on_batch leaves the mirror current: Adam writes both forms).  The captured multi-step graphs of
  * slimdqn/_graph.py use it for every step of a replay (isdqn_net_refresh_mirror in front of a replay when needed). */
 #define ISDQN_BATCH_MIRROR_CURRENT 1
+/* The batch is the first member of the struct isdqn_batch_discount above. */
+#define ISDQN_BATCH_DISCOUNT 2
 
 /* DQNNet.apply on `n_rows` observations (dqn.py:47-103) -> q [n_rows][n_heads*n_actions].
  * cnn: image j reads frame_ids[j*stack .. j*stack+stack-1]; fc: obs [n_rows][obs_c]. */

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(C51_THREADS) void c51_loss_kernel(const HeadLossArg
         // p_j = softmax(l^val(s', a*))_j and the position b_j of the pushed atom on the support, in the lanes that own j
         float v[PER_LANE], e[PER_LANE], p[PER_LANE], bpos[PER_LANE], mi[PER_LANE], s, w;
         hl_softmax_parts(nrow + (int64_t)best * nb, nb, lane, vmin, eta, v, e, &s, &w);
-        const float disc = st.nt[bl] * a.gamma_n;
+        const float disc = st.nt[bl] * st.g[bl];
         const float tg = st.r[bl] + disc * (w / s);
 #pragma unroll
         for (int t = 0; t < PER_LANE; ++t) {

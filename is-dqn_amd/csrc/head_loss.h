@@ -2,6 +2,7 @@
 // (quantile.h) and c51_loss_kernel (categorical.h).  loss_and_finalize (net_kernels.hip) fills one HeadLossArgs and launches the one
 // the plan selects; each regresses online head on0 + k at the taken action on head tg0 + k of the next-state rows, k < K.
 //
+// A transition's discount is isdqn_batch_discount::discount[b] where the batch carries the tensor, else gamma_n (cfg->gamma_n).
 // THE contract of a loss kernel -- what it writes from the head-output rows of a finished forward:
 //   q_values / targets [B][K]  the scalar Q of the online head at the taken action and the unclamped scalar target (null: not written);
 //   priorities [B]             sqrt(mean_k (q - target)^2 + 1e-10) on those scalars, never weighted by loss_weights (null: not written)
@@ -45,6 +46,7 @@ struct HeadLossArgs {
     const float* reward;
     const uint8_t* terminal;
     const float* loss_weights;               // (null: 1)
+    const float* discount;                   // isdqn_batch_discount::discount: the row's discount in gamma_n's place (null: gamma_n)
     float gamma_n;
     float *dout, *q_values, *targets;
     double* priorities;
@@ -67,6 +69,7 @@ __device__ __forceinline__ float wave_max(float v) {
 struct LossStage {
     int action[MAX_ROWS];
     float r[MAX_ROWS], nt[MAX_ROWS], w[MAX_ROWS];  // nt: 1 - terminal; w: importance-sampling weights (none: 1)
+    float g[MAX_ROWS];                              // the row's discount (isdqn_batch_discount::discount; none: gamma_n)
     float loss[MAX_ROWS * 64], td2[MAX_ROWS * 64];  // weighted loss; (q - target)^2, unweighted (0 on padded rows, stored by the kernel)
 };
 
@@ -91,6 +94,8 @@ __device__ __forceinline__ void loss_prologue(const HeadLossArgs& a, LossStage& 
         s.r[tid] = on ? a.reward[b0 + tid] : 0.f;
         s.nt[tid] = on ? 1.f - (float)a.terminal[b0 + tid] : 0.f;
         s.w[tid] = (on && a.loss_weights != nullptr) ? a.loss_weights[b0 + tid] : 1.f;
+        if (on && a.discount != nullptr) ISDQN_BOUNDS_CHECK(a.discount + b0 + tid, 4, 50);
+        s.g[tid] = (on && a.discount != nullptr) ? a.discount[b0 + tid] : a.gamma_n;
     }
 }
 

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const HeadLossArgs a) {
     const float *__restrict__ logits = a.out, *__restrict__ vlogits = a.val, *__restrict__ slogits = a.sel, *mlogits = a.mun;
     float *__restrict__ q_values = a.q_values, *__restrict__ targets = a.targets;
     const int B = a.B, R = a.R, K = a.K, A = a.A, nb = a.nb, nlog_p = a.pitch;
-    const float vmin = a.vmin, eta = a.eta, gamma_n = a.gamma_n;
+    const float vmin = a.vmin, eta = a.eta;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b0 = blockIdx.x * R;
     const int rows = min(R, B - b0);
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const HeadLossArgs a) {
             float qa = 0.f, unused;
             const float vs = hl_soft_value(srow, A, nb, lane, vmin, eta, a.mu.tau, st.action[bl], &qa);
             const float vn = hl_soft_value(nrow, A, nb, lane, vmin, eta, a.mu.tau, -1, &unused);
-            tg_m = munchausen_target(st.r[bl], st.nt[bl], gamma_n, qa, vs, vn, a.mu);
+            tg_m = munchausen_target(st.r[bl], st.nt[bl], st.g[bl], qa, vs, vn, a.mu);
             mx = 0.f;
         } else if (slogits != nullptr) {  // Double Q-learning: the selector head decides, the value head supplies the value
             const float* srow = slogits + (int64_t)b * a.sel_pitch + (int64_t)(a.sel_head + k) * ldk;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const HeadLossArgs a) {
         } else {
             for (int a2 = 0; a2 < A; ++a2) mx = fmaxf(mx, hl_expectation(nrow + (int64_t)a2 * nb, nb, lane, vmin, eta));
         }
-        const float tg = mlogits != nullptr ? tg_m : st.r[bl] + st.nt[bl] * gamma_n * mx;
+        const float tg = mlogits != nullptr ? tg_m : st.r[bl] + st.nt[bl] * st.g[bl] * mx;
         float v[PER_LANE], e[PER_LANE], s, w;
         const float m = hl_softmax_parts(logits + (int64_t)b * nlog_p + (int64_t)(a.on0 + k) * ldk + (int64_t)st.action[bl] * nb, nb, lane,
                                          vmin, eta, v, e, &s, &w);

@@ -371,7 +371,8 @@ __global__ __launch_bounds__(256) void td_kernel(const HeadLossArgs args) {
     const int* __restrict__ action = args.action;
     const uint8_t* __restrict__ terminal = args.terminal;
     const float *__restrict__ reward = args.reward, *__restrict__ loss_weights = args.loss_weights;
-    const float gamma_n = args.gamma_n, huber_delta = args.huber_delta;
+    const float* __restrict__ discount = args.discount;
+    const float huber_delta = args.huber_delta;
     float *__restrict__ dout = args.dout, *__restrict__ q_values = args.q_values, *__restrict__ targets = args.targets;
     float *__restrict__ loss_part = args.loss_part, *__restrict__ dbh_part = args.dbh_part;
     double* __restrict__ priorities = args.priorities;
@@ -389,11 +390,16 @@ __global__ __launch_bounds__(256) void td_kernel(const HeadLossArgs args) {
     }
     int a = 0;
     float r = 0.f, nt = 0.f, w = 1.f;  // w: importance-sampling weight of the transition (isdqn_batch.loss_weights; none: 1)
+    float gamma_n = args.gamma_n;      // the transition's discount (isdqn_batch_discount::discount; none: cfg->gamma_n)
     if (on) {
         a = action[b];
         r = reward[b];
         nt = 1.f - (float)terminal[b];
         if (loss_weights != nullptr) w = loss_weights[b];
+        if (discount != nullptr) {
+            ISDQN_BOUNDS_CHECK(discount + b, 4, 50);
+            gamma_n = discount[b];
+        }
     }
     if (wave == 0) s_action[lane] = on ? a : -1;
     for (int k = wave; k < K; k += 4) {
@@ -482,6 +488,7 @@ struct HeadChainParams {
     const float* reward;
     const uint8_t* terminal;
     const float* loss_weights;  // [B] importance-sampling weights, or null (weight 1)
+    const float* discount;      // [B] per-transition discounts in gamma_n's place, or null (isdqn_batch_discount::discount)
     float gamma_n, huber_delta;
     int double_q;       // isdqn_net_config::double_q: head oh + k of the next-state row selects, head k values
     Munchausen mu;      // isdqn_net_config::munchausen_*: head k of the state row gives the bonus, of the next-state row the soft value
@@ -565,7 +572,7 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
         ISDQN_BOUNDS_CHECK((s < S && b0 + s < p.B) ? (const void*)(p.action + b0 + s) : zero_chunk(), 4, 20);
         act[s] = *(const ISDQN_GLOBAL int*)((s < S && b0 + s < p.B) ? (const void*)(p.action + b0 + s) : zero_chunk());
     }
-    float td_r, td_w;    // reward, importance-sampling weight, terminal flag of this thread's (transition, head) pair
+    float td_r, td_w, td_g;  // reward, importance-sampling weight, discount, terminal flag of this thread's (transition, head) pair
     uint8_t td_term;
     {
         const int s = tid / K;
@@ -573,6 +580,9 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
         const bool okw = ok && p.loss_weights != nullptr;
         ISDQN_BOUNDS_CHECK(okw ? (const void*)(p.loss_weights + b0 + s) : zero_chunk(), 4, 29);
         td_w = *(const ISDQN_GLOBAL float*)(okw ? (const void*)(p.loss_weights + b0 + s) : zero_chunk());
+        const bool okg = ok && p.discount != nullptr;
+        ISDQN_BOUNDS_CHECK(okg ? (const void*)(p.discount + b0 + s) : zero_chunk(), 4, 50);
+        td_g = *(const ISDQN_GLOBAL float*)(okg ? (const void*)(p.discount + b0 + s) : zero_chunk());
         ISDQN_BOUNDS_CHECK(ok ? (const void*)(p.reward + b0 + s) : zero_chunk(), 4, 21);
         ISDQN_BOUNDS_CHECK(ok ? (const void*)(p.terminal + b0 + s) : zero_chunk(), 1, 22);
         td_r = *(const ISDQN_GLOBAL float*)(ok ? (const void*)(p.reward + b0 + s) : zero_chunk());
@@ -811,10 +821,11 @@ __global__ __launch_bounds__(HC_THREADS) void head_chain_kernel(const HeadChainP
             } else {
                 for (int j = 1; j < A; ++j) mx = fmaxf(mx, nq[j]);
             }
-            float tg = td_r + (1.f - (float)td_term) * p.gamma_n * mx;
+            const float gamma_n = p.discount != nullptr ? td_g : p.gamma_n;
+            float tg = td_r + (1.f - (float)td_term) * gamma_n * mx;
             if (p.mu.tau > 0.f) {  // the value head's own row of the state: head k, not oh + k
                 const float* sv = s_q + s * Op + k * A;
-                tg = munchausen_target(td_r, 1.f - (float)td_term, p.gamma_n, sv[a], soft_value(sv, A, p.mu.tau), soft_value(nq, A, p.mu.tau), p.mu);
+                tg = munchausen_target(td_r, 1.f - (float)td_term, gamma_n, sv[a], soft_value(sv, A, p.mu.tau), soft_value(nq, A, p.mu.tau), p.mu);
             }
             d = qv - tg;
             td = td_loss(d, p.huber_delta);
@@ -1816,6 +1827,11 @@ static int loss_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, 
 // `double_q`: selector head on0 + k of rows [B, 2B) of the forward -- the online parameters on the next states -- picks the action;
 // Munchausen targets (cfg->munchausen_tau > 0): `state_val_rows`, head-output rows [B][nlog_p] of the states from the network that
 // supplies the value (null: rows [0, B) of the forward)
+// The per-transition discounts behind a batch that says it has them (include/isdqn_hip.h, isdqn_batch_discount), else null.
+static inline const float* batch_discount(const isdqn_batch* batch) {
+    return (batch->flags & ISDQN_BATCH_DISCOUNT) ? reinterpret_cast<const isdqn_batch_discount*>(batch)->discount : nullptr;
+}
+
 static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, const isdqn_batch* batch, int K, int on0, int tg0, bool learn,
                              int32_t* adam_count, float* qv, float* tg, double* priorities, float* losses, float* loss_accum, hipStream_t st,
                              bool double_q = false, const float* val_rows = nullptr, const float* state_val_rows = nullptr) {
@@ -1839,7 +1855,7 @@ static int loss_and_finalize(const Plan& P, const isdqn_net_config* cfg, float* 
     a.vmin = P.hl_min; a.eta = P.head_nb > 0 ? (P.hl_max - P.hl_min) / (float)P.head_nb : 0.f; a.sigma = P.hl_sigma;
     a.huber_delta = cfg->huber_delta;
     a.action = batch->action; a.reward = batch->reward; a.terminal = batch->terminal; a.loss_weights = batch->loss_weights;
-    a.gamma_n = cfg->gamma_n;
+    a.discount = batch_discount(batch); a.gamma_n = cfg->gamma_n;
     a.dout = learn ? ws + P.dout_off : nullptr;
     a.q_values = qv; a.targets = tg; a.priorities = priorities;
     a.loss_part = loss_part; a.dbh_part = loss_part + (int64_t)n_blk * K;
@@ -2216,7 +2232,7 @@ static int launch_head_chain(const LearnCtx& c) {
     hp.B = c.B; hp.S = c.hc_S; hp.F = hid.out_f; hp.Fp = hid.out_p; hp.O = P.nha; hp.Op = P.nha_p; hp.K = c.K; hp.oh = P.oh;
     hp.A = P.n_actions;
     hp.action = c.batch->action; hp.reward = c.batch->reward; hp.terminal = c.batch->terminal;
-    hp.loss_weights = c.batch->loss_weights;
+    hp.loss_weights = c.batch->loss_weights; hp.discount = batch_discount(c.batch);
     hp.gamma_n = c.cfg->gamma_n; hp.huber_delta = c.cfg->huber_delta;
     hp.double_q = c.double_q ? 1 : 0;
     hp.mu = Munchausen{c.cfg->munchausen_tau, c.cfg->munchausen_alpha, c.cfg->munchausen_clip};
@@ -3188,9 +3204,9 @@ extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu
     if (rc) return rc;
     // the full two-stream gradient pass on eff: its optimizer launches write the reduced gradient (masked under dueling) and update
     // nothing; loss_finalize_kernel advances adam_count and leaves the bias corrections in the workspace, as in a plain learn step
-    isdqn_batch b = *batch;
-    b.flags |= ISDQN_BATCH_MIRROR_CURRENT;  // (compose wrote the mirror of eff; the *_target form rebuilds both mirrors itself)
-    rc = learn_or_loss(cfg, eff, nullptr, nullptr, adam_count, &b, losses, losses_accum, q_values, targets, priorities, workspace, stream, true, grad,
+    isdqn_batch_discount b{*batch, batch_discount(batch)};  // (the copy keeps the discounts that may follow the caller's batch)
+    b.batch.flags |= ISDQN_BATCH_MIRROR_CURRENT;  // (compose wrote the mirror of eff; the *_target form rebuilds both mirrors itself)
+    rc = learn_or_loss(cfg, eff, nullptr, nullptr, adam_count, &b.batch, losses, losses_accum, q_values, targets, priorities, workspace, stream, true, grad,
                        eff_target, nullptr, false);
     if (rc) return rc;
     const int64_t quads = P.n_params / 4;

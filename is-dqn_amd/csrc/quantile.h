@@ -151,7 +151,7 @@ __global__ __launch_bounds__(QR_THREADS) void qr_loss_kernel(const HeadLossArgs 
             }
         }
         if (slogits != nullptr) mx = qr_mean(nrow + (int64_t)best * N, N, lane, tv);
-        const float disc = st.nt[bl] * a.gamma_n;
+        const float disc = st.nt[bl] * st.g[bl];
         const float tg = st.r[bl] + disc * mx;
 #pragma unroll
         for (int t = 0; t < PER_LANE; ++t) tv[t] = st.r[bl] + disc * tv[t];  // the target atoms t_j, j = lane + 64 t

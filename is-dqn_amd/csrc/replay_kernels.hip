@@ -234,3 +234,121 @@ extern "C" int isdqn_replay_augment_shift(const uint8_t* frames, int64_t frame_s
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }
+
+// Horizon windows (include/isdqn_hip.h, isdqn_replay_gather_horizon holds THE definition): an element row keeps the frame ids of its
+// whole window [stack + n_max], its n_max per-step rewards and how many of them lie inside the trajectory; the gather cuts the window
+// at a horizon m and sums the return at a discount that it reads from device memory, so a captured step changes both between replays.
+// Behind every kernel this code object had, as the augmentation: they keep their places in it.  Bounds sites 48 (gather), 49 (scatter).
+namespace isdqn {
+
+constexpr int HORIZON_MAX = 128;
+
+// Lanes over the 2 * stack output ids of the B rows, as gather_rows_kernel; the lane of a row's first id also sums the row's return,
+// sequentially and in float64 (one rounding per operation: -ffp-contract=off), and writes the row's scalars.
+__global__ __launch_bounds__(256) void gather_horizon_kernel(const int* __restrict__ elem_window, const float* __restrict__ elem_steps,
+                                                             const int* __restrict__ elem_len, const int* __restrict__ elem_action,
+                                                             const uint8_t* __restrict__ elem_terminal, int stack, int n_max,
+                                                             const int* __restrict__ index_to_slot, const int* __restrict__ slots, int B,
+                                                             const int* __restrict__ horizon, const float* __restrict__ gamma,
+                                                             int* __restrict__ out_ids, int* __restrict__ out_action,
+                                                             float* __restrict__ out_reward, uint8_t* __restrict__ out_terminal,
+                                                             float* __restrict__ out_discount) {
+    const int stack2 = 2 * stack;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * stack2) return;
+    const int b = i / stack2, c = i - b * stack2;
+    ISDQN_BOUNDS_CHECK(slots + b, 4, 48);
+    int slot = slots[b];
+    if (index_to_slot != nullptr) {
+        ISDQN_BOUNDS_CHECK(index_to_slot + slot, 4, 48);
+        slot = index_to_slot[slot];
+    }
+    ISDQN_BOUNDS_CHECK(horizon, 4, 48);
+    const int m = min(max(*horizon, 1), n_max);
+    const int* __restrict__ win = elem_window + (int64_t)slot * (stack + n_max);
+    const int col = c < stack ? c : m + (c - stack);  // state: window[0, stack); next state: window[m, m + stack)
+    ISDQN_BOUNDS_CHECK(win + col, 4, 48);
+    out_ids[i] = win[col];
+    if (c != 0) return;
+    ISDQN_BOUNDS_CHECK(elem_len + slot, 4, 48);
+    ISDQN_BOUNDS_CHECK(gamma, 4, 48);
+    const int len = elem_len[slot];
+    const int me = min(m, len);
+    const double G = (double)*gamma;
+    const float* __restrict__ steps = elem_steps + (int64_t)slot * n_max;
+    double g = 1.0, acc = 0.0;
+    for (int t = 0; t < m; ++t) {
+        if (t < me) {
+            ISDQN_BOUNDS_CHECK(steps + t, 4, 48);
+            acc = acc + (double)steps[t] * g;
+        }
+        g = g * G;
+    }
+    ISDQN_BOUNDS_CHECK(elem_action + slot, 4, 48);
+    ISDQN_BOUNDS_CHECK(elem_terminal + slot, 1, 48);
+    out_action[b] = elem_action[slot];
+    out_reward[b] = (float)acc;
+    out_discount[b] = (float)g;
+    out_terminal[b] = (elem_terminal[slot] != 0 && m >= len) ? (uint8_t)1 : (uint8_t)0;
+}
+
+// The horizon tables' part of a flush: lanes over the stack + n_max window ids of the n_rows staged rows; a row's lanes below n_max
+// also copy its step rewards, its first lane the length.
+__global__ __launch_bounds__(256) void apply_staged_horizon_kernel(const uint8_t* __restrict__ st, int n_rows, int64_t off_rows,
+                                                                   int64_t off_window, int64_t off_steps, int64_t off_len, int stack,
+                                                                   int n_max, int* __restrict__ elem_window,
+                                                                   float* __restrict__ elem_steps, int* __restrict__ elem_len) {
+    const int wn = stack + n_max;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_rows * wn) return;
+    const int r = (int)(i / wn), c = (int)(i - (int64_t)r * wn);
+    ISDQN_BOUNDS_CHECK(reinterpret_cast<const int*>(st + off_rows) + r, 4, 49);
+    ISDQN_BOUNDS_CHECK(reinterpret_cast<const int*>(st + off_window) + i, 4, 49);
+    const int row = reinterpret_cast<const int*>(st + off_rows)[r];
+    elem_window[(int64_t)row * wn + c] = reinterpret_cast<const int*>(st + off_window)[i];
+    if (c < n_max) {
+        ISDQN_BOUNDS_CHECK(reinterpret_cast<const float*>(st + off_steps) + (int64_t)r * n_max + c, 4, 49);
+        elem_steps[(int64_t)row * n_max + c] = reinterpret_cast<const float*>(st + off_steps)[(int64_t)r * n_max + c];
+    }
+    if (c == 0) {
+        ISDQN_BOUNDS_CHECK(reinterpret_cast<const int*>(st + off_len) + r, 4, 49);
+        elem_len[row] = reinterpret_cast<const int*>(st + off_len)[r];
+    }
+}
+
+}  // namespace isdqn
+
+extern "C" int isdqn_replay_apply_staged_horizon(const uint8_t* staged, int32_t n_rows, int64_t off_rows, int64_t off_window,
+                                                 int64_t off_steps, int64_t off_len, int32_t stack, int32_t n_max, int32_t* elem_window,
+                                                 float* elem_steps, int32_t* elem_len, void* stream) {
+    ISDQN_REQUIRE(staged && elem_window && elem_steps && elem_len, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(n_rows >= 0 && stack >= 1 && n_max >= 1 && n_max <= HORIZON_MAX, ISDQN_ERR_ARG, "n_rows < 0, stack < 1 or n_max outside [1, 128]");
+    ISDQN_REQUIRE(off_rows >= 0 && off_window >= 0 && off_steps >= 0 && off_len >= 0, ISDQN_ERR_ARG, "negative section offset");
+    ISDQN_REQUIRE((reinterpret_cast<uintptr_t>(staged) & 3) == 0 && ((off_rows | off_window | off_steps | off_len) & 3) == 0, ISDQN_ERR_ARG,
+                  "staged int32/float sections must be 4-byte aligned");
+    if (n_rows == 0) return ISDQN_OK;
+    const int64_t total = (int64_t)n_rows * (stack + n_max);
+    ISDQN_REQUIRE((total + 255) / 256 <= INT32_MAX, ISDQN_ERR_ARG, "too many rows");
+    hipLaunchKernelGGL(apply_staged_horizon_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, staged, n_rows,
+                       off_rows, off_window, off_steps, off_len, stack, n_max, elem_window, elem_steps, elem_len);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_replay_gather_horizon(const int32_t* elem_window, const float* elem_steps, const int32_t* elem_len,
+                                           const int32_t* elem_action, const uint8_t* elem_terminal, int32_t stack, int32_t n_max,
+                                           const int32_t* index_to_slot, const int32_t* slots, int32_t B, const int32_t* horizon,
+                                           const float* gamma, int32_t* out_frame_ids, int32_t* out_action, float* out_reward,
+                                           uint8_t* out_terminal, float* out_discount, void* stream) {
+    ISDQN_REQUIRE(elem_window && elem_steps && elem_len && elem_action && elem_terminal && slots && horizon && gamma, ISDQN_ERR_ARG,
+                  "null pointer");
+    ISDQN_REQUIRE(out_frame_ids && out_action && out_reward && out_terminal && out_discount, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(B >= 1 && stack >= 1 && n_max >= 1 && n_max <= HORIZON_MAX, ISDQN_ERR_ARG, "B < 1, stack < 1 or n_max outside [1, 128]");
+    const int64_t total = (int64_t)B * 2 * stack;
+    ISDQN_REQUIRE(total <= INT32_MAX, ISDQN_ERR_ARG, "more than 2^31 - 1 output ids");
+    hipLaunchKernelGGL(gather_horizon_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, elem_window, elem_steps,
+                       elem_len, elem_action, elem_terminal, stack, n_max, index_to_slot, slots, B, horizon, gamma, out_frame_ids, out_action,
+                       out_reward, out_terminal, out_discount);
+    ISDQN_HIP_CHECK(hipGetLastError());
+    return ISDQN_OK;
+}

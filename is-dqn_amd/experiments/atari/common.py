@@ -3,6 +3,7 @@ build the same AtariEnv + ReplayBuffer + UniformSamplingDistribution triple).  E
 environment (no ROMs in the image), n lockstep environments on host worker processes, the prioritized sampler."""
 import numpy as np
 
+from experiments.base.parser_argument import replay_horizon_kwargs
 from slimdqn.sample_collection.replay_buffer import ReplayBuffer
 from slimdqn.sample_collection.samplers import PrioritizedSamplingDistribution, UniformSamplingDistribution
 
@@ -38,7 +39,7 @@ def make_replay(p: dict, prioritized: bool = False) -> ReplayBuffer:
         sampling_distribution=sampler,
         max_capacity=p["replay_buffer_capacity"],
         batch_size=p["batch_size"],
-        update_horizon=p["update_horizon"],
+        **replay_horizon_kwargs(p),
         gamma=p["gamma"],
         clipping=lambda x: np.clip(x, -1, 1),
         stack_size=4,

@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 from experiments.base import dist as replicas
-from experiments.base.parser_argument import reset_kwargs
+from experiments.base.parser_argument import anneal_schedule, reset_kwargs
 from experiments.base.utils import save_data
 from slimdqn.sample_collection.utils import collect_single_sample, collect_vector_samples, linear_schedule
 
@@ -36,6 +36,10 @@ def train(key, p: dict, agent, env, rb):
     # keeps the default (slimdqn/_engine.py: trust_mirror).
     if hasattr(agent, "trust_mirror"):
         agent.trust_mirror = True
+    # Annealed update horizon and discount (-anneal, not in the reference): the agent cuts every batch at its step's horizon and
+    # discount on the device, counted from here and again from every reset
+    if p.get("anneal_period"):
+        agent.set_horizon_schedule(*anneal_schedule(p), replay_buffer=rb)
     epsilon_schedule = linear_schedule(1.0, p["epsilon_end"], p["epsilon_duration"])
     n_training_steps = 0
     env.reset()

@@ -70,6 +70,9 @@ _ENGINE = [
     ("-resets", "--reset_shrink", dict(type=float, default=0.5, help="Shrink factor in [0, 1] of the layers below the reset ones: p <- s * p + (1 - s) * fresh (BBF: 0.5; 1 keeps them). Means nothing without -reset.")),
     ("-resetl", "--reset_top_layers", dict(type=int, default=0, help="Number of top layers that are re-initialised fully; 0 = every Dense layer (BBF, SR-SPR). Means nothing without -reset.")),
     ("-ema", "--ema_tau", dict(type=float, default=0.0, help="EMA (Polyak) target network: target <- (1 - tau) * target + tau * online after every gradient step, on the device, instead of a copy every -tuf steps (BBF, SR-SPR: 0.005); 0 = off, in [0, 1]. DQN only: iS-DQN's target is a head of the online network, the target-free agents have none.")),
+    ("-anneal", "--anneal_period", dict(type=int, default=0, help="Anneal the update horizon and the discount (SR-SPR, BBF: -anneal 10000 -n 10 -nend 3 -gamma 0.97 -gammaend 0.997): over this many gradient steps, counted again from every -reset, n goes exponentially from -n to -nend and 1 - gamma from 1 - (-gamma) to 1 - (-gammaend); the replay keeps whole windows of max(-n, -nend) steps and every batch is cut at the step's horizon on the device. 0 = off. With every agent, torso, loss and target flag.")),
+    ("-nend", "--update_horizon_end", dict(type=int, default=None, help="Final update horizon of -anneal (default: -n). Refused without -anneal.")),
+    ("-gammaend", "--gamma_end", dict(type=float, default=None, help="Final discount of -anneal, in [0, 1) (default: -gamma). Refused without -anneal.")),
     ("-nenvs", "--n_envs", dict(type=int, default=1, help="Host environments stepped in lockstep with one batched best_actions forward (1 = the reference's loop).")),
     ("-nworkers", "--n_env_workers", dict(type=int, default=0, help="Host worker processes stepping the -nenvs environments in parallel (0 = in this process).")),
     ("-env", "--env_backend", dict(type=str, default="ale", choices=["ale", "synthetic"], help="'synthetic' replaces ALE by random frames (no ROMs needed).")),
@@ -290,6 +293,45 @@ def check_ema(p: dict, algo_name: str) -> None:
 def ema_kwargs(p) -> dict:
     """The agents' EMA keyword from parsed parameters; without -ema the keywords are the ones they were before the flag existed."""
     return dict(ema_tau=float(p["ema_tau"])) if p.get("ema_tau") else {}
+
+
+# (-anneal, -nend and -gammaend stay out of parameters.json like -reset)
+ANNEAL_END_REFUSED = "-nend / --update_horizon_end and -gammaend / --gamma_end are the end points of -anneal / --anneal_period: they need it"
+ANNEAL_MAX_HORIZON = 128  # slimdqn.sample_collection.replay_buffer.HORIZON_MAX
+
+
+def check_anneal(p: dict) -> None:
+    """-nend or -gammaend without -anneal, a negative period, a horizon outside 1..128 or a discount outside [0, 1) fails before
+    anything is written."""
+    period = p.get("anneal_period", 0)
+    if period == 0:
+        if p.get("update_horizon_end") is not None or p.get("gamma_end") is not None:
+            raise ValueError(ANNEAL_END_REFUSED)
+        return
+    if period < 0:
+        raise ValueError("-anneal / --anneal_period must be >= 0 (0 = off)")
+    n0, n1, g0, g1 = anneal_schedule(p)[:4]
+    if not (1 <= n0 <= ANNEAL_MAX_HORIZON and 1 <= n1 <= ANNEAL_MAX_HORIZON):
+        raise ValueError(f"-anneal: -n and -nend must be in 1..{ANNEAL_MAX_HORIZON}")
+    if not (0.0 <= g0 < 1.0 and 0.0 <= g1 < 1.0):  # (NaN fails both comparisons)
+        raise ValueError("-anneal: -gamma and -gammaend must be in [0, 1)")
+
+
+def anneal_schedule(p) -> tuple:
+    """The arguments of ``agent.set_horizon_schedule`` from parsed parameters: (-n, -nend, -gamma, -gammaend, -anneal), an end point
+    that is not given being its start."""
+    n_end = p["update_horizon"] if p.get("update_horizon_end") is None else p["update_horizon_end"]
+    gamma_end = p["gamma"] if p.get("gamma_end") is None else p["gamma_end"]
+    return int(p["update_horizon"]), int(n_end), float(p["gamma"]), float(gamma_end), int(p["anneal_period"])
+
+
+def replay_horizon_kwargs(p) -> dict:
+    """The replay's horizon keywords from parsed parameters: under -anneal it keeps whole windows of the larger of -n and -nend; without
+    it the keywords are the ones they were before the flag existed."""
+    if not p.get("anneal_period"):
+        return dict(update_horizon=p["update_horizon"])
+    n0, n1 = anneal_schedule(p)[:2]
+    return dict(update_horizon=max(n0, n1), horizon_window=True)
 
 
 def check_engine_arguments(p: dict) -> None:

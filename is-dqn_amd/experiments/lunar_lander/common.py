@@ -1,4 +1,5 @@
 """Environment and replay wiring shared by the LunarLander entry points (experiments/lunar_lander/{isdqn,dqn,tfdqn}.py)."""
+from experiments.base.parser_argument import replay_horizon_kwargs
 from experiments.atari.common import seeds  # noqa: F401  (re-exported: the (network, training) seed pair of an entry point)
 from slimdqn.sample_collection.replay_buffer import ReplayBuffer
 from slimdqn.sample_collection.samplers import UniformSamplingDistribution
@@ -22,7 +23,7 @@ def make_replay(p):
         sampling_distribution=UniformSamplingDistribution(p["seed"]),
         max_capacity=p["replay_buffer_capacity"],
         batch_size=p["batch_size"],
-        update_horizon=p["update_horizon"],
+        **replay_horizon_kwargs(p),
         gamma=p["gamma"],
         clipping=None,
         stack_size=1,

@@ -622,16 +622,20 @@ class QNetEngine:
 
     # ------------------------------------------------------------------ C-ABI calls
     def make_batch(self, *, frames=None, frame_stride=0, frame_ids=None, state=None, next_state=None, action=None, reward=None, terminal=None,
-                   mirror_current: bool = False, priorities_ready: torch.cuda.Event | None = None, loss_weights=None) -> _hip.Batch:
+                   mirror_current: bool = False, priorities_ready: torch.cuda.Event | None = None, loss_weights=None, discount=None) -> _hip.Batch:
         """``mirror_current``: promise that the previous call on this engine was learn_on_batch and nothing wrote the
         parameters since (include/isdqn_hip.h, ISDQN_BATCH_MIRROR_CURRENT) -- only the captured multi-step graphs do.
         ``priorities_ready``: an event (already recorded once, so that its handle exists) the learn call records on the
         caller's stream as soon as q_values / targets / priorities are final.
-        ``loss_weights``: float32 [B] device tensor of importance-sampling weights (prioritized replay), None = weight 1."""
+        ``loss_weights``: float32 [B] device tensor of importance-sampling weights (prioritized replay), None = weight 1.
+        ``discount``: float32 [B] device tensor of per-transition discounts that stand in ``gamma_n``'s place (a horizon-window replay's
+        ``DeviceBatch.discount``), None = ``gamma_n`` everywhere."""
         if loss_weights is not None:
             assert loss_weights.dtype == torch.float32 and loss_weights.numel() == self.batch_size and loss_weights.is_contiguous()
-        b = _hip.Batch()
-        b.flags = _hip.BATCH_MIRROR_CURRENT if mirror_current else 0
+        if discount is not None:
+            assert discount.dtype == torch.float32 and discount.numel() == self.batch_size and discount.is_contiguous()
+        b = _hip.Batch() if discount is None else _hip.BatchDiscount()  # (isdqn_batch_discount: the flag announces the pointer behind)
+        b.flags = (_hip.BATCH_MIRROR_CURRENT if mirror_current else 0) | (0 if discount is None else _hip.BATCH_DISCOUNT)
         b.priorities_ready = None if priorities_ready is None else int(priorities_ready.cuda_event)
         b.B = self.batch_size
         b.frames = _hip.ptr(frames)
@@ -643,8 +647,10 @@ class QNetEngine:
         b.reward = _hip.ptr(reward)
         b.terminal = _hip.ptr(terminal)
         b.loss_weights = _hip.ptr(loss_weights)
+        if discount is not None:
+            b.discount = _hip.ptr(discount)
         # keep the tensors alive for the duration of the asynchronous call
-        b._keep = (frames, frame_ids, state, next_state, action, reward, terminal, priorities_ready, loss_weights)
+        b._keep = (frames, frame_ids, state, next_state, action, reward, terminal, priorities_ready, loss_weights, discount)
         return b
 
     def forward(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, n_rows: int, params=None) -> torch.Tensor:

@@ -6,7 +6,8 @@ steps (index rows -> [sum-tree query] -> row gather -> learn_on_batch -> [priori
 static buffers, and replays them: one graph launch per S steps.
 
 The draws stay on the host (numpy PCG64, the reference's stream): before a replay the next S rows of
-pre-drawn dense indices (uniform) or unit draws (prioritized) are copied into the static input block.
+pre-drawn dense indices (uniform) or unit draws (prioritized) are copied into the static input block; so are the betas of a weighted
+update and the (horizon, discount) pairs of one under a horizon schedule, which the kernels read from device memory.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from slimdqn import _hip
 
 class GraphedUpdate:
     def __init__(self, rb, eng, prioritized: bool, steps_per_graph: int = 8, writeback: bool | None = None, learn=None,
-                 weighted: bool = False, augment=None, state=()):
+                 weighted: bool = False, augment=None, state=(), horizon: bool = False):
         """``prioritized``: the sampler is a sum tree (the query is part of the graph); ``writeback``: sqrt(mean_k td) of
         every step goes back into the tree (default: whenever prioritized); ``learn``: the learn call of one step on a C batch
         (default ``eng.learn_on_batch``; DQN passes its target-parameter form, dqn.py:59-72); ``weighted``: the query also writes
@@ -28,7 +29,13 @@ class GraphedUpdate:
         (include/isdqn_hip.h, isdqn_replay_augment_shift) or None -- the gathered rows' frames are shifted into a scratch pool inside the
         graph and every step's batch reads the pool; the counter lives on the device, so every replay draws anew and lands on the
         draws the eager steps would have taken.  ``state``: device tensors besides the engine's own that ``learn`` writes (DQN with
-        ``ema_tau``: the target buffers) -- the warm-up steps of a capture must not count on them either."""
+        ``ema_tau``: the target buffers) -- the warm-up steps of a capture must not count on them either.  ``horizon``: the replay keeps
+        horizon windows and every step's rows are cut at a horizon and discount of its own (include/isdqn_hip.h,
+        isdqn_replay_gather_horizon); the S pairs are INPUT of a replay, like the betas -- ``run(betas, horizons, gammas)`` stages them,
+        the gather of step s reads its pair from device memory, and the step's batch carries the gathered discounts."""
+        self.horizon = bool(horizon)
+        if self.horizon and not getattr(rb, "_horizon_window", False):
+            raise ValueError("a captured update at a horizon needs a replay built with horizon_window=True")
         self.augment = augment
         self._learn_state = list(state)
         self.augment_pad = int(augment[0]) if augment else 0
@@ -63,6 +70,11 @@ class GraphedUpdate:
         self.action = torch.zeros(n_b, B, dtype=torch.int32, device=dev)
         self.reward = torch.zeros(n_b, B, dtype=torch.float32, device=dev)
         self.terminal = torch.zeros(n_b, B, dtype=torch.uint8, device=dev)
+        # the pairs of the S steps (horizon 1, discount 0 until run() stages them: the warm-up of a capture reads them) and the
+        # gathered discounts of every batch slot
+        self.horizons = torch.ones(self.S, dtype=torch.int32, device=dev) if self.horizon else None
+        self.gammas = torch.zeros(self.S, dtype=torch.float32, device=dev) if self.horizon else None
+        self.discount = torch.zeros(n_b, B, dtype=torch.float32, device=dev) if self.horizon else None
         # vector observations (the fc torso, LunarLander): the replay stores the bytes of every float32 observation as one 1 x 4d "frame";
         # the captured step materialises the B state / next-state rows of a batch into static buffers the engine reads as (B, d) float32
         self.fc = eng.architecture_type == "fc"
@@ -105,12 +117,13 @@ class GraphedUpdate:
         # run()'s check
         ev = lambda i: self._prio_ready[i] if self.prioritized else None
         wt = lambda i: self.weights[i] if self.weighted else None
+        dc = lambda i: self.discount[i] if self.horizon else None
         if self.fc:
             B = self.B
             rows = lambda half, i: self.obs[half, i * B:(i + 1) * B].view(torch.float32)
             self.chained = [
                 eng.make_batch(state=rows(0, i), next_state=rows(1, i), action=self.action[i], reward=self.reward[i], terminal=self.terminal[i],
-                               mirror_current=True, priorities_ready=ev(i), loss_weights=wt(i))
+                               mirror_current=True, priorities_ready=ev(i), loss_weights=wt(i), discount=dc(i))
                 for i in range(self.frame_ids.shape[0])
             ]
             return
@@ -125,12 +138,18 @@ class GraphedUpdate:
         self.chained = [
             eng.make_batch(frames=frames(i), frame_stride=rb._hw, frame_ids=ids(i), action=self.action[i],
                            reward=self.reward[i], terminal=self.terminal[i], mirror_current=True, priorities_ready=ev(i),
-                           loss_weights=wt(i))
+                           loss_weights=wt(i), discount=dc(i))
             for i in range(self.frame_ids.shape[0])
         ]
 
-    def _gather(self, idx, n_rows: int, slot: int) -> None:
+    def _gather(self, idx, n_rows: int, slot: int, s: int = 0) -> None:
+        """Rows of ``idx`` into the batch buffers from slot ``slot`` on; with horizon windows, the B rows of step ``s`` at its pair."""
         rb = self.rb
+        if self.horizon:
+            assert n_rows == self.B
+            rb.gather_horizon_into(idx, self.horizons[s:s + 1], self.gammas[s:s + 1], self.frame_ids[slot], self.action[slot],
+                                   self.reward[slot], self.terminal[slot], self.discount[slot])
+            return
         _hip.check(
             rb._lib.isdqn_replay_gather_rows(
                 _hip.ptr(rb._d_elem_frames), _hip.ptr(rb._d_elem_action), _hip.ptr(rb._d_elem_reward),
@@ -191,11 +210,15 @@ class GraphedUpdate:
                         rb._sampling_distribution.update_device(self.indices[slot], eng.priorities)
                     if s + 1 < self.S:
                         self._query(tree, s + 1, 1 - slot)
-                        self._gather(self.indices[1 - slot], self.B, 1 - slot)
+                        self._gather(self.indices[1 - slot], self.B, 1 - slot, s + 1)
                         self._augment(1 - slot, self.B)
                 main.wait_stream(sampling)
         else:
-            self._gather(self.block, self.S * self.B, 0)  # rows of all S steps: the [S][B] buffers are contiguous
+            if self.horizon:  # (every step has a horizon of its own: S gathers of B rows in place of the one over S*B)
+                for s in range(self.S):
+                    self._gather(self.block[s], self.B, s, s)
+            else:
+                self._gather(self.block, self.S * self.B, 0)  # rows of all S steps: the [S][B] buffers are contiguous
             self._augment(0, self.S * self.B)  # (and so are the pool and its table: step s takes the draws of count + s)
             if self.fc:
                 self._materialize(0, self.S * self.B)
@@ -240,12 +263,14 @@ class GraphedUpdate:
         self.eng.invalidate_mirror()
         self.graph = g
 
-    def run(self, betas=None) -> None:
+    def run(self, betas=None, horizons=None, gammas=None) -> None:
         """S steps: draw S index rows on the host stream of the sampler, stage them (weighted: and the S float32 ``betas`` of these
-        steps), replay the graph."""
+        steps; at a horizon: and their S int32 ``horizons`` and float32 ``gammas``), replay the graph."""
         rb = self.rb
         if self.weighted != (betas is not None):
             raise ValueError("a weighted captured update takes the betas of its S steps, an unweighted one none")
+        if self.horizon != (horizons is not None) or self.horizon != (gammas is not None):
+            raise ValueError("a captured update at a horizon takes the horizons and the gammas of its S steps, another one neither")
         rb._flush()
         if rb._frames.data_ptr() != self._frames_ptr:  # the frame store was re-allocated: pointers in the graph are stale
             self._frames_ptr = rb._frames.data_ptr()
@@ -259,6 +284,12 @@ class GraphedUpdate:
             betas = np.ascontiguousarray(betas, dtype=np.float32)
             assert betas.shape == (self.S,)
             self.betas.copy_(sampler._to_device(betas, torch.float32), non_blocking=True)
+        if self.horizon:
+            horizons = np.ascontiguousarray(horizons, dtype=np.int32)
+            gammas = np.ascontiguousarray(gammas, dtype=np.float32)
+            assert horizons.shape == (self.S,) and gammas.shape == (self.S,)
+            self.horizons.copy_(sampler._to_device(horizons, torch.int32), non_blocking=True)
+            self.gammas.copy_(sampler._to_device(gammas, torch.float32), non_blocking=True)
         if self.eng.trust_mirror:
             self.eng.refresh_mirror()  # (trusted engines only: one eager launch when the bookkeeping says the mirror is stale)
         self.graph.replay()

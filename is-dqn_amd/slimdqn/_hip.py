@@ -18,6 +18,7 @@ OK = 0
 ERR_CAPACITY, ERR_NEGATIVE, ERR_SHAPE, ERR_EMPTY, ERR_RANGE, ERR_UNSUPPORTED, ERR_HIP, ERR_ARG = range(-1, -9, -1)
 STATUS_NEGATIVE_VALUE, STATUS_TARGET_RANGE, STATUS_EMPTY_TREE = 1, 2, 4
 BATCH_MIRROR_CURRENT = 1  # include/isdqn_hip.h: ISDQN_BATCH_MIRROR_CURRENT
+BATCH_DISCOUNT = 2  # include/isdqn_hip.h: ISDQN_BATCH_DISCOUNT
 TREE_MAX_BATCH = 4096
 ARCH_CNN, ARCH_FC, ARCH_IMPALA = 0, 1, 2
 PRECISION_BF16X3, PRECISION_BF16 = 0, 1
@@ -98,6 +99,10 @@ class Batch(ctypes.Structure):
     ]
 
 
+class BatchDiscount(Batch):  # isdqn_batch_discount: the batch, then the discounts that flags & BATCH_DISCOUNT announces
+    _fields_ = [("discount", c_void_p)]  # float32 [B] per-transition discounts in cfg.gamma_n's place (include/isdqn_hip.h)
+
+
 _SIGNATURES = {
     "isdqn_version": (c_char_p, []),
     "isdqn_last_error": (c_char_p, []),
@@ -129,6 +134,16 @@ _SIGNATURES = {
     "isdqn_replay_augment_shift": (
         c_int32,
         [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    # horizon windows: the scatter of their staged rows, and the gather at a horizon / discount read from device memory
+    "isdqn_replay_apply_staged_horizon": (
+        c_int32,
+        [c_void_p, c_int32, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "isdqn_replay_gather_horizon": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "isdqn_net_param_layout": (
         c_int32,

@@ -70,6 +70,20 @@ def importance_beta(beta_start: float, beta_end, n_steps: int, step: int) -> np.
     return np.float32(b0 + (b1 - b0) * (np.float64(max(step, 0)) / np.float64(n_steps)))
 
 
+def horizon_schedule(n_start: int, n_end: int, gamma_start: float, gamma_end: float, period: int, t: int):
+    """(update horizon, float32 discount) of gradient step ``t`` (0-based) under the annealing of SR-SPR and BBF: with
+    p = min(t / period, 1), n is exponential from ``n_start`` to ``n_end`` and rounded to the nearest integer, and 1 - gamma is
+    exponential from 1 - ``gamma_start`` to 1 - ``gamma_end``.  Host float64 arithmetic; at p = 0 and p = 1 exactly the end values."""
+    if t <= 0:
+        return int(n_start), np.float32(gamma_start)
+    if t >= period:
+        return int(n_end), np.float32(gamma_end)
+    p = np.float64(t) / np.float64(period)
+    ln0, ln1 = np.log(np.float64(n_start)), np.log(np.float64(n_end))
+    lg0, lg1 = np.log(1.0 - np.float64(gamma_start)), np.log(1.0 - np.float64(gamma_end))
+    return int(np.rint(np.exp(ln0 + (ln1 - ln0) * p))), np.float32(1.0 - np.exp(lg0 + (lg1 - lg0) * p))
+
+
 def recycle_seed(seed: int, k: int) -> int:
     """Seed of the fresh parameters of the agent's k-th recycle (0-based): a child of the agent's seed in numpy's SeedSequence tree,
     never the seed itself (``init_params(seed)`` draws from SeedSequence(seed) with an empty spawn key)."""
@@ -135,10 +149,80 @@ class EngineAgent:
         return np.asarray([importance_beta(*self._is_schedule, t + i) for i in range(n)], dtype=np.float32)
 
     def _sample(self, replay_buffer):
-        """The training batch of one eager gradient step: with importance sampling on, drawn with this step's beta."""
+        """The training batch of one eager gradient step: with importance sampling on, drawn with this step's beta; with a horizon
+        schedule, cut at this step's horizon and discount."""
         betas = self._next_betas()
-        batch = replay_buffer.sample() if betas is None else replay_buffer.sample(beta=float(betas[0]))
-        return self._augment(replay_buffer, batch)
+        kw = {} if betas is None else dict(beta=float(betas[0]))
+        pairs = self._next_horizons(1, replay_buffer)
+        if pairs is not None:
+            kw.update(horizon=int(pairs[0][0]), gamma=float(pairs[1][0]))
+        return self._augment(replay_buffer, replay_buffer.sample(**kw))
+
+    def _sample_eval(self, replay_buffer):
+        """The second ("eval") batch of an analysis agent's update: as sampled, at the horizon and discount of the step's training batch."""
+        if self._hz_schedule is None:
+            return replay_buffer.sample()
+        n, g = self._hz_last
+        return replay_buffer.sample(horizon=int(n), gamma=float(g))
+
+    # ------------------------------------------------------------------ annealed update horizon and discount
+    _hz_schedule = None  # (n_start, n_end, gamma_start, gamma_end, period) once set_horizon_schedule was called; None: off
+    _hz_step = 0         # gradient steps since the call or since the last reset_parameters
+    _hz_last = None      # (horizon, float32 gamma) of the last gradient step taken under the schedule
+
+    def set_horizon_schedule(self, n_start: int, n_end: int, gamma_start: float, gamma_end: float, period: int, replay_buffer=None) -> None:
+        """Anneal the update horizon from ``n_start`` to ``n_end`` and the discount from ``gamma_start`` to ``gamma_end`` over ``period``
+        gradient steps (``horizon_schedule``; SR-SPR and BBF: 10 -> 3 and 0.97 -> 0.997), counted from this call and again from every
+        ``reset_parameters``.  Needs a replay built with ``horizon_window=True`` whose n_max covers both horizons (checked here when
+        ``replay_buffer`` is given, else at the first update): every batch is then cut at the step's horizon on the device and carries
+        its discount per row (include/isdqn_hip.h, isdqn_replay_gather_horizon and isdqn_batch_discount::discount); the engine's ``gamma_n`` is
+        not read.  Until this is called the learn calls get a NULL discount pointer."""
+        n_start, n_end, period = int(n_start), int(n_end), int(period)
+        if period < 1:
+            raise ValueError("set_horizon_schedule: period must be >= 1")
+        if n_start < 1 or n_end < 1:
+            raise ValueError("set_horizon_schedule: horizons must be >= 1")
+        for g in (gamma_start, gamma_end):
+            if not 0.0 <= float(g) < 1.0:
+                raise ValueError("set_horizon_schedule: discounts must be in [0, 1)")
+        self._hz_schedule = (n_start, n_end, float(gamma_start), float(gamma_end), period)
+        if replay_buffer is not None:
+            self._check_horizon_replay(replay_buffer)
+        self._hz_step = 0
+        self._hz_last = horizon_schedule(*self._hz_schedule, 0)
+        self._drop_graph()  # (the captured step has the gather at a horizon and the discount pointer, or not)
+
+    def _check_horizon_replay(self, replay_buffer) -> None:
+        n_need = max(self._hz_schedule[0], self._hz_schedule[1])
+        if not getattr(replay_buffer, "_horizon_window", False):
+            raise ValueError("a horizon schedule (set_horizon_schedule) needs a replay built with horizon_window=True")
+        if replay_buffer._update_horizon < n_need:
+            raise ValueError(f"a horizon schedule up to n = {n_need} needs a replay with n_max >= {n_need}, this one has "
+                             f"{replay_buffer._update_horizon}")
+
+    def _next_horizons(self, n: int = 1, replay_buffer=None):
+        """(int32 horizons, float32 discounts) of the next ``n`` gradient steps (None when the schedule is off); advances the count."""
+        if self._hz_schedule is None:
+            return None
+        if replay_buffer is not None:
+            self._check_horizon_replay(replay_buffer)
+        t = self._hz_step
+        self._hz_step = t + n
+        pairs = [horizon_schedule(*self._hz_schedule, t + i) for i in range(n)]
+        self._hz_last = pairs[-1]
+        return np.asarray([p[0] for p in pairs], dtype=np.int32), np.asarray([p[1] for p in pairs], dtype=np.float32)
+
+    def _run_graph(self, g) -> None:
+        """One replay of the captured update ``g``: the betas and the (horizon, discount) pairs of its S steps are its input."""
+        betas = self._next_betas(g.S)
+        pairs = self._next_horizons(g.S, g.rb)
+        g.run(betas) if pairs is None else g.run(betas, horizons=pairs[0], gammas=pairs[1])
+
+    def _horizon_logs(self) -> dict:
+        """The update horizon and the discount of the last gradient step, logged where the loss is; {} when the schedule is off."""
+        if self._hz_schedule is None:
+            return {}
+        return {"update_horizon": int(self._hz_last[0]), "gamma": float(self._hz_last[1])}
 
     # ------------------------------------------------------------------ random-shift augmentation
     augment_pad = 0   # 0: off
@@ -298,6 +382,8 @@ class EngineAgent:
             return None
         if self.architecture_type == "fc" and not (replay_buffer._obs_float and replay_buffer._stack_size == 1):
             return None  # (the captured fc step reads float32 vector observations with stack_size 1: _graph.py)
+        if self._hz_schedule is not None:
+            self._check_horizon_replay(replay_buffer)
         eng = self._engine_for(replay_buffer._batch_size)
         prioritized = hasattr(replay_buffer._sampling_distribution, "_tree")
         writeback = bool(getattr(self, "priority_writeback", False))
@@ -306,12 +392,13 @@ class EngineAgent:
             raise ValueError("importance-sampling weights (set_importance_sampling) need the prioritized sampling distribution")
         g = self._graphed
         if (g is None or g.rb is not replay_buffer or g.eng is not eng or g.writeback != (writeback and prioritized)
-                or g.weighted != weighted or getattr(g, "key", None) != key or g.S != steps or g.augment_pad != self.augment_pad):
+                or g.weighted != weighted or getattr(g, "key", None) != key or g.S != steps or g.augment_pad != self.augment_pad
+                or g.horizon != (self._hz_schedule is not None)):
             from slimdqn._graph import GraphedUpdate
 
             self._drop_graph()
             g = self._graphed = GraphedUpdate(replay_buffer, eng, prioritized, steps_per_graph=steps, writeback=writeback, learn=learn,
-                                              weighted=weighted,
+                                              weighted=weighted, horizon=self._hz_schedule is not None,
                                               augment=self._aug_state() if self.augment_pad else None, state=state)
             g.key = key
             self._captures = getattr(self, "_captures", 0) + 1
@@ -352,14 +439,16 @@ class EngineAgent:
     # ------------------------------------------------------------------ batches
     def _c_batch(self, eng: QNetEngine, samples):
         weights = getattr(samples, "weights", None)  # importance-sampling weights of the draw, when the batch carries them
+        discount = getattr(samples, "discount", None)  # per-row discounts of a gather at a horizon, when the batch carries them
         if hasattr(samples, "frame_ids") and self.architecture_type == "fc":
             # device replay of vector observations (LunarLander): the stored float32 bytes come back as (B, d) rows
             return eng.make_batch(state=samples.state, next_state=samples.next_state, action=samples.action, reward=samples.reward,
-                                  terminal=samples.is_terminal, loss_weights=weights)
+                                  terminal=samples.is_terminal, loss_weights=weights, discount=discount)
         if hasattr(samples, "frame_ids"):  # DeviceBatch from the device replay
             return eng.make_batch(
                 frames=samples.frames, frame_stride=samples.frame_stride, frame_ids=samples.frame_ids,
                 action=samples.action, reward=samples.reward, terminal=samples.is_terminal, loss_weights=weights,
+                discount=discount,
             )
         dev = eng.device
         as_t = lambda x, dt: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(dev).to(dt).contiguous()
@@ -639,6 +728,7 @@ class EngineAgent:
         self._resets += 1
         eng.reset(fresh, **factors)
         self._grad_clip_count = 0  # (the step count _grad_clip_logs measures its interval with starts again)
+        self._hz_step = 0  # (and the horizon schedule, as BBF's does after every reset)
         target = getattr(self, "target_params", None)
         if target is not None and target.tensor is not eng.params:
             eng.reset(fresh, params=target.tensor, **factors)

@@ -47,7 +47,7 @@ class AnalysisDQN(iSDQN):
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
             batch_samples = self._sample(replay_buffer)
-            batch_samples_eval = replay_buffer.sample()
+            batch_samples_eval = self._sample_eval(replay_buffer)
             (self.params, self.optimizer_state, losses, churn_train, churn_eval, cos_is_tb, cos_tf_tb) = self.learn_on_batch(
                 self.params, self.target_params, self.optimizer_state, batch_samples, batch_samples_eval)
             # (the step accumulates `losses` on the device as iSDQN does; the diagnostics are host sums like the reference's)

@@ -15,7 +15,7 @@ class AnalysisTFDQN(TFDQN):
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
             batch_samples = self._sample(replay_buffer)
-            batch_samples_eval = replay_buffer.sample()
+            batch_samples_eval = self._sample_eval(replay_buffer)
             self.params, self.optimizer_state, _, churn_train, churn_eval = self.learn_on_batch(
                 self.params, self.optimizer_state, batch_samples, batch_samples_eval)
             self.cumulated_target_churn_train += churn_train

@@ -134,7 +134,7 @@ class DQN(EngineAgent):
             else:
                 g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw()), key=target.data_ptr())
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
-                g.run(self._next_betas(g.S))
+                self._run_graph(g)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.target_params, self.optimizer_state, batch_samples)
@@ -165,6 +165,7 @@ class DQN(EngineAgent):
             logs = {"loss": self.cumulated_loss / (self.target_update_frequency / self.data_to_update)}
             self.cumulated_loss = 0
             logs.update(self._grad_clip_logs())
+            logs.update(self._horizon_logs())
             return True, logs
         return False, {}
 

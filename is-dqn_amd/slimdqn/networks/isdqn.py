@@ -143,7 +143,7 @@ class iSDQN(EngineAgent):
                 self.update_online_params(0, replay_buffer)
             return
         for _ in range(n_steps // g.S):
-            g.run(self._next_betas(g.S))
+            self._run_graph(g)
 
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
@@ -153,7 +153,7 @@ class iSDQN(EngineAgent):
             else:
                 g = self._graphed_update(replay_buffer)
             if g is not None:
-                g.run(self._next_betas(g.S))  # same draws, same kernels, same bits as the eager branch below (tests/test_gpu_graphed_update.py)
+                self._run_graph(g)  # same draws, same kernels, same bits as the eager branch below (tests/test_gpu_graphed_update.py)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
@@ -173,6 +173,7 @@ class iSDQN(EngineAgent):
                 logs[f"networks/{idx_network}_loss"] = self.cumulated_losses[idx_network] / norm
             self.cumulated_losses = np.zeros_like(self.cumulated_losses)
             logs.update(self._grad_clip_logs())
+            logs.update(self._horizon_logs())
             return True, logs
         return False, {}
 

@@ -113,7 +113,7 @@ class TFDQN(EngineAgent):
         if step % self.data_to_update == 0:
             g = self._graphed_update(replay_buffer)
             if g is not None:
-                g.run(self._next_betas(g.S))  # same draws, same kernels, same bits as the eager branch below
+                self._run_graph(g)  # same draws, same kernels, same bits as the eager branch below
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
@@ -126,6 +126,7 @@ class TFDQN(EngineAgent):
             logs = {"loss": self.cumulated_loss / (self.target_update_frequency / self.data_to_update)}
             self.cumulated_loss = 0
             logs.update(self._grad_clip_logs())
+            logs.update(self._horizon_logs())
             return True, logs
         return False, {}
 

@@ -9,6 +9,10 @@ leading padding, :131-134), action, n-step reward, terminal flag.  The reference
 4-frame stacks per element (snappy-compressed on the host); here 1e6 Atari elements are 7.06 GB of
 frames + 41 MB of rows, resident in the 288 GB of one MI355X.
 
+With ``horizon_window=True`` every element also keeps its whole window of ``update_horizon`` steps (frame ids, per-step rewards, length),
+and ``sample(horizon=, gamma=)`` cuts the rows at any horizon up to it and at any discount on the device (include/isdqn_hip.h,
+isdqn_replay_gather_horizon): what an annealed update horizon needs.
+
 ``sample()`` returns a ``DeviceBatch`` with the reference's field names.  The update path consumes
 its frame-id table directly (the first convolution gathers pixels through it); ``.state`` /
 ``.next_state`` materialise the reference's (B, h, w, stack) arrays on demand.
@@ -27,6 +31,9 @@ import torch
 
 from slimdqn import _hip
 from slimdqn.sample_collection import ReplayItemID
+
+
+HORIZON_MAX = 128  # include/isdqn_hip.h: the largest n_max of a horizon-window replay
 
 
 class TransitionElement(typing.NamedTuple):
@@ -61,9 +68,10 @@ class ReplayElement:
 class DeviceBatch:
     """A sampled batch (ReplayElement fields, replay_buffer.py:198-213) living on the GPU."""
 
-    def __init__(self, rb: "ReplayBuffer", indices, frame_ids, action, reward, is_terminal, weights=None, frames=None):
+    def __init__(self, rb: "ReplayBuffer", indices, frame_ids, action, reward, is_terminal, weights=None, frames=None, discount=None):
         """``frames``: another frame pool than the replay's store that ``frame_ids`` point into, same stride (ReplayBuffer.augment)."""
         self._rb = rb
+        self.discount = discount  # float32 [B] gamma ** horizon of a gather at a horizon (isdqn_replay_gather_horizon), else None
         self.weights = weights  # float32 [B] importance-sampling weights (prioritized sampling with a beta), else None
         self.indices = indices  # dense sampler indices (= sum-tree leaves), int32 [B]
         self.frame_ids = frame_ids  # int32 [B][2*stack]
@@ -168,7 +176,14 @@ class ReplayBuffer:
         compress: bool = True,
         clipping: callable = None,
         device: str | None = None,
+        horizon_window: bool = False,
     ):
+        """``horizon_window``: keep every element's whole window of ``update_horizon`` (= n_max, 1..128) steps -- frame ids, per-step
+        rewards, length -- beside the tables at n_max, so that ``sample`` / ``gather`` can cut it at any horizon up to n_max and at any
+        discount (include/isdqn_hip.h, isdqn_replay_gather_horizon).  False: none of it exists."""
+        self._horizon_window = bool(horizon_window)
+        if self._horizon_window and not 1 <= int(update_horizon) <= HORIZON_MAX:
+            raise ValueError(f"horizon_window needs update_horizon (n_max) in 1..{HORIZON_MAX}, got {update_horizon}")
         self.device = _hip.resolve_device(device)
         if self.device.type == "cuda":
             _hip.require_gpu()
@@ -220,6 +235,16 @@ class ReplayBuffer:
         self._h_elem_reward64 = np.zeros(C, np.float64)  # the reference keeps python floats (f64)
         self._h_elem_terminal = np.zeros(C, np.uint8)
         self._h_index_to_slot = np.zeros(C + 1, np.int32)
+        if self._horizon_window:
+            wn, n_max = self._stack_size + self._update_horizon, self._update_horizon
+            self._d_elem_window = torch.full((C, wn), -1, dtype=torch.int32, device=self.device)
+            self._d_elem_steps = torch.zeros(C, n_max, dtype=torch.float32, device=self.device)
+            self._d_elem_len = torch.zeros(C, dtype=torch.int32, device=self.device)
+            self._h_elem_window = np.full((C, wn), -1, np.int32)
+            self._h_elem_steps = np.zeros((C, n_max), np.float32)
+            self._h_elem_len = np.zeros(C, np.int32)
+            self._d_horizon = torch.zeros(1, dtype=torch.int32, device=self.device)  # python-number arguments of gather live here
+            self._d_gamma = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._refcount = np.zeros(self._n_frame_slots, np.int32)
         self._next_fresh = 0
         self._free = []
@@ -271,7 +296,7 @@ class ReplayBuffer:
         # Everything that changed since the last flush goes up in ONE pinned copy and is scattered by ONE launch
         # (isdqn_replay_apply_staged); nine pageable copies and six index_copy_ launches were ~290 us of host time per flush,
         # a quarter of the trainer's loop.
-        frames = rows = idx = None
+        frames = rows = idx = hrows = None
         if self._pending_frames:
             slots = np.fromiter(self._pending_frames.keys(), dtype=np.int32, count=len(self._pending_frames))
             frames = (slots, np.stack(list(self._pending_frames.values())))
@@ -280,6 +305,8 @@ class ReplayBuffer:
             r = np.unique(np.asarray(self._dirty_rows, dtype=np.int64))
             rows = (r.astype(np.int32), self._h_elem_frames[r], self._h_elem_action[r], self._h_elem_reward64[r].astype(np.float32),
                     self._h_elem_terminal[r])
+            if self._horizon_window:
+                hrows = (self._h_elem_window[r], self._h_elem_steps[r], self._h_elem_len[r])
             self._dirty_rows.clear()
         if self._dirty_index:
             r = np.unique(np.asarray(self._dirty_index, dtype=np.int64))
@@ -292,21 +319,13 @@ class ReplayBuffer:
                 at = torch.from_numpy(rows[0].astype(np.int64))
                 for dst, v in zip((self._d_elem_frames, self._d_elem_action, self._d_elem_reward, self._d_elem_terminal), rows[1:]):
                     dst[at] = torch.from_numpy(np.ascontiguousarray(v))
+                if hrows is not None:
+                    for dst, v in zip((self._d_elem_window, self._d_elem_steps, self._d_elem_len), hrows):
+                        dst[at] = torch.from_numpy(np.ascontiguousarray(v))
             if idx is not None:
                 self._d_index_to_slot[torch.from_numpy(idx[0].astype(np.int64))] = torch.from_numpy(idx[1])
             return
-        u = _hip.StagedUpdates()
-        sections = []  # (field name of the offset, array)
-        if frames is not None:
-            u.n_frames, u.frame_bytes = len(frames[0]), self._hw
-            sections += [("off_frame_slots", frames[0]), ("off_frame_data", frames[1])]
-        u.stack2 = 2 * self._stack_size
-        if rows is not None:
-            u.n_rows = len(rows[0])
-            sections += list(zip(("off_rows", "off_row_frames", "off_row_action", "off_row_reward", "off_row_terminal"), rows))
-        if idx is not None:
-            u.n_index = len(idx[0])
-            sections += [("off_index_rows", idx[0]), ("off_index_vals", idx[1])]
+        u, sections = self._staged_sections(frames, rows, idx, hrows)
         align = lambda n: (n + 15) & ~15
         total = sum(align(a.nbytes) for _n, a in sections)
         st = getattr(self, "_stage", None)
@@ -318,10 +337,14 @@ class ReplayBuffer:
         else:
             st["done"].synchronize()  # the previous flush's copy has left the pinned buffer (long ago)
         off = 0
+        hoff = {}  # offsets of the horizon sections: no fields of isdqn_staged_updates, arguments of their own launch
         for name, a in sections:
             a = np.ascontiguousarray(a)
             st["np"][off : off + a.nbytes] = a.reshape(-1).view(np.uint8)
-            setattr(u, name, off)
+            if name.startswith("horizon_"):
+                hoff[name] = off
+            else:
+                setattr(u, name, off)
             off += align(a.nbytes)
         st["dev"][:off].copy_(st["host"][:off], non_blocking=True)
         st["done"].record()
@@ -333,6 +356,34 @@ class ReplayBuffer:
             ),
             "isdqn_replay_apply_staged",
         )
+        if hrows is not None:
+            _hip.check(
+                self._lib.isdqn_replay_apply_staged_horizon(
+                    _hip.ptr(st["dev"]), u.n_rows, u.off_rows, hoff["horizon_window"], hoff["horizon_steps"], hoff["horizon_len"],
+                    self._stack_size, self._update_horizon, _hip.ptr(self._d_elem_window), _hip.ptr(self._d_elem_steps),
+                    _hip.ptr(self._d_elem_len), _hip.stream_ptr(self.device),
+                ),
+                "isdqn_replay_apply_staged_horizon",
+            )
+
+    def _staged_sections(self, frames, rows, idx, hrows=None):
+        """The isdqn_staged_updates counts of a flush and its sections in staging order: (field name of the offset, array).  The horizon
+        tables' rows (``hrows``) go behind everything else, so a buffer without them stages the bytes it always did."""
+        u = _hip.StagedUpdates()
+        sections = []
+        if frames is not None:
+            u.n_frames, u.frame_bytes = len(frames[0]), self._hw
+            sections += [("off_frame_slots", frames[0]), ("off_frame_data", frames[1])]
+        u.stack2 = 2 * self._stack_size
+        if rows is not None:
+            u.n_rows = len(rows[0])
+            sections += list(zip(("off_rows", "off_row_frames", "off_row_action", "off_row_reward", "off_row_terminal"), rows))
+        if idx is not None:
+            u.n_index = len(idx[0])
+            sections += [("off_index_rows", idx[0]), ("off_index_vals", idx[1])]
+        if hrows is not None:
+            sections += list(zip(("horizon_window", "horizon_steps", "horizon_len"), hrows))
+        return u, sections
 
     # ------------------------------------------------------------------ trajectory accumulator (:102-183)
     def _window_ids(self, last: int):
@@ -345,6 +396,11 @@ class ReplayBuffer:
         reward = 0.0
         for t in range(state_last, min(next_last, len(traj))):  # rewards state_last .. next_last-1 (:138-143)
             reward += traj[t][2] * (self._gamma ** (t - state_last))
+        if self._horizon_window:  # the whole window of the element, for add() (the yield that follows hands the element over)
+            stack, n_max, L = self._stack_size, self._update_horizon, len(traj)
+            window = [traj[p][0] if 0 <= p < L else -1 for p in range(state_last - stack + 1, state_last + n_max + 1)]
+            steps = [traj[t][2] if t < L else 0.0 for t in range(state_last, state_last + n_max)]
+            self._element_window = (window, steps, min(state_last + n_max, L) - state_last)
         return (self._window_ids(state_last) + self._window_ids(next_last), traj[state_last][1], reward, is_terminal)
 
     def _pop_left(self):
@@ -404,10 +460,20 @@ class ReplayBuffer:
             key = ReplayItemID(self.add_count)
             slot = key % C
             evict = self.add_count >= C  # the row being overwritten belongs to key - C, evicted below
-            old_ids = self._h_elem_frames[slot].copy() if evict else None
-            for f in ids:
-                if f >= 0:
-                    self._refcount[f] += 1
+            if self._horizon_window:  # the reference counts run over the window, a superset of the 2 * stack ids
+                window, steps, length = self._element_window
+                old_ids = self._h_elem_window[slot].copy() if evict else None
+                for f in window:
+                    if f >= 0:
+                        self._refcount[f] += 1
+                self._h_elem_window[slot] = window
+                self._h_elem_steps[slot] = steps
+                self._h_elem_len[slot] = length
+            else:
+                old_ids = self._h_elem_frames[slot].copy() if evict else None
+                for f in ids:
+                    if f >= 0:
+                        self._refcount[f] += 1
             self._h_elem_frames[slot] = ids
             self._h_elem_action[slot] = action
             self._h_elem_reward64[slot] = reward
@@ -425,9 +491,12 @@ class ReplayBuffer:
                 for f in old_ids:
                     self._unref(int(f))
 
-    def sample(self, size=None, beta=None) -> DeviceBatch:
+    def sample(self, size=None, beta=None, horizon=None, gamma=None) -> DeviceBatch:
         """``beta`` (prioritized sampling only; python float or device float32 scalar): the batch also carries the
-        importance-sampling weights of its draws (``DeviceBatch.weights``)."""
+        importance-sampling weights of its draws (``DeviceBatch.weights``).
+        ``horizon`` and ``gamma`` (both or neither; ``horizon_window=True`` only; python numbers, or a device int32 and a device float32
+        scalar): the rows are cut at that horizon, clamped to 1..n_max, their returns summed at that discount, and the batch carries
+        ``DeviceBatch.discount`` = gamma ** horizon per row."""
         assert self.add_count, ValueError("No samples in replay buffer!")
         if size is None:
             size = self._batch_size
@@ -436,12 +505,26 @@ class ReplayBuffer:
             if not hasattr(self._sampling_distribution, "sample_weighted_device"):
                 raise ValueError("importance-sampling weights (beta) need the prioritized sampling distribution")
             indices, weights = self._sampling_distribution.sample_weighted_device(size, beta)
-            return self.gather(indices, weights=weights)
+            return self.gather(indices, weights=weights, horizon=horizon, gamma=gamma)
         indices = self._sampling_distribution.sample_device(size)
-        return self.gather(indices)
+        return self.gather(indices, horizon=horizon, gamma=gamma)
 
-    def gather(self, indices: torch.Tensor, weights: torch.Tensor | None = None) -> DeviceBatch:
-        """Rows of the element table for dense sampler indices (device int32)."""
+    def _horizon_scalar(self, value, own: torch.Tensor) -> torch.Tensor:
+        """A device scalar for a ``horizon`` / ``gamma`` argument: a tensor is the caller's own, a python number goes into the buffer's."""
+        if torch.is_tensor(value):
+            assert value.dtype == own.dtype and value.numel() == 1 and value.device == own.device, (
+                f"horizon / gamma as a tensor: one {own.dtype} element on {own.device}")
+            return value
+        own.fill_(value)
+        return own
+
+    def gather(self, indices: torch.Tensor, weights: torch.Tensor | None = None, horizon=None, gamma=None) -> DeviceBatch:
+        """Rows of the element table for dense sampler indices (device int32); with ``horizon`` and ``gamma``, of the horizon windows
+        (``sample``)."""
+        if (horizon is None) != (gamma is None):
+            raise ValueError("horizon and gamma are given both or neither")
+        if horizon is not None and not self._horizon_window:
+            raise ValueError("a horizon needs a replay built with horizon_window=True")
         if self._lib is None:
             raise RuntimeError("ReplayBuffer.sample needs the HIP path (device='cuda:N'); there is no CPU fallback")
         B = int(indices.numel())
@@ -450,6 +533,11 @@ class ReplayBuffer:
         action = torch.empty(B, dtype=torch.int32, device=self.device)
         reward = torch.empty(B, dtype=torch.float32, device=self.device)
         terminal = torch.empty(B, dtype=torch.uint8, device=self.device)
+        if horizon is not None:
+            discount = torch.empty(B, dtype=torch.float32, device=self.device)
+            self.gather_horizon_into(indices, self._horizon_scalar(horizon, self._d_horizon), self._horizon_scalar(gamma, self._d_gamma),
+                                     ids, action, reward, terminal, discount)
+            return DeviceBatch(self, indices, ids, action, reward, terminal, weights, discount=discount)
         _hip.check(
             self._lib.isdqn_replay_gather_rows(
                 _hip.ptr(self._d_elem_frames), _hip.ptr(self._d_elem_action), _hip.ptr(self._d_elem_reward),
@@ -459,6 +547,19 @@ class ReplayBuffer:
             "isdqn_replay_gather_rows",
         )
         return DeviceBatch(self, indices, ids, action, reward, terminal, weights)
+
+    def gather_horizon_into(self, indices, horizon, gamma, ids, action, reward, terminal, discount) -> None:
+        """One isdqn_replay_gather_horizon launch on the current stream: the rows of ``indices`` cut at the device scalars ``horizon``
+        (int32) and ``gamma`` (float32), into the caller's tensors."""
+        _hip.check(
+            self._lib.isdqn_replay_gather_horizon(
+                _hip.ptr(self._d_elem_window), _hip.ptr(self._d_elem_steps), _hip.ptr(self._d_elem_len), _hip.ptr(self._d_elem_action),
+                _hip.ptr(self._d_elem_terminal), self._stack_size, self._update_horizon, _hip.ptr(self._d_index_to_slot),
+                _hip.ptr(indices), int(indices.numel()), _hip.ptr(horizon), _hip.ptr(gamma), _hip.ptr(ids), _hip.ptr(action),
+                _hip.ptr(reward), _hip.ptr(terminal), _hip.ptr(discount), _hip.stream_ptr(self.device),
+            ),
+            "isdqn_replay_gather_horizon",
+        )
 
     def _augment_pool(self, n_rows: int):
         """The scratch frame pool and id table of an augmented batch of ``n_rows`` rows: allocated once per row count, then reused."""
@@ -498,7 +599,8 @@ class ReplayBuffer:
         n_rows = len(batch)
         pool, table = self._augment_pool(n_rows)
         self.augment_into(batch.frame_ids, n_rows, n_rows, pad, seed, count, pool, table)
-        return DeviceBatch(self, batch.indices, table, batch.action, batch.reward, batch.is_terminal, batch.weights, frames=pool)
+        return DeviceBatch(self, batch.indices, table, batch.action, batch.reward, batch.is_terminal, batch.weights, frames=pool,
+                           discount=batch.discount)
 
     def update(self, keys, **kwargs: Any) -> None:
         self._sampling_distribution.update(keys, **kwargs)
@@ -529,15 +631,36 @@ class ReplayBuffer:
         self._h_elem_frames[:n_elements, :stack] = base + np.arange(stack, dtype=np.int32)[None]
         self._h_elem_frames[:n_elements, stack:] = base + n + np.arange(stack, dtype=np.int32)[None]
         self._h_elem_action[:n_elements] = rng.integers(0, n_actions, n_elements)
-        self._h_elem_reward64[:n_elements] = rng.choice([-1.0, 0.0, 1.0], size=n_elements, p=[0.05, 0.9, 0.05])
-        self._h_elem_terminal[:n_elements] = rng.random(n_elements) < p_terminal
+        if self._horizon_window:
+            # windows i .. i + stack + n - 1; iid step rewards from the same distribution and their discounted sum at n; a terminal element
+            # ends after `len` steps, uniform in 1..n: nothing behind window position stack - 1 + len, no reward behind step len
+            window = base + np.arange(stack + n, dtype=np.int32)[None]
+            steps = rng.choice([-1.0, 0.0, 1.0], size=(n_elements, n), p=[0.05, 0.9, 0.05])
+            self._h_elem_terminal[:n_elements] = rng.random(n_elements) < p_terminal
+            length = np.where(self._h_elem_terminal[:n_elements] != 0, rng.integers(1, n + 1, n_elements), n).astype(np.int32)
+            window = np.where(np.arange(stack + n)[None] > (stack - 1 + length)[:, None], -1, window).astype(np.int32)
+            steps = np.where(np.arange(n)[None] < length[:, None], steps, 0.0)
+            self._h_elem_window[:n_elements] = window
+            self._h_elem_steps[:n_elements] = steps
+            self._h_elem_len[:n_elements] = length
+            self._h_elem_frames[:n_elements, stack:] = window[:, n:]
+            self._h_elem_reward64[:n_elements] = (steps * (float(self._gamma) ** np.arange(n))[None]).sum(axis=1)
+            live = window[window >= 0]
+        else:
+            self._h_elem_reward64[:n_elements] = rng.choice([-1.0, 0.0, 1.0], size=n_elements, p=[0.05, 0.9, 0.05])
+            self._h_elem_terminal[:n_elements] = rng.random(n_elements) < p_terminal
+            live = self._h_elem_frames[:n_elements].reshape(-1)
         self._h_index_to_slot[:n_elements] = np.arange(n_elements, dtype=np.int32)
-        np.add.at(self._refcount, self._h_elem_frames[:n_elements].reshape(-1), 1)
+        np.add.at(self._refcount, live, 1)
         self._next_fresh = n_frames
         self._d_elem_frames.copy_(torch.from_numpy(self._h_elem_frames))
         self._d_elem_action.copy_(torch.from_numpy(self._h_elem_action))
         self._d_elem_reward.copy_(torch.from_numpy(self._h_elem_reward64.astype(np.float32)))
         self._d_elem_terminal.copy_(torch.from_numpy(self._h_elem_terminal))
         self._d_index_to_slot.copy_(torch.from_numpy(self._h_index_to_slot))
+        if self._horizon_window:
+            self._d_elem_window.copy_(torch.from_numpy(self._h_elem_window))
+            self._d_elem_steps.copy_(torch.from_numpy(self._h_elem_steps))
+            self._d_elem_len.copy_(torch.from_numpy(self._h_elem_len))
         self.add_count = n_elements
         self._sampling_distribution.add_bulk(range(n_elements), priorities)
