@@ -5,6 +5,7 @@ wrappers over the C-ABI entry points.  Pure plumbing: no arithmetic of the hot p
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 import math
 from typing import Dict, Sequence
@@ -145,6 +146,106 @@ def check_augment(pad, architecture_type) -> None:
         raise ValueError(AUGMENT_FC_REFUSED)
 
 
+@dataclasses.dataclass(frozen=True)
+class NetOptions:
+    """The head, loss and exploration options that the agents (iSDQN, DQN, TFDQN and the analysis agents) and QNetEngine share, as one
+    checked value.  Field names are the constructors' keyword names, defaults are QNetEngine's; this is the one place that documents
+    them (the agents' docstrings say only what is particular to them).
+
+    ``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss (with quantile heads: kappa).
+    ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
+    cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins; n_heads * n_actions * n_bins logits, region
+    "logits"); acting and ``forward`` use the expectations.
+    ``double_q``: Double Q-learning targets (van Hasselt et al. 2016; include/isdqn_hip.h, isdqn_net_config::double_q) -- iS-DQN's online
+    head 1 + k picks the next action that head k values, DQN's online parameters pick the action its target parameters value; off keeps
+    the reference's max.  The *_target forms then keep the target network's rows in region "q_target".
+    ``munchausen_tau`` > 0: Munchausen targets (Vieillard et al. 2020) -- the bootstrap value is the soft value
+    tau * logsumexp(Q / tau) of the value head and ``munchausen_alpha`` * clip(tau ln pi(a|s), ``munchausen_clip``, 0) is added to the
+    reward (include/isdqn_hip.h, isdqn_net_config::munchausen_tau); 0 is off.  The *_target forms then keep the target network's rows of
+    concat(state, next_state) in region "q_target".  Not together with ``double_q`` (ValueError).
+    ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
+    quantile-regression loss with kappa = ``huber_delta`` (include/isdqn_hip.h, isdqn_net_config::n_quantiles); acting uses
+    their means.  Not with ``n_bins`` > 0, Munchausen targets or batch_norm (ValueError).
+    ``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
+    isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
+    ``n_quantiles`` > 0 or Munchausen targets (ValueError).
+    ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
+    Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
+    halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
+    values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
+    ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
+    optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
+    the device in region "grad_clip" and an agent's ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient
+    steps) and ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the
+    impala torso: ValueError.
+    ``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
+    included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)).  In an
+    agent every acting call on its own parameters draws first (one draw serves all rows of a batched call), every learn step draws
+    first, and ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network; ``get_model()`` then carries
+    "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise
+    alone.  Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError: ``check_noisy``, which the constructors call
+    beside ``check``)."""
+
+    huber_delta: float = 0.0
+    n_bins: int = 0
+    min_value: float = -100.0
+    max_value: float = 100.0
+    sigma: float = 3.0
+    double_q: bool = False
+    munchausen_tau: float = 0.0
+    munchausen_alpha: float = 0.9
+    munchausen_clip: float = -1.0
+    n_quantiles: int = 0
+    categorical: bool = False
+    dueling: bool = False
+    max_grad_norm: float = 0.0
+    noisy: bool = False
+    noisy_sigma0: float = 0.5
+
+    @classmethod
+    def pick(cls, mapping) -> "NetOptions":
+        """The options among the entries of ``mapping`` (a constructor's ``locals()``), each converted to the type of its default."""
+        return cls(**{f.name: type(f.default)(mapping[f.name]) for f in dataclasses.fields(cls)})
+
+    def check(self, architecture_type, features, batch_norm=False) -> None:
+        """The head and loss rules, once, in this order: dueling, gradient clipping, Munchausen with double_q, categorical, quantiles --
+        the first rule violated answers.  ``check_noisy`` and ``check_augment`` are not in here, because the constructors place them
+        differently around this call: QNetEngine asks ``check_noisy`` first; an agent asks its own rules first (iSDQN: ema_tau;
+        TFDQN: double_q, then ema_tau; DQN: Munchausen with double_q in front, ema_tau behind), then this, then ``check_augment``, then
+        ``check_noisy`` (tests/golden/options_snapshot.txt holds which refusal answers first for every pair of settings)."""
+        check_dueling(self.dueling, architecture_type, features, batch_norm)
+        check_grad_clip(self.max_grad_norm, architecture_type, batch_norm)
+        check_munchausen(self.double_q, self.munchausen_tau)
+        check_categorical(self.categorical, self.n_bins, self.n_quantiles, self.munchausen_tau)
+        check_quantiles(self.n_quantiles, self.n_bins, self.munchausen_tau, batch_norm)
+
+    def fill(self, cfg: "_hip.NetConfig") -> None:
+        """Write the options into an isdqn_net_config.  An option that is off leaves ``max_grad_norm``, ``categorical`` and ``dueling``
+        at the 0 the structure starts with; without ``n_bins`` the three hl_* fields are 0."""
+        if self.max_grad_norm > 0.0:
+            cfg.max_grad_norm = self.max_grad_norm
+        cfg.huber_delta = self.huber_delta
+        cfg.n_bins = self.n_bins
+        cfg.hl_min, cfg.hl_max, cfg.hl_sigma = (self.min_value, self.max_value, self.sigma) if self.n_bins else (0.0, 0.0, 0.0)
+        if self.categorical:
+            cfg.categorical = 1
+        cfg.n_quantiles = self.n_quantiles
+        if self.dueling:
+            cfg.dueling = 1
+        cfg.double_q = 1 if self.double_q else 0
+        cfg.munchausen_tau, cfg.munchausen_alpha, cfg.munchausen_clip = self.munchausen_tau, self.munchausen_alpha, self.munchausen_clip
+
+    def engine_kwargs(self, noisy_seed: int = 0) -> dict:
+        """The keywords that build a QNetEngine with these options.  ``noisy_sigma0`` and the seed of the draws go only with ``noisy``:
+        an engine without noise reads neither and keeps its defaults."""
+        kw = dataclasses.asdict(self)
+        if self.noisy:
+            kw["noisy_seed"] = noisy_seed
+        else:
+            del kw["noisy_sigma0"]
+        return kw
+
+
 def dueling_live_mask(n_hidden: int, n_heads: int, n_actions: int, width: int = 1) -> np.ndarray:
     """Which entries of the dueling head's Flax kernel (F, R) are weights (True) and which structural zeros (include/isdqn_hip.h,
     isdqn_net_config::dueling): column ((h * (A + 1)) + c) * width + j is a value column for c = A and reads the hidden units
@@ -194,13 +295,11 @@ class QNetEngine:
         ``sigma``, ``sigma_m``, ``sigma_v``, ``noise``, ``eff``, ``grad`` and ``noise_count``; ``init_params`` writes sigma =
         noisy_sigma0 / sqrt(in_f) on the real elements of the Dense kernels and biases (in_f: the true fan-in; the live fan-in F / 2 on
         a dueling head) and 0 elsewhere.  ``mu`` keeps the existing initialiser -- a deviation from the paper, which draws mu uniformly
-        from +-1 / sqrt(in_f).  Without ``noisy`` nothing new is allocated and every call takes exactly the code path it had."""
+        from +-1 / sqrt(in_f).  Without ``noisy`` nothing new is allocated and every call takes exactly the code path it had.
+        The other option keywords: NetOptions."""
+        options = self.options = NetOptions.pick(locals())
         check_noisy(noisy, architecture_type, batch_norm, max_grad_norm)
-        check_dueling(dueling, architecture_type, features, batch_norm)
-        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
-        check_munchausen(double_q, munchausen_tau)
-        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
-        check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
+        options.check(architecture_type, features, batch_norm)
         _hip.require_gpu()
         self.lib = _hip.lib()
         self.device = _hip.resolve_device(device)
@@ -233,40 +332,12 @@ class QNetEngine:
         cfg.learning_rate = float(learning_rate)
         cfg.adam_b1, cfg.adam_b2 = 0.9, 0.999
         cfg.adam_eps = float(adam_eps)
-        # max_grad_norm > 0 (inf allowed): the gradient is clipped by its global norm in front of Adam and the norm is kept in region
-        # "grad_clip" (include/isdqn_hip.h, isdqn_net_config::max_grad_norm).  0 leaves the field at its 0
-        if float(max_grad_norm) > 0.0:
-            cfg.max_grad_norm = float(max_grad_norm)
-        self.max_grad_norm = float(max_grad_norm)
-        cfg.huber_delta = float(huber_delta)  # 0: the reference's squared TD error
         cfg.batch_norm = 1 if batch_norm else 0  # architectures/dqn.py:52-53, 59-60, 66-67, 73-74, 100-101 (csrc/batchnorm.h)
         self.batch_norm = bool(batch_norm)
-        # n_bins > 0: HL-Gauss histogram heads (n_heads * n_actions * n_bins logits, region "logits"); forward still returns Q-values
-        cfg.n_bins = int(n_bins)
-        cfg.hl_min, cfg.hl_max, cfg.hl_sigma = (float(min_value), float(max_value), float(sigma)) if n_bins else (0.0, 0.0, 0.0)
-        self.n_bins = int(n_bins)
-        # categorical: the histogram heads train on the C51 categorical projection loss (include/isdqn_hip.h,
-        # isdqn_net_config::categorical) instead of HL-Gauss; sigma is then ignored.  False leaves the field at its 0
-        if categorical:
-            cfg.categorical = 1
-        self.categorical = bool(categorical)
-        # n_quantiles > 0: QR-DQN heads (n_heads * n_actions * n_quantiles quantile values, region "logits"; kappa = huber_delta);
-        # forward still returns Q-values, their means
-        cfg.n_quantiles = int(n_quantiles)
-        self.n_quantiles = int(n_quantiles)
-        # dueling: the last Dense holds a value row and n_actions advantage rows per head, read from the two halves of the last hidden
-        # layer and combined on the device (include/isdqn_hip.h, isdqn_net_config::dueling).  False leaves the field at its 0
-        if dueling:
-            cfg.dueling = 1
-        self.dueling = bool(dueling)
-        # Double Q-learning targets (include/isdqn_hip.h, isdqn_net_config::double_q); the *_target forms then keep the target
-        # network's rows in region "q_target"
-        cfg.double_q = 1 if double_q else 0
-        self.double_q = bool(double_q)
-        # Munchausen targets (include/isdqn_hip.h, isdqn_net_config::munchausen_tau): tau = 0 is off; the *_target forms then keep
-        # the target network's rows of concat(state, next_state) in region "q_target"
-        cfg.munchausen_tau, cfg.munchausen_alpha, cfg.munchausen_clip = float(munchausen_tau), float(munchausen_alpha), float(munchausen_clip)
-        self.munchausen_tau, self.munchausen_alpha, self.munchausen_clip = float(munchausen_tau), float(munchausen_alpha), float(munchausen_clip)
+        options.fill(cfg)
+        for name in ("max_grad_norm", "n_bins", "categorical", "n_quantiles", "dueling", "double_q", "munchausen_tau", "munchausen_alpha",
+                     "munchausen_clip"):  # (plain attributes of the engine; its ``sigma`` is the noisy tensor, not the histogram's std)
+            setattr(self, name, getattr(options, name))
         self.cfg = cfg
         self.features = feats
         self.architecture_type = architecture_type
@@ -318,6 +389,21 @@ class QNetEngine:
                 self.noise_target = torch.zeros_like(self.noise)
                 self.eff_target = torch.zeros_like(self.params)
             self._noise_zero = True  # the buffers above: zero noise, the mean network
+
+    def copy_state_from(self, old: "QNetEngine") -> None:
+        """Take over the training state of ``old``, an engine of the same network and options at another batch size (same parameter
+        layout, another workspace): parameters, Adam's moments and count, the loss accumulator, and what the options own -- noisy: sigma,
+        its moments and the draw counter; clipping: the two gradient-norm accumulators.  Copies on the current stream."""
+        self.params.copy_(old.params)
+        self.adam_m.copy_(old.adam_m)
+        self.adam_v.copy_(old.adam_v)
+        self.adam_count.copy_(old.adam_count)
+        self.losses_accum.copy_(old.losses_accum)
+        if self.noisy:
+            for name in ("sigma", "sigma_m", "sigma_v", "noise_count"):
+                getattr(self, name).copy_(getattr(old, name))
+        if self.max_grad_norm > 0.0:
+            self.grad_clip[2:4].copy_(old.grad_clip[2:4])
 
     # ------------------------------------------------------------------ noisy Dense layers
     noisy = False  # (class default: an engine built without the option, or a host-side stand-in for the layout)
@@ -619,6 +705,7 @@ class QNetEngine:
             raise ValueError("set_max_grad_norm: the engine must have been built with max_grad_norm > 0 and the new threshold must be > 0")
         self.cfg.max_grad_norm = c
         self.max_grad_norm = c
+        self.options = dataclasses.replace(self.options, max_grad_norm=c)
 
     # ------------------------------------------------------------------ C-ABI calls
     def make_batch(self, *, frames=None, frame_stride=0, frame_ids=None, state=None, next_state=None, action=None, reward=None, terminal=None,

@@ -2,11 +2,13 @@
 conversion, single-observation forward.  No arithmetic of the hot path lives here."""
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 import torch
 
 from slimdqn import _hip
-from slimdqn._engine import QNetEngine, check_augment, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_noisy, check_quantiles, check_redo
+from slimdqn._engine import NetOptions, QNetEngine, check_augment, check_noisy, check_redo
 
 
 class DeviceParams:
@@ -248,28 +250,24 @@ class EngineAgent:
         return int(self.augment_pad), self._aug_seed, self.aug_count
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
-                           learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta=0.0, batch_norm=False,
-                           n_bins=0, min_value=-100.0, max_value=100.0, sigma=3.0, double_q=False,
-                           munchausen_tau=0.0, munchausen_alpha=0.9, munchausen_clip=-1.0, n_quantiles=0, categorical=False, dueling=False,
-                           max_grad_norm=0.0, noisy=False, noisy_sigma0=0.5, augment_pad=0):
+                           learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options: NetOptions,
+                           batch_norm=False, augment_pad=0):
+        """``options``: what the constructor picked and checked (NetOptions.check, behind its own rules); the two rules that stand
+        behind it follow here.  Every option becomes a plain attribute of the agent and goes to every engine it builds.
+        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
+        every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
+        [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
+        draws).  Acting, ``recycle_dormant`` and the analysis agents' evaluation passes see the frames as stored.  Every torso but 'fc'
+        (ValueError); needs the device replay.  0 is off."""
         check_augment(augment_pad, architecture_type)
-        check_noisy(noisy, architecture_type, batch_norm, max_grad_norm)
-        self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
+        check_noisy(options.noisy, architecture_type, batch_norm, options.max_grad_norm)
+        self.options = options
+        for name, value in dataclasses.asdict(options).items():
+            setattr(self, name, value)
         self.noisy_eval = False  # True: acting calls run the mean network (zero noise) instead of drawing
         self._bound_sigma = None
-        check_dueling(dueling, architecture_type, features, batch_norm)
-        self.dueling = bool(dueling)
-        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
-        self.max_grad_norm = float(max_grad_norm)
         self._grad_clip_count = 0  # Adam step count at the last read of the gradient-norm accumulators (_grad_clip_logs)
-        check_munchausen(double_q, munchausen_tau)
-        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
-        self.categorical = bool(categorical)
-        check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
-        self.n_quantiles = int(n_quantiles)
         self.n_actions = n_actions
-        self.double_q = bool(double_q)
-        self.munchausen_tau, self.munchausen_alpha, self.munchausen_clip = float(munchausen_tau), float(munchausen_alpha), float(munchausen_clip)
         self.batch_norm = bool(batch_norm)
         self._n_heads = int(n_heads)
         self.features = [int(f) for f in features]
@@ -281,8 +279,6 @@ class EngineAgent:
         self.gamma = gamma
         self.update_horizon = update_horizon
         self.precision = precision
-        self.huber_delta = float(huber_delta)
-        self.n_bins, self.min_value, self.max_value, self.sigma = int(n_bins), float(min_value), float(max_value), float(sigma)
         self.device = device
         self._seed = int(key) if not isinstance(key, torch.Generator) else int(key.initial_seed())
         self._engine = None
@@ -298,30 +294,16 @@ class EngineAgent:
     def _make_engine(self, batch_size: int, init: bool = False) -> None:
         old = self._engine
         eng = QNetEngine(
-            self.observation_dim, self.n_actions, self._n_heads, self.features, self.architecture_type,
-            self.layer_norm, batch_size, gamma_n=self.gamma**self.update_horizon, learning_rate=self.learning_rate,
-            adam_eps=self.adam_eps, precision=self.precision, device=self.device, huber_delta=self.huber_delta, batch_norm=self.batch_norm,
-            n_bins=self.n_bins, min_value=self.min_value, max_value=self.max_value, sigma=self.sigma,
-            double_q=self.double_q,
-            munchausen_tau=self.munchausen_tau, munchausen_alpha=self.munchausen_alpha, munchausen_clip=self.munchausen_clip,
-            n_quantiles=self.n_quantiles, categorical=self.categorical, dueling=self.dueling, max_grad_norm=self.max_grad_norm,
-            **(dict(noisy=True, noisy_sigma0=self.noisy_sigma0, noisy_seed=self._seed) if self.noisy else {}),
+            self.observation_dim, self.n_actions, self._n_heads, self.features, self.architecture_type, self.layer_norm, batch_size,
+            gamma_n=self.gamma**self.update_horizon, learning_rate=self.learning_rate, adam_eps=self.adam_eps, precision=self.precision,
+            device=self.device, batch_norm=self.batch_norm, **self.options.engine_kwargs(noisy_seed=self._seed),
         )
         if self.noisy:
             eng.resample_on_learn = True  # every learn step of an agent draws first (eager and captured alike)
         if init:
             eng.init_params(self._seed)
         else:  # a batch of another size arrived: same parameter layout, new workspace
-            eng.params.copy_(old.params)
-            eng.adam_m.copy_(old.adam_m)
-            eng.adam_v.copy_(old.adam_v)
-            eng.adam_count.copy_(old.adam_count)
-            eng.losses_accum.copy_(old.losses_accum)
-            if self.noisy:
-                for name in ("sigma", "sigma_m", "sigma_v", "noise_count"):
-                    getattr(eng, name).copy_(getattr(old, name))
-            if self.max_grad_norm > 0.0:
-                eng.grad_clip[2:4].copy_(old.grad_clip[2:4])
+            eng.copy_state_from(old)
         self._drop_graph()  # captured against the old engine's buffers
         self._engine = eng
         if self._trust_mirror is not None:

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles
+from slimdqn._engine import NetOptions, check_munchausen
 from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -52,51 +52,20 @@ class DQN(EngineAgent):
         augment_pad: int = 0,
         ema_tau: float = 0.0,
     ):
-        """``ema_tau`` > 0: EMA (Polyak) target network (include/isdqn_hip.h, isdqn_net_ema; SR-SPR, BBF) -- every gradient step is
+        """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
+        EngineAgent._init_engine_agent.  Particular to DQN:
+        ``ema_tau`` > 0: EMA (Polyak) target network (include/isdqn_hip.h, isdqn_net_ema; SR-SPR, BBF) -- every gradient step is
         followed by target <- (1 - tau) * target + tau * online on the device (noisy: ``target_sigma`` likewise), in the eager step
         and inside the captured one, on the step's own stream; ``update_target_params`` then copies nothing and only reports its
         logs.  0 keeps the hard copy every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
-        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
-        every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
-        [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
-        draws).  Acting and ``recycle_dormant`` see the frames as stored.  Every torso but 'fc' (ValueError); needs the device replay.
-        0 is off.
-        ``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
-        included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
-        call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
-        ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
-        "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise alone.
-        Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError).
-        The target network has a sigma of its own (copied with the parameters at every target update) and, in every learn step, a draw
-        of its own (stream 1), as in Fortunato's DQN.
-        ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
-        optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
-        the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
-        ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
-        torso: ValueError.
-        ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
-        Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
-        halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
-        values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
-        ``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
-        isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
-        ``n_quantiles`` > 0 or Munchausen targets (ValueError).
-        ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
-        quantile-regression loss with kappa = ``huber_delta`` (include/isdqn_hip.h, isdqn_net_config::n_quantiles); acting uses
-        their means.  Not with ``n_bins`` > 0, Munchausen targets or batch_norm (ValueError).
-        ``huber_delta``: 0 keeps the reference's squared TD error; > 0 trains on the Huber loss (with quantile heads: kappa).
-        ``munchausen_tau`` > 0: Munchausen targets (Vieillard et al. 2020) -- the bootstrap value is the soft value
-        tau * logsumexp(Q / tau) of the value head and alpha * clip(tau ln pi(a|s), munchausen_clip, 0) is added to the reward
-        (include/isdqn_hip.h, isdqn_net_config::munchausen_tau); 0 is off.  Here the
-        target parameters then run over the states as well as the next states: about one more forward of B images per step.  Not together with ``double_q`` (ValueError).
-        ``double_q``: Double DQN (van Hasselt et al. 2016) -- the online parameters pick the next action, the target parameters
-        value it (include/isdqn_hip.h, isdqn_net_config::double_q): one more forward per step.
-        ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h)."""
-        check_munchausen(double_q, munchausen_tau)
-        check_dueling(dueling, architecture_type, features, False)
-        check_grad_clip(max_grad_norm, architecture_type, False)
-        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
-        check_quantiles(n_quantiles, n_bins, munchausen_tau)
+        ``noisy``: the target network has a sigma of its own (copied with the parameters at every target update) and, in every learn
+        step, a draw of its own (stream 1), as in Fortunato's DQN.
+        ``double_q``: the online parameters pick the next action, the target parameters value it: one more forward per step.
+        ``munchausen_tau`` > 0: the target parameters run over the states as well as the next states: about one more forward of B
+        images per step."""
+        options = NetOptions.pick(locals())
+        check_munchausen(double_q, munchausen_tau)  # (in front of the other rules, where this constructor has always asked it)
+        options.check(architecture_type, features)
         self.ema_tau = check_ema_tau(ema_tau, supported=True)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
@@ -104,11 +73,7 @@ class DQN(EngineAgent):
         self.target_update_frequency = target_update_frequency
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
-                                gamma, update_horizon, adam_eps, batch_size, precision, device, n_bins=n_bins, min_value=min_value,
-                                max_value=max_value, sigma=sigma, double_q=double_q, munchausen_tau=munchausen_tau,
-                                munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm,
-                                noisy=noisy, noisy_sigma0=noisy_sigma0, augment_pad=augment_pad)
+                                gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad)
         self.target_params = self.params.copy()  # dqn.py:34
         self.target_sigma = self._engine.sigma.clone() if self.noisy else None  # (one persistent buffer, refreshed in place like the target)
         self.cumulated_loss = 0

@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from slimdqn._engine import QNetEngine, check_categorical, check_dueling, check_grad_clip, check_munchausen, check_quantiles
+from slimdqn._engine import NetOptions
 from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -64,47 +64,12 @@ class iSDQN(EngineAgent):
         augment_pad: int = 0,
         ema_tau: float = 0.0,
     ):
-        """``ema_tau`` > 0 is refused (EMA_REFUSED): the target is head 0 of the online parameters.
-        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
-        every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
-        [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
-        draws).  Acting, ``recycle_dormant`` and the evaluation passes see the frames as stored.  Every torso but 'fc' (ValueError);
-        needs the device replay.  0 is off.
-        ``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
-        included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
-        call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
-        ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
-        "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise alone.
-        Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError).
-        ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
-        optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
-        the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
-        ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
-        torso: ValueError.
-        ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
-        Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
-        halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
-        values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
-        ``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
-        isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
-        ``n_quantiles`` > 0 or Munchausen targets (ValueError).
-        ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
-        quantile-regression loss with kappa = ``huber_delta`` (include/isdqn_hip.h, isdqn_net_config::n_quantiles); acting uses
-        their means.  Not with ``n_bins`` > 0, Munchausen targets or batch_norm (ValueError).
-        ``munchausen_tau`` > 0: Munchausen targets (Vieillard et al. 2020) -- the bootstrap value is the soft value
-        tau * logsumexp(Q / tau) of the value head and alpha * clip(tau ln pi(a|s), munchausen_clip, 0) is added to the reward
-        (include/isdqn_hip.h, isdqn_net_config::munchausen_tau); 0 is off.  Not together with ``double_q`` (ValueError).
-        ``double_q``: Double Q-learning targets -- online head 1 + k picks the next action that head k values
-        (include/isdqn_hip.h, isdqn_net_config::double_q); off keeps the reference's max.
-        ``huber_delta``: 0 keeps the reference's squared TD error (isdqn.py:102); > 0 trains on the Huber loss.
-        ``n_bins`` > 0: each head predicts a histogram of ``n_bins`` bins over [min_value, max_value] and trains on the HL-Gauss
-        cross-entropy with std ``sigma`` (include/isdqn_hip.h, isdqn_net_config::n_bins); acting uses the expectations."""
+        """The option keywords from ``huber_delta`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
+        EngineAgent._init_engine_agent.  Here ``double_q`` lets online head 1 + k pick the next action that head k values, and
+        ``ema_tau`` > 0 is refused (EMA_REFUSED): the target is head 0 of the online parameters."""
+        options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
-        check_dueling(dueling, architecture_type, features, batch_norm)
-        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
-        check_munchausen(double_q, munchausen_tau)
-        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
-        check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
+        options.check(architecture_type, features, batch_norm)
         self.n_bellman_iterations = n_bellman_iterations
         self.last_idx_mlp = len(features) if architecture_type == "fc" else len(features) - 3
         self.network = DQNNet([int(f) for f in features], architecture_type, (1 + n_bellman_iterations) * (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1),
@@ -116,9 +81,8 @@ class iSDQN(EngineAgent):
         self.use_graph = bool(use_graph)
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
-                                learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, huber_delta, batch_norm,
-                                n_bins, min_value, max_value, sigma, double_q, munchausen_tau, munchausen_alpha, munchausen_clip, n_quantiles, categorical, dueling,
-                                max_grad_norm, noisy, noisy_sigma0, augment_pad)
+                                learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options,
+                                batch_norm=batch_norm, augment_pad=augment_pad)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 

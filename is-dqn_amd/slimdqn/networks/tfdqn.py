@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from slimdqn._engine import check_categorical, check_dueling, check_grad_clip, check_quantiles
+from slimdqn._engine import NetOptions
 from slimdqn.networks._agent import EngineAgent, check_ema_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
@@ -57,55 +57,23 @@ class TFDQN(EngineAgent):
         augment_pad: int = 0,
         ema_tau: float = 0.0,
     ):
-        """``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.
-        ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
-        every gradient step trains on its sampled batch with each state stack and each next-state stack shifted by a draw of its own in
-        [-pad, pad]^2, borders replicated, on the device (eager and captured alike; the device counter ``aug_count`` selects the
-        draws).  Acting and ``recycle_dormant`` see the frames as stored.  Every torso but 'fc' (ValueError); needs the device replay.
-        0 is off.
-        ``noisy``: NoisyNet exploration (Fortunato et al. 2018; include/isdqn_hip.h, isdqn_noisy_layout) -- every Dense layer, the head
-        included, carries factorised Gaussian noise with a learned scale sigma (initialised to ``noisy_sigma0`` / sqrt(fan-in)); every acting
-        call on the agent's own parameters draws first (one draw serves all rows of a batched call), every learn step draws first, and
-        ``noisy_eval`` = True (or the ``noisy_evaluation()`` context) acts with the mean network.  ``get_model()`` then carries
-        "sigma_kernel" / "sigma_bias" beside the Dense leaves.  The epsilon schedule is the caller's: set it to 0 to explore by noise alone.
-        Not with batch_norm, the impala torso or ``max_grad_norm`` > 0 (ValueError).
-        ``max_grad_norm`` > 0 (``inf`` allowed): clip the gradient by its global norm in front of Adam, as
-        optax.clip_by_global_norm chained with optax.adam does (include/isdqn_hip.h, isdqn_net_config::max_grad_norm); the norm stays on
-        the device and ``update_target_params`` adds ``grad_norm`` (the mean over the interval's gradient steps) and
-        ``grad_clipped_fraction`` to its logs.  ``inf`` measures and never clips; 0 is off.  Negative or NaN, batch_norm or the impala
-        torso: ValueError.
-        ``dueling``: dueling value / advantage heads (Wang et al. 2016; include/isdqn_hip.h, isdqn_net_config::dueling) -- the last
-        Dense holds a value row and ``n_actions`` advantage rows per head (per bin / quantile with those heads), read from the two
-        halves of the last hidden layer and combined on the device; every loss, target and acting rule then runs on the combined
-        values.  Needs a hidden Dense layer of even width; not with batch_norm or the impala torso (ValueError).
-        ``categorical``: with ``n_bins`` > 0, train the histogram heads on the C51 categorical projection loss (include/isdqn_hip.h,
-        isdqn_net_config::categorical) instead of HL-Gauss: same heads, same acting, ``sigma`` ignored.  Not without ``n_bins``, nor with
-        ``n_quantiles`` > 0 or Munchausen targets (ValueError).
-        ``n_quantiles`` > 0: QR-DQN heads -- each action of each head predicts ``n_quantiles`` quantile values and trains on the
-        quantile-regression loss with kappa = ``huber_delta`` (include/isdqn_hip.h, isdqn_net_config::n_quantiles); acting uses
-        their means.  Not with ``n_bins`` > 0, Munchausen targets or batch_norm (ValueError).
-        ``huber_delta``: 0 keeps the reference's squared TD error; > 0 trains on the Huber loss (with quantile heads: kappa).
-        ``munchausen_tau`` > 0: Munchausen targets (include/isdqn_hip.h, isdqn_net_config::munchausen_tau) -- unlike ``double_q``
-        well defined here: the single head is regularised by its own stop-gradient policy.
-        ``n_bins`` > 0: HL-Gauss histogram loss over [min_value, max_value] with std ``sigma`` (include/isdqn_hip.h).
-        ``double_q`` is refused: see DOUBLE_Q_REFUSED."""
+        """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
+        EngineAgent._init_engine_agent.  Particular to target-free DQN:
+        ``double_q`` is refused: see DOUBLE_Q_REFUSED.
+        ``munchausen_tau`` > 0 is, unlike ``double_q``, well defined here: the single head is regularised by its own stop-gradient policy.
+        ``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
+        options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
-        check_dueling(dueling, architecture_type, features, batch_norm)
-        check_grad_clip(max_grad_norm, architecture_type, batch_norm)
-        check_categorical(categorical, n_bins, n_quantiles, munchausen_tau)
-        check_quantiles(n_quantiles, n_bins, munchausen_tau, batch_norm)
+        options.check(architecture_type, features, batch_norm)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, batch_norm)
         self.data_to_update = data_to_update
         self.target_update_frequency = target_update_frequency
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
-                                gamma, update_horizon, adam_eps, batch_size, precision, device, batch_norm=batch_norm,
-                                n_bins=n_bins, min_value=min_value, max_value=max_value, sigma=sigma, munchausen_tau=munchausen_tau,
-                                munchausen_alpha=munchausen_alpha, munchausen_clip=munchausen_clip, n_quantiles=n_quantiles,
-                                huber_delta=huber_delta, categorical=categorical, dueling=dueling, max_grad_norm=max_grad_norm,
-                                noisy=noisy, noisy_sigma0=noisy_sigma0, augment_pad=augment_pad)
+                                gamma, update_horizon, adam_eps, batch_size, precision, device, options, batch_norm=batch_norm,
+                                augment_pad=augment_pad)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54
