@@ -326,14 +326,15 @@ static int bn_forward(const Plan& P, bool x3, const float* params, const NetInpu
 // `sel`: the heads a gradient-only pass regresses (analysisdqn.py:162-183).  `target_params` (gradient-only passes: compute_loss_tb,
 // analysisdqn.py:165-173): the next states go through them in a forward of their own B rows -- on THEIR batch statistics -- and the
 // states through `params` on the statistics of the B state rows; the backward then runs over those B rows only.
-static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* params, float* adam_m, float* adam_v, int32_t* adam_count,
-                            const isdqn_batch* batch, float* losses, float* loss_accum, float* q_values, float* targets, double* priorities,
-                            float* ws, hipStream_t st, bool learn, float* grad_out, bool update, const float* target_params, const HeadSel* sel) {
-    const bool x3 = cfg->precision == ISDQN_PRECISION_BF16X3;
-    const int B = P.B, N2 = P.N2, K = sel ? sel->K : P.K;
-    const int on0 = sel ? sel->on0 : P.oh, tg0 = sel ? sel->tg0 : 0;
-    if (sel) ISDQN_REQUIRE(sel->K >= 1 && on0 >= 0 && tg0 >= 0 && on0 + K <= P.n_heads && tg0 + K <= P.n_heads && K <= P.K, ISDQN_ERR_ARG,
-                           "head selection outside the network's heads");
+// (`call`: as learn_or_loss hands it on -- heads resolved, q_values / targets at their destination)
+static int bn_learn_or_loss(const Plan& P, const LearnCall& call) {
+    const isdqn_net_config* cfg = call.cfg;
+    const isdqn_batch* batch = call.batch;
+    const float* target_params = call.target_params;
+    float *params = call.params, *ws = call.ws;
+    hipStream_t st = call.st;
+    const bool x3 = cfg->precision == ISDQN_PRECISION_BF16X3, learn = call.learn();
+    const int B = P.B, N2 = P.N2;
     int rc;
     NetInput in{batch->frames, batch->frame_stride, batch->frame_ids, B, batch->state, batch->next_state, B};
     if (target_params != nullptr) {
@@ -362,11 +363,8 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
     if (rc) return rc;
 
     // ---- targets, loss, dL/dq (rows [0, B); the next-state rows of dL/dq are zero: stop_gradient, isdqn.py:99) ----
-    float* qv = q_values ? q_values : ws + P.qv_off;
-    float* tg = targets ? targets : ws + P.tg_off;
     // (BatchNorm networks never have histogram heads: the TD loss, and nlog_p == nha_p)
-    rc = loss_and_finalize(P, cfg, ws, batch, K, on0, tg0, learn, (learn && update) ? adam_count : nullptr, qv, tg, priorities, losses, loss_accum, st,
-                           /*double_q=*/cfg->double_q != 0 && target_params == nullptr && on0 != tg0);  // (with target_params: refused by the caller)
+    rc = loss_and_finalize(P, call, /*double_q=*/cfg->double_q != 0 && target_params == nullptr && call.sel.on0 != call.sel.tg0);  // (with target_params: refused by the caller)
     if (rc) return rc;
     if (batch->priorities_ready != nullptr) ISDQN_HIP_CHECK(hipEventRecord((hipEvent_t)batch->priorities_ready, st));
     if (!learn) return ISDQN_OK;
@@ -400,7 +398,7 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
             dz_cur = ws + l.dz_off;
             dz_ld = l.out_p;
             if (l.kind == 2) {  // the impala torso: its own backward and optimizer launches over the 2B rows
-                rc = impala_backward(P, cfg, x3, params, adam_m, adam_v, wmir, ws, Bb, grad_out, update, st, true);
+                rc = impala_backward(P, call, Bb, true);
                 if (rc) return rc;
                 continue;
             }
@@ -429,9 +427,9 @@ static int bn_learn_or_loss(const isdqn_net_config* cfg, const Plan& P, float* p
             adam.add(below->bias_off, below->G_p, ws + below->s1_off, 1, 0);
         }
     }
-    rc = adam.launch(st, P, cfg, params, adam_m, adam_v, ws, grad_out, update);
+    rc = adam_launch(adam, st, P, call);
     if (rc) return rc;
-    if (update)  // params["batch_stats"] = batch_stats (isdqn.py:87-88): the running averages the forward's flax modules produced
+    if (call.update())  // params["batch_stats"] = batch_stats (isdqn.py:87-88): the running averages the forward's flax modules produced
         for (int s = 0; s < P.n_bn; ++s) {
             const BnSite& b = P.bns[s];
             hipLaunchKernelGGL(bn_running_kernel, dim3(ceil_div(b.G, 256)), dim3(256), 0, st, params + b.mean_off, params + b.var_off,

@@ -371,8 +371,12 @@ static int impala_forward(const Plan& P, bool x3, const float* params, const flo
 // Stack_2); every inner tensor's gradient goes straight into its own optimizer launch (slab sums inside adam_kernel)
 // (`bn`: BatchNorm networks -- B is then the 2B rows of concat(state, next_state), and the first Stack's convolution gets a data
 // gradient too: the input site has a scale and a bias)
-static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, float* params, float* adam_m, float* adam_v, const float* wmir,
-                           float* ws, int B, float* grad_out, bool update, hipStream_t st, bool bn = false) {
+static int impala_backward(const Plan& P, const LearnCall& call, int B, bool bn = false) {
+    const bool x3 = call.cfg->precision == ISDQN_PRECISION_BF16X3;
+    const float* params = call.params;
+    float* ws = call.ws;
+    const float* wmir = ws + P.wsplit_off;
+    hipStream_t st = call.st;
     const Layer& L0 = P.L[0];
     AdamList adam;
     const NetInput none{nullptr, 0, nullptr, 0, nullptr, nullptr, 0};
@@ -464,5 +468,5 @@ static int impala_backward(const Plan& P, const isdqn_net_config* cfg, bool x3, 
         }
     }
     // the optimizer over the torso's tensors (slab / partial sums inside the kernel)
-    return adam.launch(st, P, cfg, params, adam_m, adam_v, ws, grad_out, update);
+    return adam_launch(adam, st, P, call);
 }

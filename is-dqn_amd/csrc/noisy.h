@@ -1,6 +1,7 @@
 // NoisyNet exploration: factorised Gaussian noise on every Dense layer (Fortunato et al., "Noisy Networks for Exploration", ICLR 2018).
-// include/isdqn_hip.h, isdqn_noisy_layout holds THE definition.  Included by net_kernels.hip inside namespace isdqn, behind every kernel of
-// the learn step and in front of the noisy entry points: the code object keeps the order of the kernels it had (docs/NOTEBOOK.md).
+// include/isdqn_hip.h, isdqn_noisy_layout holds THE definition.  Included by net_kernels.hip inside namespace isdqn, behind the learn
+// step and in front of the noisy entry points: its kernels are the last but reset.h's in tests/golden/kernel_order.txt, and
+// tests/test_kernel_order_host.py holds every kernel of the code object to its place there (why: docs/NOTEBOOK.md).
 // Built beside the plan: no field of isdqn_net_config, no workspace region and nothing of build_plan belongs to it.  The caller owns
 // sigma, its moments, the noise vectors, the composed parameters `eff` and the reduced gradient; the existing forward / loss / gradient
 // code runs unchanged on `eff`.

@@ -175,7 +175,7 @@ extern "C" int isdqn_replay_deinterleave(const uint8_t* state, const uint8_t* ne
     return ISDQN_OK;
 }
 
-// The random-shift augmentation, behind every kernel this code object had: they keep their places in it.
+// The random-shift augmentation, last in this code object: tests/test_kernel_order_host.py holds every kernel to its place.
 namespace isdqn {
 #include "augment.h"
 }  // namespace isdqn
@@ -238,7 +238,7 @@ extern "C" int isdqn_replay_augment_shift(const uint8_t* frames, int64_t frame_s
 // Horizon windows (include/isdqn_hip.h, isdqn_replay_gather_horizon holds THE definition): an element row keeps the frame ids of its
 // whole window [stack + n_max], its n_max per-step rewards and how many of them lie inside the trajectory; the gather cuts the window
 // at a horizon m and sums the return at a discount that it reads from device memory, so a captured step changes both between replays.
-// Behind every kernel this code object had, as the augmentation: they keep their places in it.  Bounds sites 48 (gather), 49 (scatter).
+// Appended behind the augmentation, as tests/golden/kernel_order.txt has them (tests/test_kernel_order_host.py).  Bounds sites 48 (gather), 49 (scatter).
 namespace isdqn {
 
 constexpr int HORIZON_MAX = 128;

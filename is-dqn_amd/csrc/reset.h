@@ -1,7 +1,7 @@
 // Periodic resets (Nikishin et al. 2022, "The Primacy Bias in Deep RL"; shrink and perturb: Ash & Adams 2020; SR-SPR, BBF) and EMA
 // target networks (optax.incremental_update).  include/isdqn_hip.h, isdqn_net_reset / isdqn_net_ema hold THE definitions.  The reference
-// has no counterpart.  Included by net_kernels.hip inside namespace isdqn, behind every kernel the library had: the code object keeps the
-// order of its kernels.  Built beside the plan: no field of isdqn_net_config, no workspace region, nothing of build_plan.
+// has no counterpart.  Included by net_kernels.hip inside namespace isdqn, last of its headers: tests/test_kernel_order_host.py holds every
+// kernel of the code object to its place in tests/golden/kernel_order.txt, these at the end.  Built beside the plan: no field of isdqn_net_config, no workspace region, nothing of build_plan.
 //   reset_kernel       one launch over every tensor that is written, found through ResetTable (passed by value, as AdamTable): per
 //                      tensor a factor pair (s, q) by its class; s == 0: p <- q * f without reading p, else p <- s * p + q * f, the two
 //                      products and the sum rounded separately; both Adam moments <- +0.  A virtual block covers RESET_BLOCK_ELEMS
