@@ -563,6 +563,37 @@ typedef struct isdqn_batch_discount {
 #define ISDQN_BATCH_MIRROR_CURRENT 1
 /* The batch is the first member of the struct isdqn_batch_discount above. */
 #define ISDQN_BATCH_DISCOUNT 2
+/* The batch is the first member of the struct isdqn_batch_decay below (through its isdqn_batch_discount). */
+#define ISDQN_BATCH_WEIGHT_DECAY 4
+
+/* AdamW: decoupled weight decay in the learn step's optimizer (optax.adamw(..., weight_decay=wd, mask=kernels),
+ * torch.optim.AdamW).  THE definition, per parameter element of a tensor that decays: with p0 the element before the step, p1 what the
+ * step without decay leaves (Adam on the same gradient and moments), lr = cfg->learning_rate and wd = weight_decay,
+ *
+ *     p_new = fl32( p1 - fl32( lr * fl32( wd * p0 ) ) )
+ *
+ * three roundings, never a fused multiply-add.  Moments, step count, bias corrections, the reduced gradient, losses, q_values, targets
+ * and priorities are what they are without decay, bit for bit; the S8 weight mirror is written from p_new.  Up to rounding this is
+ * optax.adamw's -lr * (adam_direction + wd * p0) and torch's p *= 1 - lr * wd followed by Adam.  An element of a tensor that does not
+ * decay, and every element when weight_decay == 0, takes the instructions of a step without decay and gets its bits (the decay is not
+ * folded into the arithmetic: -0 - lr * (+0) and -0 - lr * (-0) differ).  Padding elements and a dueling head's structural zeros are +0
+ * and stay +0.
+ * decay_kinds: bit k set = tensors of isdqn_tensor_info::kind k decay.  ISDQN_DECAY_KINDS_KERNELS (conv and dense kernels) is the usual
+ * mask of the optax and torch recipes, ISDQN_DECAY_KINDS_ALL adds biases and the LayerNorm / BatchNorm scales and biases; the running
+ * statistics (kinds 7, 8) are never the optimizer's.
+ * As with the discounts, isdqn_batch keeps its size: a caller hands the entry points &x.base.batch and sets ISDQN_BATCH_WEIGHT_DECAY in
+ * x.base.batch.flags; base.discount is read only when ISDQN_BATCH_DISCOUNT is set as well.
+ * Honoured by isdqn_net_learn_on_batch, its _target form and its debug form, every torso, with and without max_grad_norm.  Ignored by
+ * the loss-only and gradient-only entry points, which update nothing.  ISDQN_ERR_ARG, nothing launched: weight_decay negative, NaN or
+ * infinite; a decay_kinds bit above 6; decay_kinds == 0 with weight_decay > 0.  isdqn_noisy_learn_on_batch answers
+ * ISDQN_ERR_UNSUPPORTED to weight_decay > 0 (its optimizer kernel does not know the tensors' kinds). */
+#define ISDQN_DECAY_KINDS_KERNELS 0x03
+#define ISDQN_DECAY_KINDS_ALL 0x7f
+typedef struct isdqn_batch_decay {
+    isdqn_batch_discount base; /* base.batch.flags carries ISDQN_BATCH_WEIGHT_DECAY */
+    float weight_decay;        /* finite, >= 0; 0 = every bit as without the flag */
+    int32_t decay_kinds;       /* bit k: tensors of kind k decay; bits 0..6 only, at least one */
+} isdqn_batch_decay;
 
 /* DQNNet.apply on `n_rows` observations (dqn.py:47-103) -> q [n_rows][n_heads*n_actions].
  * cnn: image j reads frame_ids[j*stack .. j*stack+stack-1]; fc: obs [n_rows][obs_c]. */

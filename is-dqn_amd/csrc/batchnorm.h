@@ -388,13 +388,13 @@ static int bn_learn_or_loss(const Plan& P, const LearnCall& call) {
             const BnSite* site = bn_site_of(P, i);
             rc = bn_site_backward(*site, params, ws, da, Bb, true, st);
             if (rc) return rc;
-            adam.add(site->scale_off, site->G_p, ws + site->s2_off, 1, 0);
-            adam.add(site->bias_off, site->G_p, ws + site->s1_off, 1, 0);
+            adam.add(site->scale_off, site->G_p, ws + site->s2_off, 1, 0, call.wd(5));
+            adam.add(site->bias_off, site->G_p, ws + site->s1_off, 1, 0, call.wd(6));
             const int rows = l.kind != 1 ? Bb * l.npix : Bb;
             int nb = 0;
             rc = ln_bwd(l, params, da, ws + l.z_off, rows, ws + l.dz_off, ws + l.part_off, &nb, st);
             if (rc) return rc;
-            add_ln_bias_entries(adam, l, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
+            add_ln_bias_entries(adam, call, l, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
             dz_cur = ws + l.dz_off;
             dz_ld = l.out_p;
             if (l.kind == 2) {  // the impala torso: its own backward and optimizer launches over the 2B rows
@@ -403,7 +403,7 @@ static int bn_learn_or_loss(const Plan& P, const LearnCall& call) {
                 continue;
             }
         } else {
-            adam.add(l.b_off, l.out_p, ws + P.dbh_off, 1, 0);
+            adam.add(l.b_off, l.out_p, ws + P.dbh_off, 1, 0, call.wd(2));
         }
         // data gradient w.r.t. this layer's input (the BatchNorm output below); the first convolution's feeds the input site
         if (i > 0 || (l.kind == 0 && below != nullptr)) {
@@ -419,12 +419,12 @@ static int bn_learn_or_loss(const Plan& P, const LearnCall& call) {
             rc = dense_wgrad(l, x3, in, act_in, dz_cur, dz_ld, ws + l.gw_off, Bb, st);
         }
         if (rc) return rc;
-        adam.add(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size);
+        adam.add(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size, call.wd(l.kind == 0 ? 0 : 1));
         if (i == 0 && below != nullptr) {  // scale / bias of the input site (dqn.py:52-53): sums only, nothing lies below it
             rc = bn_site_backward(*below, params, ws, da, Bb, false, st);
             if (rc) return rc;
-            adam.add(below->scale_off, below->G_p, ws + below->s2_off, 1, 0);
-            adam.add(below->bias_off, below->G_p, ws + below->s1_off, 1, 0);
+            adam.add(below->scale_off, below->G_p, ws + below->s2_off, 1, 0, call.wd(5));
+            adam.add(below->bias_off, below->G_p, ws + below->s1_off, 1, 0, call.wd(6));
         }
     }
     rc = adam_launch(adam, st, P, call);

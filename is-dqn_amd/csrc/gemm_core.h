@@ -542,6 +542,10 @@ __device__ __forceinline__ float adam_element(float& m, float& v, float p, float
     return p - lr * ((m * inv_c1) * __builtin_amdgcn_rcpf(den));
 #endif
 }
+// AdamW (include/isdqn_hip.h, isdqn_batch_decay: THE definition) on top of adam_element's result `p1` for an element that was `p0` before
+// the step: fl32(p1 - fl32(lr * fl32(wd * p0))), three roundings, never an FMA (the build has -ffp-contract=off).  Callers guard it with a
+// wave-uniform wd != 0 test and do not fold it into adam_element: without decay the instructions, and the sign of a zero, are plain Adam's
+__device__ __forceinline__ float adamw_decay(float p1, float p0, float lr, float wd) { return p1 - lr * (wd * p0); }
 __device__ __forceinline__ void load8_aligned(const float* p, float (&v)[8]) {
     ISDQN_BOUNDS_CHECK(p, 32, 1);
     const ISDQN_GLOBAL f32x4* gp = (const ISDQN_GLOBAL f32x4*)p;

@@ -139,7 +139,12 @@ __global__ __launch_bounds__(GC_FLAT_THREADS) void adam_flat_kernel(const AdamTa
     const float inv_c1 = 1.f / c1, inv_c2 = 1.f / c2;
     float* gp = &g.x; float* mp = &pm.x; float* vp = &pv.x; float* xp = &pp.x;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) xp[r] = adam_element(mp[r], vp[r], xp[r], gp[r] * sc, b1, b2, lr, eps, inv_c1, inv_c2);
+    for (int r = 0; r < 4; ++r) gp[r] = adam_element(mp[r], vp[r], xp[r], gp[r] * sc, b1, b2, lr, eps, inv_c1, inv_c2);  // (g: the new parameters)
+    if (en.wd != 0.f) {  // (wave-uniform: one tensor per workgroup)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gp[r] = adamw_decay(gp[r], xp[r], lr, en.wd);
+    }
+    pp = g;
     *reinterpret_cast<float4*>(m + o) = pm;
     *reinterpret_cast<float4*>(v + o) = pv;
     *reinterpret_cast<float4*>(p + o) = pp;

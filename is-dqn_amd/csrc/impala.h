@@ -383,7 +383,7 @@ static int impala_backward(const Plan& P, const LearnCall& call, int B, bool bn 
     auto wgrad = [&](const Layer& c, const float* x_s8, const float* dz_s8) -> int {
         int rc = x3 ? launch_conv_wgrad<3, false>(c, none, x_s8, dz_s8, ws + c.gw_off, B, st)
                     : launch_conv_wgrad<1, false>(c, none, x_s8, dz_s8, ws + c.gw_off, B, st);
-        adam.add(c.w_off, c.w_size, ws + c.gw_off, conv_wgrad_slabs(c, B), c.w_size);
+        adam.add(c.w_off, c.w_size, ws + c.gw_off, conv_wgrad_slabs(c, B), c.w_size, call.wd(0));
         return rc;
     };
     auto dgrad = [&](const Layer& c, const float* dz_s8, float* da) -> int {
@@ -395,7 +395,7 @@ static int impala_backward(const Plan& P, const LearnCall& call, int B, bool bn 
         const int nb = imp_blocks(rows);
         hipLaunchKernelGGL(imp_to_s8_kernel, dim3(nb), dim3(256), 0, st, d, mask, rows, Cp, out, part);
         ISDQN_HIP_CHECK(hipGetLastError());
-        adam.add(b_off, Cp, part, nb, Cp);
+        adam.add(b_off, Cp, part, nb, Cp, call.wd(2));
         return ISDQN_OK;
     };
 
@@ -432,8 +432,8 @@ static int impala_backward(const Plan& P, const LearnCall& call, int B, bool bn 
             if (bs) {  // through the block's BatchNorm: da becomes the gradient w.r.t. relu([LN](r)) in place
                 rc = bn_site_backward(*bs, params, ws, da, B, true, st);
                 if (rc) return rc;
-                adam.add(bs->scale_off, bs->G_p, ws + bs->s2_off, 1, 0);
-                adam.add(bs->bias_off, bs->G_p, ws + bs->s1_off, 1, 0);
+                adam.add(bs->scale_off, bs->G_p, ws + bs->s2_off, 1, 0, call.wd(5));
+                adam.add(bs->bias_off, bs->G_p, ws + bs->s1_off, 1, 0, call.wd(6));
             }
             const float* g = S.ln_g[b] >= 0 ? params + S.ln_g[b] : nullptr;
             const float* be = S.ln_b[b] >= 0 ? params + S.ln_b[b] : nullptr;
@@ -442,8 +442,8 @@ static int impala_backward(const Plan& P, const LearnCall& call, int B, bool bn 
                                ws + S.lnpart_off[b]);
             ISDQN_HIP_CHECK(hipGetLastError());
             if (g != nullptr) {
-                adam.add(S.ln_g[b], S.C_p, ws + S.lnpart_off[b], nb, 2 * (int64_t)S.C_p);
-                adam.add(S.ln_b[b], S.C_p, ws + S.lnpart_off[b] + S.C_p, nb, 2 * (int64_t)S.C_p);
+                adam.add(S.ln_g[b], S.C_p, ws + S.lnpart_off[b], nb, 2 * (int64_t)S.C_p, call.wd(3));
+                adam.add(S.ln_b[b], S.C_p, ws + S.lnpart_off[b] + S.C_p, nb, 2 * (int64_t)S.C_p, call.wd(4));
             }
         }
         const int cq = S.C_p / 4;
@@ -463,8 +463,8 @@ static int impala_backward(const Plan& P, const LearnCall& call, int B, bool bn 
         if (b0) {  // scale / bias of the input site (sums only)
             rc = bn_site_backward(*b0, params, ws, da, B, false, st);
             if (rc) return rc;
-            adam.add(b0->scale_off, b0->G_p, ws + b0->s2_off, 1, 0);
-            adam.add(b0->bias_off, b0->G_p, ws + b0->s1_off, 1, 0);
+            adam.add(b0->scale_off, b0->G_p, ws + b0->s2_off, 1, 0, call.wd(5));
+            adam.add(b0->bias_off, b0->G_p, ws + b0->s1_off, 1, 0, call.wd(6));
         }
     }
     // the optimizer over the torso's tensors (slab / partial sums inside the kernel)

@@ -230,7 +230,7 @@ static int dense_wgrad_fused_adam(const LearnCtx& c, const Layer& l, const float
     const MatSrc Bm{act_in, l.in_p, c.B, l.in_p, 1};
     AdamFuse af{c.params + l.w_off, c.adam_m + l.w_off, c.adam_v + l.w_off, c.ws + c.P.adam_tab_off,
                 c.cfg->learning_rate, c.cfg->adam_b1, c.cfg->adam_b2, c.cfg->adam_eps,
-                c.grad_out ? c.grad_out + l.w_off : nullptr, c.ws + c.P.wsplit_off + l.w_off, c.update() ? 1 : 0};
+                c.grad_out ? c.grad_out + l.w_off : nullptr, c.ws + c.P.wsplit_off + l.w_off, c.update() ? 1 : 0, c.wd(1)};
     // 64x64 tiles: the contraction is only B deep, the kernel lives off streaming p/m/v through the Adam
     // epilogue, and 128x128 tiles would leave 100 workgroups for 256 CUs
     // (operands: dz of a hidden layer -- or the fp32 dL/dq of the head -- and the S8 activations below it)
@@ -264,7 +264,7 @@ static int weight_gradient(const LearnCtx& c, const WgradJob& j, AdamList* adam)
         rc = dense_wgrad(l, c.x3, c.in, act_in, j.dz, j.dz_ld, ws + l.gw_off, c.B, j.stream);
         if (rc) return rc;
     }
-    adam[c.ss && j.stream == c.wst ? 1 : 0].add(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size);
+    adam[c.ss && j.stream == c.wst ? 1 : 0].add(l.w_off, l.w_size, ws + l.gw_off, w_slabs, l.w_size, c.wd(l.kind == 0 ? 0 : 1));
     return ISDQN_OK;
 }
 
@@ -472,20 +472,20 @@ static int learn_backward(const LearnCtx& c, BackwardSchedule& sched, AdamList* 
     for (int i = P.n_layers - 1; i >= 0; --i) {
         const Layer& l = P.L[i];
         if (l.is_head) {
-            adam[c.hc_S && c.ss ? 1 : 0].add(l.b_off, l.out_p, ws + (P.dueling ? P.dbh_raw_off : P.dbh_off), 1, 0);  // loss_finalize_kernel's stream
+            adam[c.hc_S && c.ss ? 1 : 0].add(l.b_off, l.out_p, ws + (P.dueling ? P.dbh_raw_off : P.dbh_off), 1, 0, c.wd(2));  // loss_finalize_kernel's stream
         } else {
             dz_cur = ws + l.dz_off;
             dz_ld = l.out_p;
             if (c.hc_S && i == P.n_layers - 2) {  // dz and the partial sums came from the head chain
-                add_ln_bias_entries(adam[0], l, ws + l.part_off, c.hc_wg, 3 * (int64_t)l.out_p);
+                add_ln_bias_entries(adam[0], c, l, ws + l.part_off, c.hc_wg, 3 * (int64_t)l.out_p);
             } else if (dz_fused) {  // (reduce_rows_kernel, in front of Adam)
-                add_ln_bias_entries(adam[0], l, ws + l.red_off, 1, 0);
+                add_ln_bias_entries(adam[0], c, l, ws + l.red_off, 1, 0);
             } else {
                 // da (w.r.t. this layer's activation) was left in ws+da_off by layer i+1's data-gradient
                 int nb = 0;
                 rc = ln_bwd(l, c.params, ws + P.da_off, ws + l.z_off, l.kind != 1 ? B * l.npix : B, ws + l.dz_off, ws + l.part_off, &nb, c.st);
                 if (rc) return rc;
-                add_ln_bias_entries(adam[0], l, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
+                add_ln_bias_entries(adam[0], c, l, ws + l.part_off, nb, 3 * (int64_t)l.out_p);
             }
         }
         if (l.kind == 2) {  // the impala torso: its own backward (generic engine + row-wise kernels) and optimizer launches, on the caller's stream
@@ -540,7 +540,7 @@ static int clipped_adam(const LearnCtx& c, const AdamList* adam) {
     for (int k = 0; k < 2; ++k)
         for (const AdamEntry& t : adam[k].e) {
             (t.n_slabs > 1 ? multi : single).e.push_back(t);
-            all.add(t.p_off, t.size, t.g, 1, 0);
+            all.add(t.p_off, t.size, t.g, 1, 0, t.wd);
         }
     ISDQN_REQUIRE(all.e.size() <= (size_t)ADAM_MAX_ENTRIES, ISDQN_ERR_UNSUPPORTED, "gradient clipping: more tensors than one optimizer table holds");
     const AdamTable tab_m = multi.table(0), tab_s = single.table(0, GC_FLAT_ELEMS), tab_a = all.table(0, GC_FLAT_ELEMS);
@@ -619,6 +619,7 @@ static int learn_or_loss(LearnCall call) {
     if (!Pp) return rc;
     const Plan& P = *Pp;
     ISDQN_REQUIRE(call.params && batch && call.losses && call.ws, ISDQN_ERR_ARG, "null pointer");
+    if ((rc = check_decay(call.weight_decay, call.decay_kinds))) return rc;
     ISDQN_REQUIRE(batch->B == P.B, ISDQN_ERR_SHAPE, "batch->B != cfg->batch_size");
     ISDQN_REQUIRE(batch->action && batch->reward && batch->terminal, ISDQN_ERR_ARG, "null batch field");
     rc = check_input(cfg, batch->frames, batch->frame_stride, batch->frame_ids, batch->state);

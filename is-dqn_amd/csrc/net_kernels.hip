@@ -177,6 +177,8 @@ static LearnCall learn_call(const isdqn_net_config* cfg, LearnMode mode, const f
     LearnCall c;
     c.cfg = cfg; c.mode = mode; c.params = const_cast<float*>(params); c.batch = batch;
     c.losses = losses; c.q_values = q_values; c.targets = targets; c.ws = (float*)workspace; c.st = (hipStream_t)stream;
+    // (the loss-only and the gradient-only calls update nothing: a decay behind their batch is not read)
+    if (mode == LearnMode::Learn) batch_decay(batch, &c.weight_decay, &c.decay_kinds);
     return c;
 }
 
@@ -592,6 +594,13 @@ extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu
     const Plan& P = *Pp;
     ISDQN_REQUIRE(mu && sigma && m_mu && v_mu && m_sigma && v_sigma && adam_count && noise && eff && grad && batch && workspace, ISDQN_ERR_ARG,
                   "null pointer");
+    {  // AdamW: noisy_adam_kernel walks the flat buffer and does not know the conv tensors' kinds
+        float weight_decay;
+        int32_t decay_kinds;
+        batch_decay(batch, &weight_decay, &decay_kinds);
+        if ((rc = check_decay(weight_decay, decay_kinds))) return rc;
+        ISDQN_REQUIRE(weight_decay == 0.f, ISDQN_ERR_UNSUPPORTED, "weight decay under NoisyNet exploration is not built");
+    }
     NoisyTable tab;
     noisy_tables(P, &tab, nullptr);
     float* ws = (float*)workspace;

@@ -576,6 +576,9 @@ struct LearnCall {
     float* ws = nullptr;
     hipStream_t st = nullptr;  // the caller's stream
     HeadSel sel;
+    float weight_decay = 0.f;  // AdamW (isdqn_batch_decay, read by learn_call for the calls that update; 0: plain Adam)
+    int32_t decay_kinds = 0;   // bit k: tensors of isdqn_tensor_info::kind k decay
+    float wd(int kind) const { return ((decay_kinds >> kind) & 1) ? weight_decay : 0.f; }  // what an optimizer entry of that kind carries
     bool learn() const { return mode != LearnMode::Loss; }  // a backward pass follows the loss
     bool update() const { return mode == LearnMode::Learn; }
 };
@@ -599,8 +602,8 @@ static void moments_of_a_gradient_only_pass(LearnCall& call) { call.adam_m = cal
 struct AdamList {
     std::vector<AdamEntry> e;
     AdamList() { e.reserve(ADAM_MAX_ENTRIES); }
-    void add(int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride) {
-        e.push_back(AdamEntry{p_off, size, stride, g, n_slabs, 0});
+    void add(int64_t p_off, int64_t size, const float* g, int n_slabs, int64_t stride, float wd) {
+        e.push_back(AdamEntry{p_off, size, stride, g, n_slabs, 0, wd});
     }
     // entries [e0, e0 + ADAM_MAX_ENTRIES) as one launch's table; `per_block`: elements a workgroup of the launch covers
     AdamTable table(size_t e0, int per_block = 64) const {
@@ -652,6 +655,19 @@ static int loss_finalize(const Plan& P, const isdqn_net_config* cfg, float* ws, 
 // The per-transition discounts behind a batch that says it has them (include/isdqn_hip.h, isdqn_batch_discount), else null.
 static inline const float* batch_discount(const isdqn_batch* batch) {
     return (batch->flags & ISDQN_BATCH_DISCOUNT) ? reinterpret_cast<const isdqn_batch_discount*>(batch)->discount : nullptr;
+}
+// The weight decay behind a batch that says it has one (include/isdqn_hip.h, isdqn_batch_decay), else none; unchecked (check_decay).
+static inline void batch_decay(const isdqn_batch* batch, float* weight_decay, int32_t* decay_kinds) {
+    const bool has = batch != nullptr && (batch->flags & ISDQN_BATCH_WEIGHT_DECAY);
+    const isdqn_batch_decay* d = reinterpret_cast<const isdqn_batch_decay*>(batch);
+    *weight_decay = has ? d->weight_decay : 0.f;
+    *decay_kinds = has ? d->decay_kinds : 0;
+}
+static int check_decay(float weight_decay, int32_t decay_kinds) {
+    ISDQN_REQUIRE(weight_decay >= 0.f && weight_decay <= 3.4028234e38f, ISDQN_ERR_ARG, "weight_decay must be finite and >= 0");  // (NaN fails both)
+    ISDQN_REQUIRE((decay_kinds & ~ISDQN_DECAY_KINDS_ALL) == 0, ISDQN_ERR_ARG, "decay_kinds: bits 0..6 only (kinds 7 and 8 are running statistics)");
+    ISDQN_REQUIRE(weight_decay == 0.f || decay_kinds != 0, ISDQN_ERR_ARG, "weight_decay > 0 needs at least one kind in decay_kinds");
+    return ISDQN_OK;
 }
 
 // `c`: the call with its heads resolved and q_values / targets pointing at their destination; the step count advances in a pass with
@@ -714,12 +730,12 @@ static int loss_and_finalize(const Plan& P, const LearnCall& c, bool double_q = 
 }
 
 // LayerNorm scale / bias and layer bias of `l` from `n_rows` partial rows of (dgamma, dbeta, dbias) at `part`
-static void add_ln_bias_entries(AdamList& adam, const Layer& l, const float* part, int n_rows, int64_t stride) {
+static void add_ln_bias_entries(AdamList& adam, const LearnCall& c, const Layer& l, const float* part, int n_rows, int64_t stride) {
     if (l.has_ln) {
-        adam.add(l.g_off, l.out_p, part, n_rows, stride);
-        adam.add(l.be_off, l.out_p, part + l.out_p, n_rows, stride);
+        adam.add(l.g_off, l.out_p, part, n_rows, stride, c.wd(3));
+        adam.add(l.be_off, l.out_p, part + l.out_p, n_rows, stride, c.wd(4));
     }
-    if (l.b_off >= 0) adam.add(l.b_off, l.out_p, part + 2 * l.out_p, n_rows, stride);  // (the impala torso has no bias of its own)
+    if (l.b_off >= 0) adam.add(l.b_off, l.out_p, part + 2 * l.out_p, n_rows, stride, c.wd(2));  // (the impala torso has no bias of its own)
 }
 
 // generic data gradient of conv layer `l`: da [rows][hin][win][cin_p] fp32

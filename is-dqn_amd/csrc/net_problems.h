@@ -85,6 +85,7 @@ struct AdamFuse {
     float* grad_out;         // optional: also store the raw gradient (tests)
     float* mirror;           // S8 mirror of p (same layout): the updated parameters are written in both forms
     int update;              // 0: gradient only (grad_out), p / m / v / mirror untouched
+    float wd = 0.f;          // decoupled weight decay of the tensor (include/isdqn_hip.h, isdqn_batch_decay); 0: none
 };
 
 // S8M: bit 0 / bit 1 = operand A / B is stored S8 (gemm_core.h): staged by copy; such an operand is always chunk-aligned.
@@ -213,6 +214,14 @@ struct PlainGemm {
                     np[r] = adam_element(mm, vv, pp[it][r], gp[r], adam.b1, adam.b2, adam.lr, adam.eps, inv_c1, inv_c2);
                     nm[r] = mm;
                     nv[r] = vv;
+                }
+                // AdamW (gemm_core.h adamw_decay): three roundings on top of Adam's result, pp[it] is the element before
+                // the step.  A kernel argument: the test is wave-uniform, and without decay the instructions above are all.  (One test per
+                // float4, behind its Adam: 97 + 16 registers, still four waves per SIMD; the rounds in two copies, one per answer of a
+                // single test, took 115 + 16 and lost a wave)
+                if (adam.wd != 0.f) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) np[r] = adamw_decay(np[r], pp[it][r], adam.lr, adam.wd);
                 }
                 if (on[it] && adam.grad_out) *reinterpret_cast<float4*>(adam.grad_out + off[it]) = g;
                 if (on[it] && adam.update) {

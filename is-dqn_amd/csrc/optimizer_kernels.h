@@ -57,6 +57,7 @@ struct AdamEntry {
     int64_t p_off, size, slab_stride;
     const float* g;
     int n_slabs, block_start;
+    float wd;  // decoupled weight decay of the tensor (include/isdqn_hip.h, isdqn_batch_decay); 0: none
 };
 constexpr int ADAM_MAX_ENTRIES = 4 * MAX_LAYERS;
 struct AdamTable {
@@ -137,7 +138,12 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab, float* _
     float* gp = &g.x; float* mp = &pm.x; float* vp = &pv.x; float* xp = &pp.x;
     const float inv_c1 = 1.f / c1, inv_c2 = 1.f / c2;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) xp[r] = adam_element(mp[r], vp[r], xp[r], gp[r], b1, b2, lr, eps, inv_c1, inv_c2);
+    for (int r = 0; r < 4; ++r) gp[r] = adam_element(mp[r], vp[r], xp[r], gp[r], b1, b2, lr, eps, inv_c1, inv_c2);  // (g: the new parameters)
+    if (en.wd != 0.f) {  // (wave-uniform: one tensor per workgroup)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gp[r] = adamw_decay(gp[r], xp[r], lr, en.wd);
+    }
+    pp = g;
     *reinterpret_cast<float4*>(m + o) = pm;
     *reinterpret_cast<float4*>(v + o) = pv;
     *reinterpret_cast<float4*>(p + o) = pp;

@@ -70,6 +70,8 @@ _ENGINE = [
     ("-resets", "--reset_shrink", dict(type=float, default=0.5, help="Shrink factor in [0, 1] of the layers below the reset ones: p <- s * p + (1 - s) * fresh (BBF: 0.5; 1 keeps them). Means nothing without -reset.")),
     ("-resetl", "--reset_top_layers", dict(type=int, default=0, help="Number of top layers that are re-initialised fully; 0 = every Dense layer (BBF, SR-SPR). Means nothing without -reset.")),
     ("-ema", "--ema_tau", dict(type=float, default=0.0, help="EMA (Polyak) target network: target <- (1 - tau) * target + tau * online after every gradient step, on the device, instead of a copy every -tuf steps (BBF, SR-SPR: 0.005); 0 = off, in [0, 1]. DQN only: iS-DQN's target is a head of the online network, the target-free agents have none.")),
+    ("-wd", "--weight_decay", dict(type=float, default=0.0, help="AdamW (optax.adamw; BBF, SR-SPR: 0.1): decoupled weight decay -- every learn step also takes learning_rate * weight_decay of its value off every element of the conv and dense kernels, on the device, in every Adam kernel. 0 = off (plain Adam, the bits of a run without the flag); finite and >= 0. With every agent, torso, loss and -gc; not with -noisy.")),
+    ("-wdall", "--weight_decay_all", dict(default=False, action="store_true", help="-wd also decays the biases and the LayerNorm / BatchNorm scales and biases (never the running statistics). Means nothing without -wd.")),
     ("-anneal", "--anneal_period", dict(type=int, default=0, help="Anneal the update horizon and the discount (SR-SPR, BBF: -anneal 10000 -n 10 -nend 3 -gamma 0.97 -gammaend 0.997): over this many gradient steps, counted again from every -reset, n goes exponentially from -n to -nend and 1 - gamma from 1 - (-gamma) to 1 - (-gammaend); the replay keeps whole windows of max(-n, -nend) steps and every batch is cut at the step's horizon on the device. 0 = off. With every agent, torso, loss and target flag.")),
     ("-nend", "--update_horizon_end", dict(type=int, default=None, help="Final update horizon of -anneal (default: -n). Refused without -anneal.")),
     ("-gammaend", "--gamma_end", dict(type=float, default=None, help="Final discount of -anneal, in [0, 1) (default: -gamma). Refused without -anneal.")),
@@ -293,6 +295,22 @@ def check_ema(p: dict, algo_name: str) -> None:
 def ema_kwargs(p) -> dict:
     """The agents' EMA keyword from parsed parameters; without -ema the keywords are the ones they were before the flag existed."""
     return dict(ema_tau=float(p["ema_tau"])) if p.get("ema_tau") else {}
+
+
+# (-wd and -wdall stay out of parameters.json like -reset)
+def check_weight_decay(p: dict) -> None:
+    """-wd negative, NaN or infinite, or > 0 with -noisy, fails before anything is written, with the agents' own message."""
+    from slimdqn import _optimizer
+
+    _optimizer.check_weight_decay(p.get("weight_decay", 0.0), noisy=bool(p.get("noisy_nets", False)))
+
+
+def weight_decay_kwargs(p) -> dict:
+    """The agents' weight-decay keywords from parsed parameters; without -wd (-wdall alone means nothing) the keywords are the ones they
+    were before the flag existed."""
+    if not p.get("weight_decay"):
+        return {}
+    return dict(weight_decay=float(p["weight_decay"]), weight_decay_all=bool(p.get("weight_decay_all", False)))
 
 
 # (-anneal, -nend and -gammaend stay out of parameters.json like -reset)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
+from slimdqn import _optimizer
 
 
 def _round_up(a, b):
@@ -707,6 +708,24 @@ class QNetEngine:
         self.max_grad_norm = c
         self.options = dataclasses.replace(self.options, max_grad_norm=c)
 
+    weight_decay = 0.0  # AdamW's decoupled weight decay of the following learn steps (set_weight_decay); 0: plain Adam
+    decay_kinds = 0     # bit k: tensors of TensorInfo.kind k decay
+    _captured = None    # weak set of the captured updates whose batches this engine made (slimdqn/_graph.py)
+
+    def set_weight_decay(self, weight_decay: float, all_kinds: bool = False) -> None:
+        """AdamW (Loshchilov & Hutter 2019; optax.adamw, torch.optim.AdamW) for the following learn steps of this engine: every element
+        of a decaying tensor also loses ``learning_rate * weight_decay`` times its value before the step (include/isdqn_hip.h,
+        isdqn_batch_decay: the definition, three float32 roundings).  The conv and dense kernels decay -- the usual mask --, with
+        ``all_kinds`` the biases and the LayerNorm / BatchNorm scales and biases too; running statistics never.  0 is off: the batches
+        and the bits of an engine that never heard of it.  The decay travels in every batch ``make_batch`` builds from here on; a step
+        that is already captured was captured with the old one, so every captured update of this engine is dropped (it captures again
+        at its next run).  Loss-only and gradient-only calls ignore it; noisy engines refuse it (ValueError)."""
+        wd = _optimizer.check_weight_decay(weight_decay, noisy=self.noisy)
+        self.weight_decay = wd
+        self.decay_kinds = _optimizer.decay_kinds(all_kinds) if wd > 0.0 else 0
+        for g in list(self._captured or ()):
+            g.destroy()
+
     # ------------------------------------------------------------------ C-ABI calls
     def make_batch(self, *, frames=None, frame_stride=0, frame_ids=None, state=None, next_state=None, action=None, reward=None, terminal=None,
                    mirror_current: bool = False, priorities_ready: torch.cuda.Event | None = None, loss_weights=None, discount=None) -> _hip.Batch:
@@ -723,6 +742,10 @@ class QNetEngine:
             assert discount.dtype == torch.float32 and discount.numel() == self.batch_size and discount.is_contiguous()
         b = _hip.Batch() if discount is None else _hip.BatchDiscount()  # (isdqn_batch_discount: the flag announces the pointer behind)
         b.flags = (_hip.BATCH_MIRROR_CURRENT if mirror_current else 0) | (0 if discount is None else _hip.BATCH_DISCOUNT)
+        if self.weight_decay > 0.0:  # (isdqn_batch_decay: the batch, its discount slot, then the decay; off: the structs above, as ever)
+            b, flags = _hip.BatchDecay(), b.flags
+            b.flags = flags | _hip.BATCH_WEIGHT_DECAY
+            b.weight_decay, b.decay_kinds = self.weight_decay, self.decay_kinds
         b.priorities_ready = None if priorities_ready is None else int(priorities_ready.cuda_event)
         b.B = self.batch_size
         b.frames = _hip.ptr(frames)

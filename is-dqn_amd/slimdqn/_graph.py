@@ -102,6 +102,11 @@ class GraphedUpdate:
         # keep ONE live executable each, destroy it before capturing a successor, and never re-instantiate in steady state.)
         self.graph = None
         self._capture()
+        if getattr(eng, "_captured", None) is None:  # (the engine drops its captured updates when an option that travels in the batches changes)
+            import weakref
+
+            eng._captured = weakref.WeakSet()
+        eng._captured.add(self)
 
     def destroy(self) -> None:
         """Release the executable graph (and the runtime's parallel streams it owns) after everything it enqueued has finished.
@@ -272,7 +277,8 @@ class GraphedUpdate:
         if self.horizon != (horizons is not None) or self.horizon != (gammas is not None):
             raise ValueError("a captured update at a horizon takes the horizons and the gammas of its S steps, another one neither")
         rb._flush()
-        if rb._frames.data_ptr() != self._frames_ptr:  # the frame store was re-allocated: pointers in the graph are stale
+        # the frame store was re-allocated: pointers in the graph are stale; or the engine dropped the graph (set_weight_decay)
+        if rb._frames.data_ptr() != self._frames_ptr or self.graph is None:
             self._frames_ptr = rb._frames.data_ptr()
             self.destroy()
             self._make_batches()

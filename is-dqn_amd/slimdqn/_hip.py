@@ -19,6 +19,8 @@ ERR_CAPACITY, ERR_NEGATIVE, ERR_SHAPE, ERR_EMPTY, ERR_RANGE, ERR_UNSUPPORTED, ER
 STATUS_NEGATIVE_VALUE, STATUS_TARGET_RANGE, STATUS_EMPTY_TREE = 1, 2, 4
 BATCH_MIRROR_CURRENT = 1  # include/isdqn_hip.h: ISDQN_BATCH_MIRROR_CURRENT
 BATCH_DISCOUNT = 2  # include/isdqn_hip.h: ISDQN_BATCH_DISCOUNT
+BATCH_WEIGHT_DECAY = 4  # include/isdqn_hip.h: ISDQN_BATCH_WEIGHT_DECAY
+DECAY_KINDS_KERNELS, DECAY_KINDS_ALL = 0x03, 0x7F  # include/isdqn_hip.h: ISDQN_DECAY_KINDS_* (bit k: TensorInfo.kind k decays)
 TREE_MAX_BATCH = 4096
 ARCH_CNN, ARCH_FC, ARCH_IMPALA = 0, 1, 2
 PRECISION_BF16X3, PRECISION_BF16 = 0, 1
@@ -101,6 +103,10 @@ class Batch(ctypes.Structure):
 
 class BatchDiscount(Batch):  # isdqn_batch_discount: the batch, then the discounts that flags & BATCH_DISCOUNT announces
     _fields_ = [("discount", c_void_p)]  # float32 [B] per-transition discounts in cfg.gamma_n's place (include/isdqn_hip.h)
+
+
+class BatchDecay(BatchDiscount):  # isdqn_batch_decay: the batch (and its discount slot), then what flags & BATCH_WEIGHT_DECAY announces
+    _fields_ = [("weight_decay", c_float), ("decay_kinds", c_int32)]  # AdamW's decay and the tensor kinds it acts on (include/isdqn_hip.h)
 
 
 _SIGNATURES = {

@@ -51,6 +51,9 @@ class DQN(EngineAgent):
         noisy_sigma0: float = 0.5,
         augment_pad: int = 0,
         ema_tau: float = 0.0,
+        *,
+        weight_decay: float = 0.0,
+        weight_decay_all: bool = False,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
@@ -62,7 +65,9 @@ class DQN(EngineAgent):
         step, a draw of its own (stream 1), as in Fortunato's DQN.
         ``double_q``: the online parameters pick the next action, the target parameters value it: one more forward per step.
         ``munchausen_tau`` > 0: the target parameters run over the states as well as the next states: about one more forward of B
-        images per step."""
+        images per step.
+        ``weight_decay`` / ``weight_decay_all``: AdamW (EngineAgent._init_engine_agent) on the online parameters; the target parameters
+        are never the optimizer's and never decay."""
         options = NetOptions.pick(locals())
         check_munchausen(double_q, munchausen_tau)  # (in front of the other rules, where this constructor has always asked it)
         options.check(architecture_type, features)
@@ -73,7 +78,7 @@ class DQN(EngineAgent):
         self.target_update_frequency = target_update_frequency
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
-                                gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad)
+                                gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all)
         self.target_params = self.params.copy()  # dqn.py:34
         self.target_sigma = self._engine.sigma.clone() if self.noisy else None  # (one persistent buffer, refreshed in place like the target)
         self.cumulated_loss = 0
