@@ -69,6 +69,7 @@ struct ConvImgParams {
     FastDiv d_chunk, d_Wp, d_R;  // fill index math: chunks per pixel (fp32) or per row (uint8), padded width, local rows
     PixelOrder order;        // fp32 layers: which output pixel a fragment column holds (strips when the image is one tile)
     long long* stamps;       // profiling only (isdqn_debug_set_stamps): [workgroup][8] s_memtime / s_memrealtime at phase boundaries
+    int Rd;                  // conv_fwd_u8_pair_kernel: local rows of the LDS image of two consecutive tiles (0: the layer does not take it)
 };
 
 template <int MT, int PASSES, bool U8>

@@ -1,36 +1,63 @@
-// First convolution (uint8 frames, architectures/dqn.py:51-58), two pixel tiles per workgroup with the second tile's frame rows
-// PREFETCHED INTO REGISTERS under the first tile's K loop and epilogue.
+// First convolution (uint8 frames, architectures/dqn.py:51-58): ONE workgroup of eight waves per image, the layer's weights resident
+// in LDS for the whole image, the image staged in "halves" of two 128-pixel tiles each.
 //
-// Why (profiles/round2/phase_stamps_c2.txt): conv_fwd_img_kernel<2, 2, true> runs 2048 workgroups of 9.5 us at four per
-// CU -- two rounds -- and HALF of a workgroup's life is its image fill: the frame-id row, then eight 8-byte pixel loads per thread,
-// two dependent round trips with nothing of its own to overlap them.  Here a workgroup owns tiles 2t and 2t + 1 of one image (the
-// frame ids and base pointers are shared), requests tile 2t + 1's pixels right behind tile 2t's first barrier and converts them into
-// the (then dead) LDS image after tile 2t's epilogue: one exposed fill per workgroup instead of two, one dispatch round instead
-// of two (1024 workgroups at the headline size = the chip's four per CU).
+// Why (profiles/round3/stamps_u8_pair.txt, profiles/round4/stamps_all.txt, NOTEBOOK 2026-10-20): the previous form -- four waves on a
+// pair of tiles, two workgroups per image -- walked the 32 KB of weights through a four-deep global -> register -> LDS ring once per
+// TILE (four times per image, one barrier per K step, 64 barriers per image), staged 36 input rows per tile (144 rows for the 84-row
+// image, each converted u8 -> bf16 again) and ran all four waves over the last tile's 16 pixels.  Here
+//   * the weights (32 rows x 256 k, hi + lo planes) are read from the S8 mirror once per workgroup, two 32-byte chunks per thread, and
+//     stay in LDS: the K rotation of a tile is only the LDS column its waves start from, and the K loop has no barrier;
+//   * waves 0-3 compute old tile 2h, waves 4-7 old tile 2h + 1 of half h on ONE LDS image of the rows both need (84 x 84: 56 rows for
+//     half 0, 40 for half 1: 96 rows per image);
+//   * the weights (they need no frame id: they travel under that round trip), the frame rows of half 0 and the frame rows of half 1
+//     are requested back to back at the start; half 1's rows wait in registers under half 0's K loop and epilogue (nothing in the
+//     K loop loads from global memory any more, so no wait is ordered behind them) and are converted into the (then dead) LDS image
+//     behind one barrier;
+//   * a wave whose 32 pixel slots all lie past the image skips K loop and epilogue (84 x 84, 21 x 21 pixels: waves 6-7 of half 1), and a
+//     wave none of whose 64 positions of a batch lies in the image of the half skips their conversion.
+// Three barriers per image.  512 threads at four waves per SIMD (128 registers, no scratch), 75 KB of LDS at 84 x 84: two workgroups
+// per CU, the 512 images of the headline step in one round.
+// Measured at the headline size (profiles/conv0_image/): 26.3 -> 21.2 us in the traced step, the untraced step +2 %.
 //
-// The arithmetic is conv_fwd_img_kernel's, statement for statement (same K-step rotation per (image, tile), same pass order, same
-// epilogue): the outputs are bit-identical (tests/test_gpu_network.py::test_first_layer_pair_kernel_is_bit_identical_to_the_one_tile_kernel).
-// uint8 layers of four stacked frames (K = 256: eight K steps) and at most 32 output channels (MT = 2) only; measured at the
-// headline size: 28.2 -> 26.2 us, the step +1 % (profiles/round3/ab_u8_pair.txt, phase stamps: stamps_u8_pair.txt).
+// The arithmetic is conv_fwd_img_kernel's, statement for statement (same pixel -> lane assignment inside the old tile, same K-step
+// rotation per (image, old tile), same pass order, same epilogue): the outputs are bit-identical
+// (tests/test_gpu_network.py::test_first_layer_pair_kernel_is_bit_identical_to_the_one_tile_kernel, tests/test_gpu_conv0_image_kernel.py).
+// uint8 layers of four stacked frames (K = 256: eight K steps), at most 32 output channels (MT = 2) and an even tile count only.
 #pragma once
 #include "conv_img.h"
 
 namespace isdqn {
 
-constexpr int U8P_PB = 2;  // positions per thread: one batch covers the whole tile image (R * Wp / 8 <= 2 * 256 positions)
+constexpr int U8P_PB = 2;         // positions per thread: one batch covers the image of a half (Rd * Wp / 8 <= 2 * 512 positions)
+constexpr int U8P_THREADS = 512;  // eight waves: two groups of four, one old tile each
+// Row pitch of the resident weights [32 rows][256 k]: 272 elements = 544 bytes, (pitch / 16) = 2 (mod 4) -- the rule at
+// ConvImgTraits::GA -- so the 16-lane groups of a fragment's ds_read_b128 hit 16 distinct bank quads (scripts/lds_conflicts.py:
+// 1.0; a pad of 8 elements, (pitch / 16) = 1 (mod 4), gives 2.0 on the third lane group).
+constexpr int U8P_WPITCH = 256 + 16;
+constexpr int U8P_WPLANE = 32 * U8P_WPITCH;
+
+// K rotation of conv_fwd_img_kernel's workgroup for (image j, old tile): blockIdx / 8 there is (j / 8) * tiles + tile for the images
+// of the full groups of eight (xcd_image_tile), the plain workgroup index / 8 in the tail group.
+__host__ __device__ __forceinline__ int u8p_rotation(int j, int tile, int n_img, int tiles_per_img, int nsteps) {
+    const int full = (n_img / 8) * 8;
+    const int old_wg8 = j < full ? (j >> 3) * tiles_per_img + tile : (j * tiles_per_img + tile) >> 3;
+    return (int)((unsigned)old_wg8 % (unsigned)nsteps);
+}
 
 template <int PASSES, int NSTEPS>
-__global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const ConvImgParams p) {
+__global__ __launch_bounds__(U8P_THREADS, 4) void conv_fwd_u8_pair_kernel(const ConvImgParams p) {
     ISDQN_EMPTY_KERNEL_RETURN
-    constexpr int MT = 2, NT = 2, MTW = MT, NTHR = GEMM_THREADS, STACK_MAX = 4;
-    using T = ConvImgTraits<MT, PASSES, true>;
-    using GA = typename T::GA;
+    constexpr int MT = 2, NT = 2, MTW = MT, NTHR = U8P_THREADS, STACK_MAX = 4;
+    constexpr int W_PLANES = PASSES >= 2 ? 2 : 1;
+    static_assert(NSTEPS * GEMM_BK == 256, "resident weights: [32][256 k]");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
-    __bf16* a_stage = smem;
-    __bf16* img = smem + 2 * T::A_STAGE;
+    __bf16* w_hi = smem;               // [32][U8P_WPITCH]
+    __bf16* w_lo = smem + U8P_WPLANE;  // (PASSES >= 2)
+    __bf16* img = smem + W_PLANES * U8P_WPLANE;
     const ConvGeom& g = p.g;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, grp = lane >> 4;
+    const int wave = (tid >> 6) & 3, hw = tid >> 8;  // wave inside its group of four / which tile of the half the group computes
 #if defined(ISDQN_DEV)
 #define U8P_STAMP(i)                                                                                 \
     if (p.stamps != nullptr && threadIdx.x == 0) {                                                  \
@@ -41,9 +68,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
 #define U8P_STAMP(i)
 #endif
     U8P_STAMP(0);
-    const int T2 = p.tiles_per_img >> 1;  // tile pairs per image
-    int j, tp;
-    xcd_image_tile((int)blockIdx.x, p.n_img, T2, j, tp);
+    const int j = (int)blockIdx.x;           // image
+    const int n_half = p.tiles_per_img >> 1;  // halves of two old tiles
 
     __shared__ __attribute__((aligned(16))) float s_par[3][64];
     float par_v = 0.f;
@@ -56,43 +82,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
     }
     constexpr int nsteps = NSTEPS;  // K / 32 = 2 * stacked frames, a compile-time constant: the K loop is straight-line code
     const int k_last = g.K - 8;
-    constexpr int A_PER = (GA::CHUNKS + NTHR - 1) / NTHR;
-    int a_row[A_PER], a_var[A_PER], a_lds[A_PER];
-    bool a_on[A_PER];
+    // The weights: chunk c = tid + i * 512 of the 32 x 32 chunks is row c / 32, k chunk c % 32 (a wave reads 2 KB of two rows and writes
+    // them to LDS 16 contiguous bytes per lane).  Requested first: they need no frame id, so they travel under that round trip.
+    float wv[2][8];
 #pragma unroll
-    for (int i = 0; i < A_PER; ++i) {
-        int c = tid + i * NTHR;
-        a_on[i] = c < GA::CHUNKS;
-        if (!a_on[i]) c = 0;
-        a_row[i] = stash_row(c);
-        a_var[i] = (c & 3) * 8;
-        a_lds[i] = a_row[i] * GA::PITCH + (c & 3) * 8;
-    }
-    constexpr int PF = 4;
-    float sa[PF][A_PER][8];
-    auto fetch = [&](int slot, int k) {
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) p.W.load(a_row[i], k + a_var[i], sa[slot][i]);
-    };
-    auto stash = [&](int slot, int stage) {
-        __bf16* a_hi = a_stage + stage * T::A_STAGE;
-        __bf16* a_lo = a_hi + GA::ELEMS;
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            if (GA::CHUNKS % NTHR != 0 && !a_on[i]) continue;
-            bf16x8 hi, lo;
-            if constexpr (PASSES >= 2) {
-                s8_unpack(sa[slot][i], hi, lo);
-                *reinterpret_cast<bf16x8*>(a_lo + a_lds[i]) = lo;
-            } else {
-                s8_unpack_hi(sa[slot][i], hi);
-            }
-            *reinterpret_cast<bf16x8*>(a_hi + a_lds[i]) = hi;
-        }
-    };
-    static_assert(NSTEPS >= PF + 2 && NSTEPS % 2 == 0, "ring of four slices + two staged ones");
+    for (int i = 0; i < 2; ++i) p.W.load((tid >> 5) + i * 16, (tid & 31) * 8, wv[i]);
 
-    // ---- frame rows of one tile: request (registers only) / convert into the LDS image ----
+    // ---- frame rows of one half: request (registers only) / convert into the LDS image ----
     const FrameSrc& fs = p.fs;
     const uint8_t* base[STACK_MAX];
 #pragma unroll
@@ -101,9 +97,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
         base[c] = id >= 0 ? fs.frames + (int64_t)id * fs.stride : nullptr;
     }
     const uint8_t* zeros = reinterpret_cast<const uint8_t*>(zero_chunk());
-    const int cpr = p.Wp / 8, per_plane = p.R * cpr, plane = p.R * p.Wp;
-    unsigned long long raw[U8P_PB][STACK_MAX];  // the only registers a request keeps alive (shift and LDS offset are recomputed)
-    auto request = [&](int row_base) {  // loads only: nothing here touches the loaded registers
+    const int cpr = p.Wp / 8, plane = p.Rd * p.Wp;
+    auto half_rows = [&](int h, int& row_base) {  // global input row of local row 0 of half h; returns the positions of one plane
+        const int oy_min = (int)g.d_wout.div((uint32_t)(h * 256));
+        const int oy_max = (int)g.d_wout.div((uint32_t)(min(g.npix, h * 256 + 256) - 1));
+        row_base = oy_min * g.stride - g.pad;
+        return ((oy_max - oy_min) * g.stride + g.ksz) * cpr;
+    };
+    typedef unsigned long long RawRows[U8P_PB][STACK_MAX];  // the only registers a request keeps alive (shift and LDS offset are recomputed)
+    auto request = [&](RawRows& raw, int h) {  // loads only: nothing here touches the loaded registers (a half past the image: zeros)
+        int row_base = 0;
+        const int per_plane = h < n_half ? half_rows(h, row_base) : 0;
 #pragma unroll
         for (int k = 0; k < U8P_PB; ++k) {
             const int pos = k * NTHR + tid;
@@ -118,10 +122,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
             for (int c = 0; c < STACK_MAX; ++c) raw[k][c] = load_u64_unaligned((ok && base[c] != nullptr) ? base[c] + off : zeros);
         }
     };
-    auto commit = [&]() {
+    auto commit = [&](const RawRows& raw, int h) {
+        int row_base;
+        const int per_plane = half_rows(h, row_base);
 #pragma unroll
         for (int k = 0; k < U8P_PB; ++k) {
             const int pos = k * NTHR + tid;
+            if (pos - lane >= per_plane) continue;  // (wave-uniform: none of this wave's 64 positions is in the image of the half)
             const bool on = pos < per_plane;
             uint32_t lr, cx;
             p.d_chunk.divmod((uint32_t)(on ? pos : 0), lr, cx);
@@ -139,36 +146,42 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
             }
         }
     };
-    auto tile_rows = [&](int tile) {  // global input row of local row 0 of this tile's image
-        const int oy_min = (int)g.d_wout.div((uint32_t)(tile * 128));
-        return oy_min * g.stride - g.pad;
-    };
+
+    // ---- everything this image needs from global memory, back to back: (the weights,) half 0's rows, half 1's rows ----
+    RawRows raw0, raw1;
+    request(raw0, 0);
+    request(raw1, 1);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {  // (the oldest loads: written to LDS while the rows travel)
+        const int at = ((tid >> 5) + i * 16) * U8P_WPITCH + (tid & 31) * 8;
+        bf16x8 hi, lo;
+        if constexpr (PASSES >= 2) {
+            s8_unpack(wv[i], hi, lo);
+            *reinterpret_cast<bf16x8*>(w_lo + at) = lo;
+        } else {
+            s8_unpack_hi(wv[i], hi);
+        }
+        *reinterpret_cast<bf16x8*>(w_hi + at) = hi;
+    }
+    if (tid < 192) s_par[tid >> 6][tid & 63] = par_v;
+    commit(raw0, 0);
 
     struct Frags {
         bf16x8 a_hi[MTW], a_lo[MTW], b_hi[NT];
     };
 
-    // The two tiles are two copies of straight-line code (compile-time `it`): a request under a run-time condition would end in a
-    // control-flow merge, where the compiler has to assume the larger number of loads in flight for every later wait.
-    auto do_tile = [&](auto it_c) {
-        constexpr int it = decltype(it_c)::value;
-        const int tile = 2 * tp + it;
+    // One half: this wave's 32 pixels of old tile 2h + hw.  No barrier inside: a wave without a live pixel leaves at once.
+    auto do_half = [&](int h) {
+        const int tile = 2 * h + hw;
         const int p0 = tile * 128;
-        const int row_base = tile_rows(tile);
-        // the K walk of conv_fwd_img_kernel's workgroup for (image j, tile): blockIdx / 8 there is (j / 8) * tiles + tile for the
-        // images of the full groups of eight (xcd_image_tile), the plain workgroup index / 8 in the tail group
-        const int full = (p.n_img / 8) * 8;
-        const int old_wg8 = j < full ? (j >> 3) * p.tiles_per_img + tile : (j * p.tiles_per_img + tile) >> 3;
-        const int rot = (int)((unsigned)old_wg8 % (unsigned)nsteps);
+        if (p0 + wave * 32 >= g.npix) return;  // (wave-uniform)
+        int row_base;
+        half_rows(h, row_base);
+        const int rot = u8p_rotation(j, tile, p.n_img, p.tiles_per_img, nsteps);
         auto slice = [&](int s) {  // (s < nsteps wherever it is called)
             const int k = s + rot;
             return k >= nsteps ? k - nsteps : k;
         };
-#pragma unroll
-        for (int d = 0; d < PF; ++d) fetch(d, slice(d) * GEMM_BK);
-        if constexpr (it == 0) request(row_base);
-        commit();  // (it == 1: the rows requested under the previous tile's K loop)
-        U8P_STAMP(it == 0 ? 1 : 4);  // tile image written
 
         int b_org[NT], out_pix[NT];
 #pragma unroll
@@ -190,18 +203,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) mfma_init(acc[mt][nt]);
 
-        auto read_frags = [&](int stage, int kk, Frags& f) {
-            const __bf16* a_hi = a_stage + stage * T::A_STAGE;
-            const __bf16* a_lo = a_hi + GA::ELEMS;
+        auto read_frags = [&](int kk, Frags& f) {
 #pragma unroll
             for (int mt = 0; mt < MTW; ++mt) {
-                f.a_hi[mt] = read_frag<false, GA::PITCH>(a_hi, mt * 16, lane);
-                if constexpr (PASSES >= 2) f.a_lo[mt] = read_frag<false, GA::PITCH>(a_lo, mt * 16, lane);
+                f.a_hi[mt] = read_frag<false, U8P_WPITCH>(w_hi + kk * GEMM_BK, mt * 16, lane);
+                if constexpr (PASSES >= 2) f.a_lo[mt] = read_frag<false, U8P_WPITCH>(w_lo + kk * GEMM_BK, mt * 16, lane);
             }
             int kq = kk * GEMM_BK + grp * 8;
             kq = kq < k_last ? kq : k_last;
             const int c = kq >> 6, ky = (kq >> 3) & 7;
-            const int tap_off = (c * p.R + ky) * p.Wp;
+            const int tap_off = (c * p.Rd + ky) * p.Wp;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const __bf16* src = img + b_org[nt] + tap_off;
@@ -220,42 +231,22 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
                     mfma_acc(acc[mt][nt], f.a_hi[mt], f.b_hi[nt]);
                 }
         };
+        // conv_fwd_img_kernel's K walk, from LDS only: the fragments of step s + 1 are read under the MFMAs of step s
         Frags fr[2];
-        if constexpr (it == 0) {
-            if (tid < 192) s_par[tid >> 6][tid & 63] = par_v;
-        }
-        stash(0, 0);
-        stash(1, 1);
-        fetch(0, slice(PF) * GEMM_BK);
-        fetch(1, slice(PF + 1) * GEMM_BK);
-        __syncthreads();  // image and the first two weight slices visible
-        read_frags(0, slice(0), fr[0]);
-        __syncthreads();
-        // conv_fwd_img_kernel's K loop, unrolled over the NSTEPS steps: no slice past the last one is requested (there: the zero
-        // block), so after step NSTEPS - PF - 3 the loop issues no load and after step NSTEPS - 3 it waits for none.
-        // vmcnt retires IN ORDER: the partner tile's rows may only be requested once every load this tile still waits for is
-        // OLDER than them -- i.e. behind the stash of the last weight slice -- or the next wait of the ring would wait for
-        // them too (the first version requested them in front of the loop: 27.3 us, exactly the two-round kernel's time).
+        read_frags(slice(0), fr[0]);
 #pragma unroll
         for (int s = 0; s < NSTEPS; ++s) {
-            if (s + 1 < NSTEPS) read_frags((s + 1) & 1, slice(s + 1), fr[(s + 1) & 1]);
+            if (s + 1 < NSTEPS) read_frags(slice(s + 1), fr[(s + 1) & 1]);
             mfma_step(fr[s & 1]);
-            if (s + 2 < NSTEPS) stash((s + 2) % PF, s & 1);
-            if (s + 2 + PF < NSTEPS) fetch((s + 2) % PF, slice(s + 2 + PF) * GEMM_BK);
-            if constexpr (it == 0) {
-                if (s == NSTEPS - 3) request(tile_rows(tile + 1));  // (the last stash is behind us: 2 steps + the epilogue cover the trip)
-            }
-            constexpr int N_MFMA = MTW * NT * (PASSES >= 3 ? 3 : PASSES);
+            constexpr int N_MFMA = MTW * NT * PASSES;
 #pragma unroll
             for (int i = 0; i < N_MFMA; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (i < N_MFMA / 2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, PASSES >= 2 ? 1 : 2, 0);
             }
-            __syncthreads();
         }
 
-        U8P_STAMP(it == 0 ? 2 : 5);  // K loop done
+        U8P_STAMP(h == 0 ? 2 : 5);  // K loop done
         // ---- epilogue: bias + LayerNorm over channels + ReLU (conv_fwd_img_kernel's, KG = 1) ----
         float bi[MTW][4], ga[MTW][4], be[MTW][4];
 #pragma unroll
@@ -317,24 +308,43 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void conv_fwd_u8_pair_kernel(const
                 }
             }
         }
-        U8P_STAMP(it == 0 ? 3 : 6);  // epilogue stores issued
-        // (the K loop ended with a barrier: every wave is done with the LDS image, the next tile's commit may overwrite it; the
-        // weight stages are rewritten by that tile's stash(0, 0) / stash(1, 1), whose readers finished before the same barrier)
+        U8P_STAMP(h == 0 ? 3 : 6);  // epilogue stores issued
     };
-    do_tile(std::integral_constant<int, 0>{});
-    do_tile(std::integral_constant<int, 1>{});
+
+    U8P_STAMP(1);  // half 0's image and the weights written (this thread)
+    for (int h = 0; h < n_half; ++h) {
+        __syncthreads();  // the image of half h (h == 0: and the weights, the epilogue parameters) visible
+        do_half(h);
+        if (h + 1 < n_half) {
+            __syncthreads();  // every wave is done with the LDS image: the next half's rows may overwrite it
+            commit(raw1, h + 1);
+            U8P_STAMP(4);  // next half's image written
+            if (h + 2 < n_half) request(raw1, h + 2);  // (images of more than four tiles: under the next half's K loop)
+        }
+    }
 #undef U8P_STAMP
+}
+
+// LDS bytes of the kernel above: resident weights + the image of a half (`Rd` rows of `Wp` columns, four planes)
+template <int PASSES>
+static inline int conv_u8_pair_lds(int Rd, int Wp) {
+    return ((PASSES >= 2 ? 2 : 1) * U8P_WPLANE + 4 * Rd * Wp) * 2;
+}
+// input rows that two consecutive 128-pixel tiles need together (conv_img_geometry's R for 256 pixels)
+static inline int conv_u8_pair_rows(const ConvGeom& g) {
+    int rows = g.npix <= 256 ? g.hout : ((256 + g.wout - 2) / g.wout + 1);
+    if (rows > g.hout) rows = g.hout;
+    return g.stride * (rows - 1) + g.ksz;
 }
 
 template <int PASSES, int NSTEPS>
 static int launch_conv_fwd_u8_pair(const ConvImgParams& p, hipStream_t st) {
-    using T = ConvImgTraits<2, PASSES, true>;
-    const int lds = (2 * T::A_STAGE + T::B_PLANES * p.plane_elems) * 2;
+    const int lds = conv_u8_pair_lds<PASSES>(p.Rd, p.Wp);
     static LdsConfigured configured;
     if (int rc = ensure_dynamic_lds(&conv_fwd_u8_pair_kernel<PASSES, NSTEPS>, lds, configured)) return rc;
-    const int grid = p.n_img * (p.tiles_per_img / 2);
-    ISDQN_REPORT_OCCUPANCY((&conv_fwd_u8_pair_kernel<PASSES, NSTEPS>), GEMM_THREADS, lds, grid);
-    hipLaunchKernelGGL((conv_fwd_u8_pair_kernel<PASSES, NSTEPS>), dim3(grid), dim3(GEMM_THREADS), lds, st, p);
+    const int grid = p.n_img;
+    ISDQN_REPORT_OCCUPANCY((&conv_fwd_u8_pair_kernel<PASSES, NSTEPS>), U8P_THREADS, lds, grid);
+    hipLaunchKernelGGL((conv_fwd_u8_pair_kernel<PASSES, NSTEPS>), dim3(grid), dim3(U8P_THREADS), lds, st, p);
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }

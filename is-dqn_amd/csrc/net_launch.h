@@ -133,16 +133,27 @@ static int conv_fwd_img(const Layer& l, bool x3, const float* params, const floa
     ip.order = PixelOrder(l.hout, l.wout, !l.is_u8 && ip.tiles_per_img == 1);
     ip.stamps = stamps_for(l.name);
     ip.ablate = 0;
+    ip.Rd = 0;
 #if defined(ISDQN_DEV)
     if (const char* e = getenv("ISDQN_ABLATE")) ip.ablate = atoi(e);
 #endif
     *done = true;
     if (l.is_u8) {
 #if !defined(ISDQN_NO_U8_PAIR)
-        // two pixel tiles per workgroup, the second one's frame rows prefetched into registers (conv_u8_pair.h): the tile image
-        // must be one batch of 2 x 256 positions, the frame ids four at most
-        // (four stacked frames: K = 256, eight K steps as straight-line code)
-        if (mt == 2 && ip.tiles_per_img % 2 == 0 && ip.R * (ip.Wp / 8) <= U8P_PB * GEMM_THREADS && l.cin == 4 && l.K == 256 && ip.ablate == 0)
+        // one workgroup of eight waves per image, weights resident in LDS, the image staged in halves of two tiles (conv_u8_pair.h):
+        //   * an even tile count (a half is two tiles; images of more than four tiles loop over their halves);
+        //   * four stacked frames (the frame ids live in four registers, the resident weights are [32][256]: K = 256, eight K steps
+        //     as straight-line code) and at most 32 output channels (mt == 2);
+        //   * the image of a half -- the input rows of 256 consecutive pixels -- is one batch of 2 x 512 positions;
+        //   * weights + that image fit the LDS (84 x 84: 34 + 41 KB, two workgroups per CU).
+        // Any other geometry runs on the one-tile kernel below.  Measured at the headline size: 26.2 -> 21.2 us, the step +2 % (c2 and
+        // c3).  At c5 (B = 1024, four rounds of 512 workgroups) the kernel is 86 -> 72 us but the untraced step did not resolve either
+        // way in four calls (+1.6, +0.1, -0.8, +0.2 %): there is no crossover to put a batch-size threshold at, and none is here
+        // (docs/NOTEBOOK.md 2026-10-20, profiles/conv0_image/).
+        ip.Rd = conv_u8_pair_rows(ip.g);
+        const int lds_pair = passes == 2 ? conv_u8_pair_lds<2>(ip.Rd, ip.Wp) : conv_u8_pair_lds<1>(ip.Rd, ip.Wp);
+        if (mt == 2 && ip.tiles_per_img % 2 == 0 && ip.Rd * (ip.Wp / 8) <= U8P_PB * U8P_THREADS && lds_pair <= LDS_LIMIT && l.cin == 4 &&
+            l.K == 256 && ip.ablate == 0)
             return passes == 2 ? launch_conv_fwd_u8_pair<2, 8>(ip, st) : launch_conv_fwd_u8_pair<1, 8>(ip, st);
 #endif
         if (passes == 2) return mt == 2 ? launch_conv_fwd_img<2, 2, true>(ip, st) : launch_conv_fwd_img<4, 2, true>(ip, st);

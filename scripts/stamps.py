@@ -38,6 +38,8 @@ span_cyc = s[:, 5].max() - t0
 span_rt = (s[:, 7].max() - s[:, 7].min())  # start-to-last-start only; use as lower bound
 order = np.argsort(s[:, 0])
 names = ["fill(load+convert+write)", "weights0+sync", "K loop", "epilogue issue", "store drain"]
+if layer == "Conv_0":  # conv_fwd_u8_pair_kernel (csrc/conv_u8_pair.h): slots 0 start, 1 / 4 image of half 0 / 1 written, 2 / 5 K loop done, 3 / 6 epilogue issued
+    names = ["weights + image of half 0 staged", "barrier + K loop of half 0", "epilogue of half 0 issued", "barrier + image of half 1 (commit)", "barrier + K loop of half 1"]
 if layer.startswith("wgrad:"):
     names = ["image 0 staged (fetch + commit)", "K steps of image 0", "image 1 staged (commit)", "K steps of image 1", "slab stores drained"]
 if layer == "head_chain":
