@@ -595,6 +595,37 @@ typedef struct isdqn_batch_decay {
     int32_t decay_kinds;       /* bit k: tensors of kind k decay; bits 0..6 only, at least one */
 } isdqn_batch_decay;
 
+/* The batch is the first member of the struct isdqn_batch_conservative below (through its isdqn_batch_decay). */
+#define ISDQN_BATCH_CONSERVATIVE 8
+
+/* CQL(H), the conservative term of offline Q-learning (Kumar et al. 2020): alpha * (logsumexp_a Q(s, a) - Q(s, a_b)) beside the
+ * configured loss.  THE definition.  It applies to every regressed pair k of a call (the selected pairs of isdqn_net_grad_on_batch
+ * included), on online head h = on0 + k of the STATE rows.  The action value Q_a comes from the head-output rows the loss reads (the
+ * combined rows of a dueling head):
+ *     scalar heads:     Q_a = the output;                                dQ_a/d(output) = 1
+ *     quantile heads:   Q_a = mean of the N values;                      dQ_a/d(output) = 1 / N on each of the N
+ *     histogram heads:  Q_a = sum_j p_j z_j, p = softmax(logits),
+ *                       z_j = v_min + (j + 1/2) eta  (HL-Gauss, C51);    dQ_a/d(logit j) = p_j (z_j - Q_a)
+ * Per transition b and pair k, with m = max_a Q_a, fp32, full-accuracy expf / logf, the maximum subtracted first:
+ *     c_bk      = m + log(sum_a exp(Q_a - m)) - Q_{a_b}
+ *     losses[k] = (1 / B) sum_b w_b (l_bk + alpha c_bk)                   (w_b: loss_weights, l_bk: the configured loss)
+ * losses_accum follows losses.  With pi = softmax_a Q, dL/d(output of (h, a')) gains
+ *     t = fl32(alpha w_b / B (pi_a' - 1{a' = a_b})) * dQ_a'/d(output),
+ * added once in fp32 to what the loss left, dout_new = fl32(dout_old + t); the head-bias gradient is the column sum of the new rows.
+ * q_values, targets and priorities are those of the call without the term, bit for bit, and nothing flows through the targets.
+ * cql_alpha == 0, or no flag: nothing is launched, read or routed differently, every bit is as without the option.  With
+ * cql_alpha > 0 a learn step on scalar heads takes the generic loss and head backward (the head chain knows one action per row).
+ * As with the decay, isdqn_batch keeps its size: a caller hands the entry points &x.base.base.batch and sets ISDQN_BATCH_CONSERVATIVE
+ * in its flags; base.weight_decay / base.decay_kinds are read only when ISDQN_BATCH_WEIGHT_DECAY is set as well, base.base.discount only
+ * with ISDQN_BATCH_DISCOUNT.  Honoured by learn / loss / their _target and debug forms / isdqn_net_grad_on_batch /
+ * isdqn_noisy_learn_on_batch, every torso.  ISDQN_ERR_ARG, nothing launched: cql_alpha negative, NaN or infinite.
+ * ISDQN_ERR_UNSUPPORTED: more than 64 regressed pairs, or histogram / quantile heads with more than 960 actions. */
+typedef struct isdqn_batch_conservative {
+    isdqn_batch_decay base; /* base.base.batch.flags carries ISDQN_BATCH_CONSERVATIVE */
+    float cql_alpha;        /* finite, >= 0; 0 = every bit as without the flag */
+    int32_t reserved;       /* 0 */
+} isdqn_batch_conservative;
+
 /* DQNNet.apply on `n_rows` observations (dqn.py:47-103) -> q [n_rows][n_heads*n_actions].
  * cnn: image j reads frame_ids[j*stack .. j*stack+stack-1]; fc: obs [n_rows][obs_c]. */
 int isdqn_net_forward(const isdqn_net_config* cfg, const float* params, const uint8_t* frames, int64_t frame_stride,

@@ -13,6 +13,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libisdqn_hip.so")
 SOURCES = ["api.hip", "tree_kernels.hip", "replay_kernels.hip", "net_kernels.hip"]
+# Translation units beside the four whose kernels and kernel order tests/golden/kernel_order.txt pins: compiled and linked into every
+# variant, and behind the four in emit_asm()'s list (scripts/isa_lint.py reads them all).
+EXTRA_SOURCES = ["conservative_kernels.hip"]
 HEADERS = sorted(f for f in os.listdir(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")) if f.endswith(".h")) + [
     os.path.join("..", "..", "include", "isdqn_hip.h")]
 # -fno-slp-vectorize: hipcc's SLP vectoriser turns scalar fp32 epilogue math into packed v_pk_*_f32 sequences, and one of
@@ -40,7 +43,7 @@ def build(force=False, verbose=True, variant=None, defines=(), extra_flags=()):
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     objs = []
     procs = []
-    for src in SOURCES:
+    for src in SOURCES + EXTRA_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
@@ -67,7 +70,7 @@ def emit_asm(force=False, verbose=False):
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     outs, procs = [], []
-    for src in SOURCES:
+    for src in SOURCES + EXTRA_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".s"))
         outs.append(o)

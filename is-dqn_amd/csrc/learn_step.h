@@ -68,6 +68,8 @@ static void head_chain_plan(LearnCtx& c, bool plan_heads) {
     // (histogram and quantile heads take the generic backward: head GEMMs at the logit width; the head chain is built for scalar heads)
     // (dueling heads too: the chain multiplies by the head kernel itself and knows no combine)
     if (P.dueling) return;
+    // (the conservative term too: its dL/dq is dense over the actions, the chain exploits one non-zero per row and pair)
+    if (c.cql_alpha > 0.f) return;
     if (!(c.update() && plan_heads && !hc_disabled && c.target_params == nullptr && P.head_nb == 0 && P.n_layers >= 2 && hid.kind == 1 &&
           !hid.is_head && hid.has_relu && hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0))
         return;
@@ -620,6 +622,7 @@ static int learn_or_loss(LearnCall call) {
     const Plan& P = *Pp;
     ISDQN_REQUIRE(call.params && batch && call.losses && call.ws, ISDQN_ERR_ARG, "null pointer");
     if ((rc = check_decay(call.weight_decay, call.decay_kinds))) return rc;
+    if ((rc = check_conservative(call.cql_alpha))) return rc;
     ISDQN_REQUIRE(batch->B == P.B, ISDQN_ERR_SHAPE, "batch->B != cfg->batch_size");
     ISDQN_REQUIRE(batch->action && batch->reward && batch->terminal, ISDQN_ERR_ARG, "null batch field");
     rc = check_input(cfg, batch->frames, batch->frame_stride, batch->frame_ids, batch->state);

@@ -16,6 +16,7 @@
 #include "conv_u8_pair.h"
 #include "conv_s8_pair.h"
 #include "head_loss.h"
+#include "conservative.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
 #include "quantile.h"
@@ -179,6 +180,7 @@ static LearnCall learn_call(const isdqn_net_config* cfg, LearnMode mode, const f
     c.losses = losses; c.q_values = q_values; c.targets = targets; c.ws = (float*)workspace; c.st = (hipStream_t)stream;
     // (the loss-only and the gradient-only calls update nothing: a decay behind their batch is not read)
     if (mode == LearnMode::Learn) batch_decay(batch, &c.weight_decay, &c.decay_kinds);
+    c.cql_alpha = batch_conservative(batch);  // (a loss term: every mode takes it)
     return c;
 }
 
@@ -601,6 +603,7 @@ extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu
         if ((rc = check_decay(weight_decay, decay_kinds))) return rc;
         ISDQN_REQUIRE(weight_decay == 0.f, ISDQN_ERR_UNSUPPORTED, "weight decay under NoisyNet exploration is not built");
     }
+    if ((rc = check_conservative(batch_conservative(batch)))) return rc;  // (in front of the first launch)
     NoisyTable tab;
     noisy_tables(P, &tab, nullptr);
     float* ws = (float*)workspace;
@@ -611,7 +614,9 @@ extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu
     // nothing; loss_finalize_kernel advances adam_count and leaves the bias corrections in the workspace, as in a plain learn step
     isdqn_batch_discount b{*batch, batch_discount(batch)};  // (the copy keeps the discounts that may follow the caller's batch)
     b.batch.flags |= ISDQN_BATCH_MIRROR_CURRENT;  // (compose wrote the mirror of eff; the *_target form rebuilds both mirrors itself)
+    b.batch.flags &= ~(ISDQN_BATCH_WEIGHT_DECAY | ISDQN_BATCH_CONSERVATIVE);  // (the copy ends at the discounts)
     LearnCall c = learn_call(cfg, LearnMode::GradOnly, eff, &b.batch, losses, q_values, targets, workspace, stream);
+    c.cql_alpha = batch_conservative(batch);  // (the conservative term behind the caller's batch)
     c.target_params = eff_target; c.adam_count = adam_count; c.loss_accum = losses_accum; c.priorities = priorities; c.grad_out = grad;
     rc = learn_or_loss(c);
     if (rc) return rc;

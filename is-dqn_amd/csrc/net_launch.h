@@ -590,6 +590,7 @@ struct LearnCall {
     float weight_decay = 0.f;  // AdamW (isdqn_batch_decay, read by learn_call for the calls that update; 0: plain Adam)
     int32_t decay_kinds = 0;   // bit k: tensors of isdqn_tensor_info::kind k decay
     float wd(int kind) const { return ((decay_kinds >> kind) & 1) ? weight_decay : 0.f; }  // what an optimizer entry of that kind carries
+    float cql_alpha = 0.f;     // the conservative term (isdqn_batch_conservative, read by learn_call in every mode; 0: none, nothing launched)
     bool learn() const { return mode != LearnMode::Loss; }  // a backward pass follows the loss
     bool update() const { return mode == LearnMode::Learn; }
 };
@@ -674,6 +675,16 @@ static inline void batch_decay(const isdqn_batch* batch, float* weight_decay, in
     *weight_decay = has ? d->weight_decay : 0.f;
     *decay_kinds = has ? d->decay_kinds : 0;
 }
+// The conservative term's alpha behind a batch that says it has one (include/isdqn_hip.h, isdqn_batch_conservative), else 0; unchecked
+// (check_conservative).
+static inline float batch_conservative(const isdqn_batch* batch) {
+    const bool has = batch != nullptr && (batch->flags & ISDQN_BATCH_CONSERVATIVE);
+    return has ? reinterpret_cast<const isdqn_batch_conservative*>(batch)->cql_alpha : 0.f;
+}
+static int check_conservative(float cql_alpha) {
+    ISDQN_REQUIRE(cql_alpha >= 0.f && cql_alpha <= 3.4028234e38f, ISDQN_ERR_ARG, "cql_alpha must be finite and >= 0");  // (NaN fails both)
+    return ISDQN_OK;
+}
 static int check_decay(float weight_decay, int32_t decay_kinds) {
     ISDQN_REQUIRE(weight_decay >= 0.f && weight_decay <= 3.4028234e38f, ISDQN_ERR_ARG, "weight_decay must be finite and >= 0");  // (NaN fails both)
     ISDQN_REQUIRE((decay_kinds & ~ISDQN_DECAY_KINDS_ALL) == 0, ISDQN_ERR_ARG, "decay_kinds: bits 0..6 only (kinds 7 and 8 are running statistics)");
@@ -737,6 +748,16 @@ static int loss_and_finalize(const Plan& P, const LearnCall& c, bool double_q = 
     else
         launch(td_kernel, 256, 2 * TD_ROWS * K * sizeof(float));
     ISDQN_HIP_CHECK(hipGetLastError());
+    if (c.cql_alpha > 0.f) {  // the conservative term (conservative_kernels.hip), on the rows and with the row partition of the launch above
+        ConservativeArgs ca{};
+        ca.out = a.out; ca.dout = a.dout; ca.loss_part = a.loss_part; ca.dbh_part = a.dbh_part;
+        ca.action = a.action; ca.loss_weights = a.loss_weights;
+        ca.B = B; ca.rows_per_blk = R ? R : TD_ROWS; ca.n_blk = n_blk; ca.K = K; ca.on0 = on0; ca.A = P.n_actions;
+        ca.nb = P.head_nb; ca.pitch = P.nlog_p; ca.quantile = P.qr ? 1 : 0;
+        ca.vmin = a.vmin; ca.eta = a.eta; ca.alpha = c.cql_alpha;
+        ca.dout_floats = (int64_t)P.Bb * P.nlog_p; ca.part_floats = (int64_t)P.B * (P.K + P.nlog_p);
+        if (int rc = launch_conservative(ca, c.st)) return rc;
+    }
     return loss_finalize(P, cfg, ws, n_blk, K, P.nlog_p, c.losses, c.loss_accum, learn, learn ? c.adam_count : nullptr, c.st);
 }
 

@@ -17,7 +17,8 @@ import numpy as np
 from experiments.base.dqn import train
 from experiments.atari.common import make_environment, make_replay, seeds
 from experiments.base.utils import prepare_logs
-from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, augment_kwargs, quantile_kappa
+from experiments.base.offline import environment_for
+from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, conservative_kwargs, augment_kwargs, quantile_kappa
 from slimdqn.networks.dqn import DQN
 
 
@@ -27,7 +28,7 @@ def run(argvs=sys.argv[1:], root=None):
     replicas.init_from_env()  # one process per GPU: picks this rank's device before the first GPU call (no-op alone)
     p = prepare_logs("atari", "dqn", argvs, root=root)
     q_seed, train_seed = seeds(p)
-    env = make_environment(p)  # (worker processes of a VectorEnv start here, before this process's first GPU call)
+    env = environment_for(p, make_environment)  # (worker processes of a VectorEnv start here, before this process's first GPU call)
     rb = make_replay(p, prioritized=False)
     agent = DQN(
         q_seed,
@@ -53,6 +54,7 @@ def run(argvs=sys.argv[1:], root=None):
         **noisy_kwargs(p),
         **ema_kwargs(p),
         **weight_decay_kwargs(p),
+        **conservative_kwargs(p),
         **augment_kwargs(p),
         huber_delta=quantile_kappa(p),
     )

@@ -42,7 +42,9 @@ def train(key, p: dict, agent, env, rb):
         agent.set_horizon_schedule(*anneal_schedule(p), replay_buffer=rb)
     epsilon_schedule = linear_schedule(1.0, p["epsilon_end"], p["epsilon_duration"])
     n_training_steps = 0
-    env.reset()
+    offline_dir = p.get("offline_dir")  # -offline (experiments/base/offline.py): no environment step feeds the replay
+    if not offline_dir:
+        env.reset()
     returns, lengths = [[0]], [[0]]
     best_avg_return = -float("inf")
     gathered = []
@@ -104,6 +106,17 @@ def train(key, p: dict, agent, env, rb):
                     after_target_update(step, logs)
         agent.learn_steps(owed, rb)
 
+    if offline_dir:
+        from experiments.base.offline import train_offline
+
+        return train_offline(rng, p, agent, env, rb, after_target_update, analysis_logs)
+    transition_log = None
+    if p.get("log_replay"):  # -logrb: every transition handed to rb.add goes into the log as well
+        from experiments.base.offline import TransitionLog, log_replay_adds
+
+        transition_log = TransitionLog(p["log_replay"], n_actions=env.n_actions)
+        log_replay_adds(rb, transition_log)
+
     for idx_epoch in range(p["n_epochs"]):
         steps_in_epoch, has_reset = 0, False
         t_epoch = time.perf_counter()
@@ -156,4 +169,6 @@ def train(key, p: dict, agent, env, rb):
         if os.environ.get("WORLD_SIZE", "1") != "1":  # rank 0: every replica's per-epoch metrics in one file
             replicas.write_gathered(os.path.join(os.path.dirname(os.path.dirname(p["save_path"])), "gathered_metrics.json"),
                                     gathered, EPOCH_FIELDS)
+        if transition_log is not None and idx_epoch == p["n_epochs"] - 1:
+            transition_log.close()
     return gathered

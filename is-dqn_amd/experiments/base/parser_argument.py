@@ -72,6 +72,10 @@ _ENGINE = [
     ("-ema", "--ema_tau", dict(type=float, default=0.0, help="EMA (Polyak) target network: target <- (1 - tau) * target + tau * online after every gradient step, on the device, instead of a copy every -tuf steps (BBF, SR-SPR: 0.005); 0 = off, in [0, 1]. DQN only: iS-DQN's target is a head of the online network, the target-free agents have none.")),
     ("-wd", "--weight_decay", dict(type=float, default=0.0, help="AdamW (optax.adamw; BBF, SR-SPR: 0.1): decoupled weight decay -- every learn step also takes learning_rate * weight_decay of its value off every element of the conv and dense kernels, on the device, in every Adam kernel. 0 = off (plain Adam, the bits of a run without the flag); finite and >= 0. With every agent, torso, loss and -gc; not with -noisy.")),
     ("-wdall", "--weight_decay_all", dict(default=False, action="store_true", help="-wd also decays the biases and the LayerNorm / BatchNorm scales and biases (never the running statistics). Means nothing without -wd.")),
+    ("-cql", "--cql_alpha", dict(type=float, default=0.0, help="CQL(H) (Kumar et al. 2020; offline QR-DQN + CQL: -qr -nq 200 -hd 1 -cql 1.0 -offline DIR): every loss also carries cql_alpha * (logsumexp_a Q(s, a) - Q(s, a_b)) per regressed head, on the device, its gradient dense over the actions. 0 = off (the bits of a run without the flag); finite and >= 0. With every agent, torso, head type, target flag, -gc, -noisy, -wd, -per, -aug and -anneal.")),
+    ("-logrb", "--log_replay", dict(type=str, default=None, help="Directory that receives every transition handed to the replay, in arrival order, as shard_%%06d.npz files (experiments/base/offline.py: TransitionLog) -- the dataset of a later -offline run. Single environment only: refused with -nenvs > 1.")),
+    ("-offline", "--offline_dir", dict(type=str, default=None, help="Train from the transition log in this directory instead of an environment: the replay is filled once through its own add, then every epoch issues -ntspe gradient steps, with the target updates and their hooks (ReDo, resets, anneal, logs) counted in gradient steps. -utd must be 1; a dataset larger than -rbc is refused. Offline QR-DQN + CQL: -qr -nq 200 -hd 1 -cql 1.0 -offline DIR.")),
+    ("-evals", "--evaluation_steps", dict(type=int, default=0, help="With -offline: environment steps of evaluation behind every epoch (epsilon = -ee, the running episode is finished, nothing enters the replay); 0 = none, and no environment is built.")),
     ("-anneal", "--anneal_period", dict(type=int, default=0, help="Anneal the update horizon and the discount (SR-SPR, BBF: -anneal 10000 -n 10 -nend 3 -gamma 0.97 -gammaend 0.997): over this many gradient steps, counted again from every -reset, n goes exponentially from -n to -nend and 1 - gamma from 1 - (-gamma) to 1 - (-gammaend); the replay keeps whole windows of max(-n, -nend) steps and every batch is cut at the step's horizon on the device. 0 = off. With every agent, torso, loss and target flag.")),
     ("-nend", "--update_horizon_end", dict(type=int, default=None, help="Final update horizon of -anneal (default: -n). Refused without -anneal.")),
     ("-gammaend", "--gamma_end", dict(type=float, default=None, help="Final discount of -anneal, in [0, 1) (default: -gamma). Refused without -anneal.")),
@@ -311,6 +315,28 @@ def weight_decay_kwargs(p) -> dict:
     if not p.get("weight_decay"):
         return {}
     return dict(weight_decay=float(p["weight_decay"]), weight_decay_all=bool(p.get("weight_decay_all", False)))
+
+
+# (-cql stays out of parameters.json like -wd)
+def check_conservative(p: dict) -> None:
+    """-cql negative, NaN or infinite fails before anything is written, with the agents' own message."""
+    from slimdqn import _conservative
+
+    _conservative.check_cql_alpha(p.get("cql_alpha", 0.0))
+
+
+def conservative_kwargs(p) -> dict:
+    """The agents' keyword of the conservative term from parsed parameters; without -cql the keywords are the ones they were before the
+    flag existed."""
+    return dict(cql_alpha=float(p["cql_alpha"])) if p.get("cql_alpha") else {}
+
+
+# (-logrb, -offline and -evals stay out of parameters.json like -cql)
+def check_offline(p: dict) -> None:
+    """-logrb with -nenvs > 1, -offline with -utd other than 1 and their kin fail before anything is written."""
+    from experiments.base import offline
+
+    offline.check_offline(p)
 
 
 # (-anneal, -nend and -gammaend stay out of parameters.json like -reset)

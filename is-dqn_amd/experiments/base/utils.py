@@ -42,6 +42,8 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     parser_argument.check_reset(p)
     parser_argument.check_ema(p, algo_name)
     parser_argument.check_weight_decay(p)
+    parser_argument.check_conservative(p)
+    parser_argument.check_offline(p)
     parser_argument.check_anneal(p)
     parser_argument.check_dueling(p)
     parser_argument.check_grad_clip(p)

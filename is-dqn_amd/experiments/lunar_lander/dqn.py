@@ -16,7 +16,8 @@ import numpy as np
 
 from experiments.base.dqn import train
 from experiments.base.utils import prepare_logs
-from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, quantile_kappa
+from experiments.base.offline import environment_for
+from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, conservative_kwargs, quantile_kappa
 from experiments.lunar_lander.common import make_environment, make_replay, seeds
 from slimdqn.networks.dqn import DQN
 
@@ -27,7 +28,7 @@ def run(argvs=sys.argv[1:], root=None):
     replicas.init_from_env()
     p = prepare_logs("lunar_lander", "dqn", argvs, root=root)
     q_seed, train_seed = seeds(p)
-    env = make_environment(p)
+    env = environment_for(p, make_environment)
     rb = make_replay(p)
     agent = DQN(
         q_seed,
@@ -52,6 +53,7 @@ def run(argvs=sys.argv[1:], root=None):
         **noisy_kwargs(p),
         **ema_kwargs(p),
         **weight_decay_kwargs(p),
+        **conservative_kwargs(p),
         huber_delta=quantile_kappa(p),
     )
     out = train(np.random.default_rng(train_seed), p, agent, env, rb)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip
+from slimdqn import _conservative
 from slimdqn import _optimizer
 
 
@@ -726,6 +727,19 @@ class QNetEngine:
         for g in list(self._captured or ()):
             g.destroy()
 
+    cql_alpha = 0.0  # weight of the conservative term of the following loss / gradient / learn calls (set_conservative); 0: none
+
+    def set_conservative(self, alpha: float) -> None:
+        """CQL(H) (Kumar et al. 2020) for the following calls of this engine: every loss, gradient and learn call adds
+        ``alpha * (logsumexp_a Q(s, a) - Q(s, a_b))`` per regressed pair to the configured loss, on the device (include/isdqn_hip.h,
+        isdqn_batch_conservative: the definition).  q_values, targets and priorities stay those of the configured loss.  0 is off: the
+        batches and the bits of an engine that never heard of it.  The weight travels in every batch ``make_batch`` builds from here on;
+        every captured update of this engine is dropped and captures again at its next run, as ``set_weight_decay`` does.  Every
+        torso, head type, target form and the noisy learn step take it; a learn step on scalar heads leaves the head chain."""
+        self.cql_alpha = _conservative.check_cql_alpha(alpha)
+        for g in list(self._captured or ()):
+            g.destroy()
+
     # ------------------------------------------------------------------ C-ABI calls
     def make_batch(self, *, frames=None, frame_stride=0, frame_ids=None, state=None, next_state=None, action=None, reward=None, terminal=None,
                    mirror_current: bool = False, priorities_ready: torch.cuda.Event | None = None, loss_weights=None, discount=None) -> _hip.Batch:
@@ -746,6 +760,12 @@ class QNetEngine:
             b, flags = _hip.BatchDecay(), b.flags
             b.flags = flags | _hip.BATCH_WEIGHT_DECAY
             b.weight_decay, b.decay_kinds = self.weight_decay, self.decay_kinds
+        if self.cql_alpha > 0.0:  # (isdqn_batch_conservative: the structs above, then the term's weight; the decay slot is read with its own flag)
+            inner, b = b, _hip.BatchConservative()
+            b.flags = inner.flags | _hip.BATCH_CONSERVATIVE
+            if self.weight_decay > 0.0:
+                b.weight_decay, b.decay_kinds = inner.weight_decay, inner.decay_kinds
+            b.cql_alpha = self.cql_alpha
         b.priorities_ready = None if priorities_ready is None else int(priorities_ready.cuda_event)
         b.B = self.batch_size
         b.frames = _hip.ptr(frames)

@@ -20,6 +20,7 @@ STATUS_NEGATIVE_VALUE, STATUS_TARGET_RANGE, STATUS_EMPTY_TREE = 1, 2, 4
 BATCH_MIRROR_CURRENT = 1  # include/isdqn_hip.h: ISDQN_BATCH_MIRROR_CURRENT
 BATCH_DISCOUNT = 2  # include/isdqn_hip.h: ISDQN_BATCH_DISCOUNT
 BATCH_WEIGHT_DECAY = 4  # include/isdqn_hip.h: ISDQN_BATCH_WEIGHT_DECAY
+BATCH_CONSERVATIVE = 8  # include/isdqn_hip.h: ISDQN_BATCH_CONSERVATIVE
 DECAY_KINDS_KERNELS, DECAY_KINDS_ALL = 0x03, 0x7F  # include/isdqn_hip.h: ISDQN_DECAY_KINDS_* (bit k: TensorInfo.kind k decays)
 TREE_MAX_BATCH = 4096
 ARCH_CNN, ARCH_FC, ARCH_IMPALA = 0, 1, 2
@@ -107,6 +108,10 @@ class BatchDiscount(Batch):  # isdqn_batch_discount: the batch, then the discoun
 
 class BatchDecay(BatchDiscount):  # isdqn_batch_decay: the batch (and its discount slot), then what flags & BATCH_WEIGHT_DECAY announces
     _fields_ = [("weight_decay", c_float), ("decay_kinds", c_int32)]  # AdamW's decay and the tensor kinds it acts on (include/isdqn_hip.h)
+
+
+class BatchConservative(BatchDecay):  # isdqn_batch_conservative: the batch (its discount and decay slots), then what flags & BATCH_CONSERVATIVE announces
+    _fields_ = [("cql_alpha", c_float), ("reserved", c_int32)]  # the weight of the conservative term (include/isdqn_hip.h)
 
 
 _SIGNATURES = {

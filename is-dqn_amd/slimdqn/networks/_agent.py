@@ -7,7 +7,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from slimdqn import _hip, _optimizer
+from slimdqn import _conservative, _hip, _optimizer
 from slimdqn._engine import NetOptions, QNetEngine, check_augment, check_noisy, check_redo
 
 
@@ -251,7 +251,7 @@ class EngineAgent:
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options: NetOptions,
-                           batch_norm=False, augment_pad=0, weight_decay=0.0, weight_decay_all=False):
+                           batch_norm=False, augment_pad=0, weight_decay=0.0, weight_decay_all=False, cql_alpha=0.0):
         """``options``: what the constructor picked and checked (NetOptions.check, behind its own rules); the two rules that stand
         behind it follow here.  Every option becomes a plain attribute of the agent and goes to every engine it builds.
         ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
@@ -262,11 +262,16 @@ class EngineAgent:
         ``weight_decay`` > 0: AdamW (optax.adamw, as BBF and SR-SPR train; include/isdqn_hip.h, isdqn_batch_decay) -- every learn step of
         every engine the agent builds also decays the conv and dense kernels by ``learning_rate * weight_decay`` of their value, with
         ``weight_decay_all`` the biases and the normalisation scales and biases too (QNetEngine.set_weight_decay).  0 is off: the bits
-        of an agent built without the argument.  Refused with ``noisy`` (ValueError), before anything is built."""
+        of an agent built without the argument.  Refused with ``noisy`` (ValueError), before anything is built.
+        ``cql_alpha`` > 0: the conservative term of CQL(H) (Kumar et al. 2020; include/isdqn_hip.h, isdqn_batch_conservative) -- every
+        loss and every learn step of every engine the agent builds adds ``cql_alpha * (logsumexp_a Q(s, a) - Q(s, a_b))`` per regressed
+        head (QNetEngine.set_conservative): the offline recipe with ``n_quantiles`` is QR-DQN + CQL.  0 is off: the bits of an agent
+        built without the argument.  Negative, NaN or infinite: ValueError, before anything is built."""
         check_augment(augment_pad, architecture_type)
         check_noisy(options.noisy, architecture_type, batch_norm, options.max_grad_norm)
         self.weight_decay = _optimizer.check_weight_decay(weight_decay, noisy=options.noisy)
         self.weight_decay_all = bool(weight_decay_all)
+        self.cql_alpha = _conservative.check_cql_alpha(cql_alpha)
         self.options = options
         for name, value in dataclasses.asdict(options).items():
             setattr(self, name, value)
@@ -308,6 +313,8 @@ class EngineAgent:
             eng.resample_on_learn = True  # every learn step of an agent draws first (eager and captured alike)
         if self.weight_decay > 0.0:
             eng.set_weight_decay(self.weight_decay, self.weight_decay_all)
+        if self.cql_alpha > 0.0:
+            eng.set_conservative(self.cql_alpha)
         if init:
             eng.init_params(self._seed)
         else:  # a batch of another size arrived: same parameter layout, new workspace

@@ -54,6 +54,7 @@ class DQN(EngineAgent):
         *,
         weight_decay: float = 0.0,
         weight_decay_all: bool = False,
+        cql_alpha: float = 0.0,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
@@ -67,7 +68,8 @@ class DQN(EngineAgent):
         ``munchausen_tau`` > 0: the target parameters run over the states as well as the next states: about one more forward of B
         images per step.
         ``weight_decay`` / ``weight_decay_all``: AdamW (EngineAgent._init_engine_agent) on the online parameters; the target parameters
-        are never the optimizer's and never decay."""
+        are never the optimizer's and never decay.
+        ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent) on the online parameters' state rows."""
         options = NetOptions.pick(locals())
         check_munchausen(double_q, munchausen_tau)  # (in front of the other rules, where this constructor has always asked it)
         options.check(architecture_type, features)
@@ -78,7 +80,8 @@ class DQN(EngineAgent):
         self.target_update_frequency = target_update_frequency
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
-                                gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all)
+                                gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
+                                cql_alpha=cql_alpha)
         self.target_params = self.params.copy()  # dqn.py:34
         self.target_sigma = self._engine.sigma.clone() if self.noisy else None  # (one persistent buffer, refreshed in place like the target)
         self.cumulated_loss = 0

@@ -66,11 +66,12 @@ class iSDQN(EngineAgent):
         *,
         weight_decay: float = 0.0,
         weight_decay_all: bool = False,
+        cql_alpha: float = 0.0,
     ):
         """The option keywords from ``huber_delta`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Here ``double_q`` lets online head 1 + k pick the next action that head k values, and
         ``ema_tau`` > 0 is refused (EMA_REFUSED): the target is head 0 of the online parameters.  ``weight_decay`` /
-        ``weight_decay_all``: AdamW (EngineAgent._init_engine_agent)."""
+        ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent)."""
         options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
         options.check(architecture_type, features, batch_norm)
@@ -86,7 +87,8 @@ class iSDQN(EngineAgent):
         self.priority_writeback = False
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options,
-                                batch_norm=batch_norm, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all)
+                                batch_norm=batch_norm, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
+                                cql_alpha=cql_alpha)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 

@@ -59,12 +59,13 @@ class TFDQN(EngineAgent):
         *,
         weight_decay: float = 0.0,
         weight_decay_all: bool = False,
+        cql_alpha: float = 0.0,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to target-free DQN:
         ``double_q`` is refused: see DOUBLE_Q_REFUSED.
         ``munchausen_tau`` > 0 is, unlike ``double_q``, well defined here: the single head is regularised by its own stop-gradient policy.
-        ``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.  ``weight_decay`` / ``weight_decay_all``: AdamW
+        ``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.  ``weight_decay`` / ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term
         (EngineAgent._init_engine_agent)."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
@@ -77,7 +78,8 @@ class TFDQN(EngineAgent):
         self.target_update_frequency = target_update_frequency
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, options, batch_norm=batch_norm,
-                                augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all)
+                                augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
+                                cql_alpha=cql_alpha)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54
