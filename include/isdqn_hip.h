@@ -858,6 +858,31 @@ int isdqn_net_reset(const isdqn_net_config* cfg, float* params, float* adam_m, f
                     float perturb_upper, void* workspace, void* stream);
 int isdqn_net_ema(const isdqn_net_config* cfg, float* target, const float* online, float tau, void* stream);
 
+/* Soft head shift: iS-DQN's target is head 0 of the online parameters, so it has no target buffer an EMA could act on; the soft form of
+ * iSDQN.shift_params moves every head towards its upper neighbour inside the parameter buffer, once per gradient step (K = 1: DQN's
+ * Polyak target on a shared torso; larger K slides the whole window of heads continuously at rate tau per step).  The reference has no
+ * counterpart.  Built BESIDE the plan, like the resets: no field of isdqn_net_config, no workspace region, no launch of any existing entry
+ * point.  On the device, in place, stream-ordered, capturable, without a host synchronisation, an allocation or an atomic.  THE definition:
+ * The last Dense holds n_heads = 1 + K head blocks of R rows each, R = (n_actions + dueling) * max(n_bins, n_quantiles, 1) -- the block
+ * isdqn_net_shift_params moves.  For every head k = 0 .. K-1, every row of the block and every one of the in_p weight columns (the padded
+ * ones too), and for the block's R biases:
+ *     new[k] = fl32( fl32(omt * old[k]) + fl32(tau * old[k+1]) ),   omt = fl32(1.0f - tau) computed once on the host,
+ * the two products and the sum rounded separately, never contracted into an FMA (isdqn_net_ema's arithmetic; a numpy float32 restatement
+ * gives the same bits).  Every head reads the value its upper neighbour had BEFORE the call.  Head K, the padding rows behind the last
+ * head, every other tensor, both Adam moments and the step count are neither arguments nor touched: they keep their bits.
+ *   tau == 0 launches nothing.  tau == 1 is isdqn_net_shift_params (the call is routed there: a NaN and the sign of a zero behave as in
+ *   the hard shift), followed by a rebuild of the mirror when a workspace is given.
+ *   workspace == NULL: the fp32 master alone (a noisy engine's sigma, a copy).  With a workspace the same launch also stores the S8 weight
+ *   mirror (region "wsplit", same offsets as the master) of every element it wrote, weights and biases, with the bits
+ *   isdqn_net_refresh_mirror would produce from the new master: a mirror that was current before the call is current after it, so the
+ *   steps of a captured update that run with ISDQN_BATCH_MIRROR_CURRENT stay one node longer on the same stream.
+ *   One launch: a lane owns a row of the block and four consecutive columns (16 bytes) and walks the heads upward with old[k+1] kept in
+ *   registers; every element of heads 0 .. K is loaded once and every element of heads 0 .. K-1 stored once; the grid is sized by
+ *   positions, capped at 2048 workgroups, and strides.
+ * ISDQN_ERR_ARG, nothing launched: NULL params; tau outside [0, 1] or NaN; n_heads < 2; params not 16-byte aligned (the lanes are 16
+ * bytes wide: there is no scalar path, a view at an odd offset is refused). */
+int isdqn_net_soft_shift(const isdqn_net_config* cfg, float* params, float tau, void* workspace, void* stream);
+
 /* Engine self-test: C[M][N] = A . B on the MFMA tile engine for every operand-layout
  * combination (a_tr/b_tr: 0 = operand stored [rows][K], 1 = stored [K][rows]).  Test hook. */
 int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int32_t a_tr,

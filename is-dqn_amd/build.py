@@ -16,6 +16,9 @@ SOURCES = ["api.hip", "tree_kernels.hip", "replay_kernels.hip", "net_kernels.hip
 # Translation units beside the four whose kernels and kernel order tests/golden/kernel_order.txt pins: compiled and linked into every
 # variant, and behind the four in emit_asm()'s list (scripts/isa_lint.py reads them all).
 EXTRA_SOURCES = ["conservative_kernels.hip"]
+# Further translation units of their own (tests/test_conservative_host.py holds the two lists above to what they are): compiled and linked
+# into every variant like the others; their assembly comes from emit_side_asm(), which tests/test_soft_shift_host.py lints.
+SIDE_SOURCES = ["soft_shift_kernels.hip"]
 HEADERS = sorted(f for f in os.listdir(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")) if f.endswith(".h")) + [
     os.path.join("..", "..", "include", "isdqn_hip.h")]
 # -fno-slp-vectorize: hipcc's SLP vectoriser turns scalar fp32 epilogue math into packed v_pk_*_f32 sequences, and one of
@@ -43,7 +46,7 @@ def build(force=False, verbose=True, variant=None, defines=(), extra_flags=()):
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     objs = []
     procs = []
-    for src in SOURCES + EXTRA_SOURCES:
+    for src in SOURCES + EXTRA_SOURCES + SIDE_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
@@ -63,14 +66,15 @@ def build(force=False, verbose=True, variant=None, defines=(), extra_flags=()):
     return lib
 
 
-def emit_asm(force=False, verbose=False):
-    """Device-side assembly of every source under the product flags (build/<name>.s), for scripts/isa_lint.py."""
+def emit_asm(force=False, verbose=False, sources=None):
+    """Device-side assembly of every source of SOURCES + EXTRA_SOURCES (or of ``sources``) under the product flags (build/<name>.s), for
+    scripts/isa_lint.py."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     outs, procs = [], []
-    for src in SOURCES + EXTRA_SOURCES:
+    for src in (SOURCES + EXTRA_SOURCES if sources is None else sources):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".s"))
         outs.append(o)
@@ -85,6 +89,11 @@ def emit_asm(force=False, verbose=False):
     return outs
 
 
+def emit_side_asm(force=False, verbose=False):
+    """emit_asm for SIDE_SOURCES."""
+    return emit_asm(force=force, verbose=verbose, sources=SIDE_SOURCES)
+
+
 if __name__ == "__main__":
     _variant = None
     _defs = []
@@ -96,4 +105,4 @@ if __name__ == "__main__":
     _extra = [_a for _a in sys.argv[1:] if _a.startswith("-f") or _a.startswith("-m")]
     print(build(force="--force" in sys.argv, variant=_variant, defines=_defs, extra_flags=_extra))
     if "--emit-asm" in sys.argv:
-        print("\n".join(emit_asm(force="--force" in sys.argv, verbose=True)))
+        print("\n".join(emit_asm(force="--force" in sys.argv, verbose=True) + emit_side_asm(force="--force" in sys.argv, verbose=True)))

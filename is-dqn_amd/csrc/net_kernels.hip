@@ -17,6 +17,7 @@
 #include "conv_s8_pair.h"
 #include "head_loss.h"
 #include "conservative.h"
+#include "soft_shift.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
 #include "quantile.h"
@@ -737,4 +738,38 @@ extern "C" int isdqn_selftest_gemm(const float* A, const float* B, float* C, int
     if (!a_tr && b_tr) return plain_big<false, true, false>(x3, a, nullptr, 0, b, C, N, M, N, K, split_k, slab, st);
     if (a_tr && !b_tr) return plain_big<true, false, false>(x3, a, nullptr, 0, b, C, N, M, N, K, split_k, slab, st);
     return plain_big<true, true, false>(x3, a, nullptr, 0, b, C, N, M, N, K, split_k, slab, st);
+}
+
+// ---- soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift): host code here, the kernel in soft_shift_kernels.hip ----
+
+extern "C" int isdqn_net_soft_shift(const isdqn_net_config* cfg, float* params, float tau, void* workspace, void* stream) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    const Plan& P = *Pp;
+    ISDQN_REQUIRE(params != nullptr, ISDQN_ERR_ARG, "null pointer");
+    ISDQN_REQUIRE(tau >= 0.f && tau <= 1.f, ISDQN_ERR_ARG, "tau must be in [0, 1]");  // (NaN fails both comparisons)
+    ISDQN_REQUIRE(P.n_heads >= 2, ISDQN_ERR_ARG, "a soft head shift needs n_heads >= 2: a single head has no upper neighbour");
+    ISDQN_REQUIRE(((uintptr_t)params & 15) == 0, ISDQN_ERR_ARG, "soft head shift: params must be 16-byte aligned");
+    if (tau == 0.f) return ISDQN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (tau == 1.f) {  // the hard shift's bits, a NaN and the sign of a zero included
+        if ((rc = isdqn_net_shift_params(cfg, params, stream))) return rc;
+        if (workspace != nullptr) return refresh_mirror(P, params, (float*)workspace, st);
+        return ISDQN_OK;
+    }
+    const Layer& l = P.L[P.n_layers - 1];
+    SoftShiftArgs a;
+    a.p = params;
+    a.mirror = workspace != nullptr ? (float*)workspace + P.wsplit_off : nullptr;
+    a.w_off = l.w_off; a.b_off = l.b_off; a.in_p = l.in_p;
+    a.R = (P.n_actions + (P.dueling ? 1 : 0)) * (P.head_nb > 0 ? P.head_nb : 1);  // the block isdqn_net_shift_params moves
+    a.K = P.n_heads - 1;
+    a.omt = 1.0f - tau; a.tau = tau;
+    // every position the grid touches lies inside the last Dense (the launcher checks what the 16-byte lanes and the mirror's groups need)
+    ISDQN_REQUIRE((int64_t)P.n_heads * a.R == (P.dueling ? P.raw : P.nlog) && (int64_t)P.n_heads * a.R <= l.out_p, ISDQN_ERR_SHAPE,
+                  "soft head shift: the head blocks do not tile the last Dense");
+    ISDQN_REQUIRE(l.w_off + (int64_t)l.out_p * l.in_p <= P.n_params && l.b_off + (int64_t)l.out_p <= P.n_params, ISDQN_ERR_SHAPE,
+                  "soft head shift: the last Dense lies outside the parameter buffer");
+    return launch_soft_shift(a, st);
 }

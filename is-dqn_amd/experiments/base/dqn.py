@@ -82,7 +82,24 @@ def train(key, p: dict, agent, env, rb):
             logs["reset"] = 1
         p["wandb"].log({"n_training_steps": step, **logs})
 
+    # Replay ratio (-rr N > 1, not in the reference; SR-SPR, BBF): every environment step past n_initial_samples owes N gradient steps,
+    # issued together (agent.learn_steps: one captured update of N steps where the agent has one); target updates, their hooks (ReDo,
+    # resets, logs) and the step handed to them then count GRADIENT steps, as experiments/base/offline.py does.  -tuf is a multiple of N
+    # (parser_argument.check_replay_ratio): the N steps of an environment step never straddle a target update, so learn_steps is asked for
+    # the same N every time and the agent keeps one captured update for the whole run.  N = 1 is the loop below, call for call.
+    replay_ratio = int(p.get("replay_ratio", 1))
+    n_gradient_steps = 0
+
     def after_step():
+        nonlocal n_gradient_steps
+        if replay_ratio > 1:
+            if n_training_steps > p["n_initial_samples"]:
+                agent.learn_steps(replay_ratio, rb)
+                n_gradient_steps += replay_ratio
+                updated, logs = agent.update_target_params(n_gradient_steps)
+                if updated:
+                    after_target_update(n_gradient_steps, logs)
+            return
         if n_training_steps > p["n_initial_samples"]:
             agent.update_online_params(n_training_steps, rb)
             updated, logs = agent.update_target_params(n_training_steps)
@@ -92,7 +109,22 @@ def train(key, p: dict, agent, env, rb):
     def after_round(first_step, count):
         """The cadence of `after_step` for the steps first_step+1 .. first_step+count of one vector round, with the gradient
         steps between two target updates issued together (agent.learn_steps: one graph replay)."""
+        nonlocal n_gradient_steps
         owed = 0
+        if replay_ratio > 1:  # (-utd is 1: every step past n_initial_samples owes N, and -tuf is counted in gradient steps)
+            for step in range(first_step + 1, first_step + count + 1):
+                if step <= p["n_initial_samples"]:
+                    continue
+                owed += replay_ratio
+                n_gradient_steps += replay_ratio
+                if n_gradient_steps % agent.target_update_frequency == 0:
+                    agent.learn_steps(owed, rb)
+                    owed = 0
+                    updated, logs = agent.update_target_params(n_gradient_steps)
+                    if updated:
+                        after_target_update(n_gradient_steps, logs)
+            agent.learn_steps(owed, rb)
+            return
         for step in range(first_step + 1, first_step + count + 1):
             if step <= p["n_initial_samples"]:
                 continue

@@ -70,6 +70,8 @@ _ENGINE = [
     ("-resets", "--reset_shrink", dict(type=float, default=0.5, help="Shrink factor in [0, 1] of the layers below the reset ones: p <- s * p + (1 - s) * fresh (BBF: 0.5; 1 keeps them). Means nothing without -reset.")),
     ("-resetl", "--reset_top_layers", dict(type=int, default=0, help="Number of top layers that are re-initialised fully; 0 = every Dense layer (BBF, SR-SPR). Means nothing without -reset.")),
     ("-ema", "--ema_tau", dict(type=float, default=0.0, help="EMA (Polyak) target network: target <- (1 - tau) * target + tau * online after every gradient step, on the device, instead of a copy every -tuf steps (BBF, SR-SPR: 0.005); 0 = off, in [0, 1]. DQN only: iS-DQN's target is a head of the online network, the target-free agents have none.")),
+    ("-sst", "--soft_shift_tau", dict(type=float, default=0.0, help="Soft head shift of iS-DQN: after every gradient step head k <- (1 - tau) * head k + tau * head k+1 for every k < -nbi, on the device, instead of the hard shift every -tuf steps (the counterpart of -ema, whose usual 0.005 fits here too; -nbi 1 is DQN's Polyak target on a shared torso); -tuf keeps the cadence of the logs, -redo and -reset. 0 = off, in [0, 1]. iS-DQN and its analysis agent only.")),
+    ("-rr", "--replay_ratio", dict(type=int, default=1, help="Gradient steps per environment step past -nis (SR-SPR, BBF: 2 to 16), issued together as one captured update where the agent has one. Above 1, -tuf, -redo, -reset and the step of their logs count gradient steps, as -anneal and the -isb schedule always do. 1 = the loop without the flag. Above 1: -utd must be 1, -tuf a multiple of -rr, not with -offline.")),
     ("-wd", "--weight_decay", dict(type=float, default=0.0, help="AdamW (optax.adamw; BBF, SR-SPR: 0.1): decoupled weight decay -- every learn step also takes learning_rate * weight_decay of its value off every element of the conv and dense kernels, on the device, in every Adam kernel. 0 = off (plain Adam, the bits of a run without the flag); finite and >= 0. With every agent, torso, loss and -gc; not with -noisy.")),
     ("-wdall", "--weight_decay_all", dict(default=False, action="store_true", help="-wd also decays the biases and the LayerNorm / BatchNorm scales and biases (never the running statistics). Means nothing without -wd.")),
     ("-cql", "--cql_alpha", dict(type=float, default=0.0, help="CQL(H) (Kumar et al. 2020; offline QR-DQN + CQL: -qr -nq 200 -hd 1 -cql 1.0 -offline DIR): every loss also carries cql_alpha * (logsumexp_a Q(s, a) - Q(s, a_b)) per regressed head, on the device, its gradient dense over the actions. 0 = off (the bits of a run without the flag); finite and >= 0. With every agent, torso, head type, target flag, -gc, -noisy, -wd, -per, -aug and -anneal.")),
@@ -301,6 +303,50 @@ def ema_kwargs(p) -> dict:
     return dict(ema_tau=float(p["ema_tau"])) if p.get("ema_tau") else {}
 
 
+# (-sst stays out of parameters.json like -ema)
+SOFT_SHIFT_ALGOS = ("isdqn", "analysisdqn")
+SOFT_SHIFT_TAU_REFUSED = "-sst / --soft_shift_tau must be in [0, 1] (0 = off)"
+
+
+def check_soft_shift(p: dict, algo_name: str) -> None:
+    """-sst outside [0, 1], or > 0 on any agent but iS-DQN and its analysis agent (the agents' own message), fails before anything is
+    written."""
+    tau = p.get("soft_shift_tau", 0.0)
+    if not 0.0 <= tau <= 1.0:  # (NaN fails both comparisons)
+        raise ValueError(SOFT_SHIFT_TAU_REFUSED)
+    if tau > 0.0 and algo_name not in SOFT_SHIFT_ALGOS:
+        from slimdqn.networks._agent import SOFT_SHIFT_REFUSED
+
+        raise ValueError(SOFT_SHIFT_REFUSED)
+
+
+def soft_shift_kwargs(p) -> dict:
+    """The agents' soft-shift keyword from parsed parameters; without -sst the keywords are the ones they were before the flag existed."""
+    return dict(soft_shift_tau=float(p["soft_shift_tau"])) if p.get("soft_shift_tau") else {}
+
+
+# (-rr stays out of parameters.json like -sst)
+REPLAY_RATIO_REFUSED = "-rr / --replay_ratio must be >= 1 (1 = one gradient step every -utd environment steps)"
+REPLAY_RATIO_UTD_REFUSED = "-rr / --replay_ratio above 1 issues several gradient steps per environment step: -utd / --data_to_update must be 1"
+REPLAY_RATIO_OFFLINE_REFUSED = "-rr / --replay_ratio counts gradient steps per environment step: -offline / --offline_dir has no environment steps"
+REPLAY_RATIO_TUF_REFUSED = ("-tuf / --target_update_frequency counts gradient steps under -rr / --replay_ratio and must be a multiple of it "
+                            "(the gradient steps of one environment step never straddle a target update)")
+
+
+def check_replay_ratio(p: dict) -> None:
+    """-rr below 1, -rr above 1 with -utd other than 1 or with -offline, or a -tuf that is no multiple of -rr fails before anything is
+    written."""
+    rr = p.get("replay_ratio", 1)
+    if rr < 1:
+        raise ValueError(REPLAY_RATIO_REFUSED)
+    if rr > 1 and p["data_to_update"] != 1:
+        raise ValueError(REPLAY_RATIO_UTD_REFUSED)
+    if rr > 1 and p.get("offline_dir"):
+        raise ValueError(REPLAY_RATIO_OFFLINE_REFUSED)
+    if p["target_update_frequency"] % rr != 0:
+        raise ValueError(REPLAY_RATIO_TUF_REFUSED)
+
+
 # (-wd and -wdall stay out of parameters.json like -reset)
 def check_weight_decay(p: dict) -> None:
     """-wd negative, NaN or infinite, or > 0 with -noisy, fails before anything is written, with the agents' own message."""
@@ -384,9 +430,9 @@ def check_engine_arguments(p: dict) -> None:
 
 
 def n_gradient_steps(p: dict) -> int:
-    """Gradient steps of a whole run (the length of the beta schedule): one every data_to_update environment steps once
+    """Gradient steps of a whole run (the length of the beta schedule): replay_ratio every data_to_update environment steps once
     n_initial_samples are in the buffer."""
-    return max(1, int((p["n_epochs"] * p["n_training_steps_per_epoch"] - p["n_initial_samples"]) / p["data_to_update"]))
+    return max(1, int((p["n_epochs"] * p["n_training_steps_per_epoch"] - p["n_initial_samples"]) / p["data_to_update"]) * int(p.get("replay_ratio", 1)))
 
 
 def histogram_loss_kwargs(p) -> dict:

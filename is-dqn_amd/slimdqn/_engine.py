@@ -903,6 +903,28 @@ class QNetEngine:
             _hip.check(self.lib.isdqn_net_shift_params(ctypes.byref(self.cfg), _hip.ptr(self.sigma), _hip.stream_ptr(self.device)))
         self._mirror_version = None  # the head rows moved in the master only
 
+    def soft_shift(self, tau: float, params=None) -> None:
+        """Soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift): head k <- (1 - tau) * head k + tau * head k+1 on the last Dense,
+        k < n_heads - 1, every head reading its neighbour's value from before the call; one stream-ordered launch.  ``params`` None: the
+        engine's own parameters, and the same launch stores the weight mirror of the rows it wrote -- a mirror that was current stays
+        current, one that was not stays marked so.  A noisy engine shifts ``sigma`` with the same rule and the masters alone (its mirror
+        holds the composed parameters, which the next step's compose rebuilds); another buffer of the layout: that buffer alone."""
+        own = params is None
+        p = self.params if own else params
+        ws = _hip.ptr(self.workspace) if own and not self.noisy else 0
+        _hip.check(self.lib.isdqn_net_soft_shift(ctypes.byref(self.cfg), _hip.ptr(p), float(tau), ws, _hip.stream_ptr(self.device)),
+                   "isdqn_net_soft_shift")
+        if not own:
+            return
+        if self.noisy:
+            _hip.check(self.lib.isdqn_net_soft_shift(ctypes.byref(self.cfg), _hip.ptr(self.sigma), float(tau), 0, _hip.stream_ptr(self.device)),
+                       "isdqn_net_soft_shift")
+            if tau > 0:
+                self._mirror_version = None  # (it held eff of the unshifted masters)
+        elif tau == 1:
+            self._mirror_holds(None)  # the hard shift's route ends by rebuilding the mirror from the new parameters
+        # otherwise the raw-pointer write moved neither torch's version counter nor the relation between master and mirror
+
     def best_action(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, idx_network: int, params=None) -> torch.Tensor:
         p = self._acting_params(params)
         _hip.check(

@@ -231,6 +231,8 @@ _SIGNATURES = {
         [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p],
     ),
     "isdqn_net_ema": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_float, c_void_p]),
+    # soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift): cfg, params, tau, workspace or NULL, stream
+    "isdqn_net_soft_shift": (c_int32, [POINTER(NetConfig), c_void_p, c_float, c_void_p, c_void_p]),
     "isdqn_selftest_gemm": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],

@@ -115,6 +115,21 @@ def check_ema_tau(ema_tau, supported: bool = False) -> float:
     return tau
 
 
+SOFT_SHIFT_REFUSED = (
+    "soft_shift_tau > 0 needs heads to shift: only iS-DQN and its analysis agent keep 1 + K heads in one set of parameters (DQN's "
+    "soft target is ema_tau, on its target buffer; the target-free agents have no target)")
+
+
+def check_soft_shift_tau(soft_shift_tau, supported: bool = False) -> float:
+    """soft_shift_tau of an agent's constructor: in [0, 1] (NaN refused), and 0 for every agent but iS-DQN's (SOFT_SHIFT_REFUSED)."""
+    tau = float(soft_shift_tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("soft_shift_tau must be in [0, 1] (0 = off: the hard head shift at every target update)")
+    if tau > 0.0 and not supported:
+        raise ValueError(SOFT_SHIFT_REFUSED)
+    return tau
+
+
 def augment_seed(seed: int) -> int:
     """64-bit seed of the agent's random-shift draws: a child of the agent's seed in numpy's SeedSequence tree under a spawn key of its
     own ((2,); ``recycle_seed`` has (1, k)), never the seed itself."""

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from slimdqn._engine import NetOptions, check_munchausen
-from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau
+from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau, check_soft_shift_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -55,6 +55,7 @@ class DQN(EngineAgent):
         weight_decay: float = 0.0,
         weight_decay_all: bool = False,
         cql_alpha: float = 0.0,
+        soft_shift_tau: float = 0.0,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
@@ -69,11 +70,13 @@ class DQN(EngineAgent):
         images per step.
         ``weight_decay`` / ``weight_decay_all``: AdamW (EngineAgent._init_engine_agent) on the online parameters; the target parameters
         are never the optimizer's and never decay.
-        ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent) on the online parameters' state rows."""
+        ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent) on the online parameters' state rows.
+        ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head; the soft target here is ``ema_tau``."""
         options = NetOptions.pick(locals())
         check_munchausen(double_q, munchausen_tau)  # (in front of the other rules, where this constructor has always asked it)
         options.check(architecture_type, features)
         self.ema_tau = check_ema_tau(ema_tau, supported=True)
+        check_soft_shift_tau(soft_shift_tau)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
         self.data_to_update = data_to_update

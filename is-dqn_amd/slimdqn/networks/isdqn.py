@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from slimdqn._engine import NetOptions
-from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau
+from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau, check_soft_shift_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -67,13 +67,19 @@ class iSDQN(EngineAgent):
         weight_decay: float = 0.0,
         weight_decay_all: bool = False,
         cql_alpha: float = 0.0,
+        soft_shift_tau: float = 0.0,
     ):
         """The option keywords from ``huber_delta`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Here ``double_q`` lets online head 1 + k pick the next action that head k values, and
         ``ema_tau`` > 0 is refused (EMA_REFUSED): the target is head 0 of the online parameters.  ``weight_decay`` /
-        ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent)."""
+        ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent).
+        ``soft_shift_tau`` > 0: the soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift) -- every gradient step is followed by
+        head k <- (1 - tau) * head k + tau * head k+1 on the device (noisy: sigma likewise), in the eager step and inside the captured
+        one, on the step's own stream; ``update_target_params`` then shifts nothing and only reports its logs.  0 keeps the hard shift
+        every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError."""
         options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
+        self.soft_shift_tau = check_soft_shift_tau(soft_shift_tau, supported=True)
         options.check(architecture_type, features, batch_norm)
         self.n_bellman_iterations = n_bellman_iterations
         self.last_idx_mlp = len(features) if architecture_type == "fc" else len(features) - 3
@@ -107,7 +113,7 @@ class iSDQN(EngineAgent):
             steps = live.S
         else:
             steps = 1 if settled else n_steps
-        g = self._graphed_update(replay_buffer, steps=steps)
+        g = self._graphed_update(replay_buffer, steps=steps, **self._soft_shift_step(replay_buffer))
         if g is None:
             for _ in range(n_steps):
                 self.update_online_params(0, replay_buffer)
@@ -121,19 +127,37 @@ class iSDQN(EngineAgent):
             if live is not None and live.S > 1 and live.rb is replay_buffer:  # learn_steps' capture is the live graph: eager step
                 g = None
             else:
-                g = self._graphed_update(replay_buffer)
+                g = self._graphed_update(replay_buffer, **self._soft_shift_step(replay_buffer))
             if g is not None:
                 self._run_graph(g)  # same draws, same kernels, same bits as the eager branch below (tests/test_gpu_graphed_update.py)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
+            if self.soft_shift_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
+                self._engine.soft_shift(self.soft_shift_tau)
             if self.priority_writeback and hasattr(replay_buffer, "update_device"):
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_losses += losses` (isdqn.py:62) happens on the device inside the step
 
+    def _soft_shift_step(self, replay_buffer) -> dict:
+        """What _graphed_update is handed under ``soft_shift_tau`` > 0: the learn call and the soft shift behind it, enqueued on one
+        stream -- the captured step gets one more node and no new branch -- and a key that holds the tau.  {} without."""
+        if not self.soft_shift_tau > 0.0:
+            return {}
+        eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
+        tau = self.soft_shift_tau
+
+        def learn(cb):
+            eng.learn_on_batch(cb)
+            eng.soft_shift(tau)
+
+        return dict(learn=learn, key=("soft_shift", tau))
+
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:
-            self.params = self.shift_params(self.params)
+            # with soft_shift_tau > 0 the heads follow every gradient step instead: nothing is shifted here
+            if not self.soft_shift_tau > 0.0:
+                self.params = self.shift_params(self.params)
             eng = self._engine
             self.cumulated_losses = self.cumulated_losses + eng.losses_accum.cpu().numpy().astype(np.float64)
             eng.losses_accum.zero_()

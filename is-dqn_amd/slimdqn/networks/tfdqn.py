@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from slimdqn._engine import NetOptions
-from slimdqn.networks._agent import EngineAgent, check_ema_tau
+from slimdqn.networks._agent import EngineAgent, check_ema_tau, check_soft_shift_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -60,17 +60,19 @@ class TFDQN(EngineAgent):
         weight_decay: float = 0.0,
         weight_decay_all: bool = False,
         cql_alpha: float = 0.0,
+        soft_shift_tau: float = 0.0,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to target-free DQN:
         ``double_q`` is refused: see DOUBLE_Q_REFUSED.
         ``munchausen_tau`` > 0 is, unlike ``double_q``, well defined here: the single head is regularised by its own stop-gradient policy.
         ``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.  ``weight_decay`` / ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term
-        (EngineAgent._init_engine_agent)."""
+        (EngineAgent._init_engine_agent).  ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head, nothing to shift."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
         options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
+        check_soft_shift_tau(soft_shift_tau)
         options.check(architecture_type, features, batch_norm)
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
         self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, batch_norm)
