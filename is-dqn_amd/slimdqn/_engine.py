@@ -885,9 +885,11 @@ class QNetEngine:
 
     def commit_batch_stats(self) -> None:
         """params["batch_stats"] <- the collection the last training-mode forward in this workspace returned (the analysis agents keep
-        the evaluation batch's: analysisdqn.py:121-131)."""
+        the evaluation batch's: analysisdqn.py:121-131).  The running averages are written in the master alone: the weight mirror is
+        marked stale."""
         _hip.check(self.lib.isdqn_net_bn_commit_running(ctypes.byref(self.cfg), _hip.ptr(self.params), _hip.ptr(self.workspace),
                                                         _hip.stream_ptr(self.device)), "isdqn_net_bn_commit_running")
+        self._mirror_version = None
 
     def batch_stats_slice(self) -> slice:
         """Where the running averages (tensor kinds 7, 8) sit in the flat parameter buffer: one contiguous block behind the optimised ones."""
@@ -908,13 +910,15 @@ class QNetEngine:
         k < n_heads - 1, every head reading its neighbour's value from before the call; one stream-ordered launch.  ``params`` None: the
         engine's own parameters, and the same launch stores the weight mirror of the rows it wrote -- a mirror that was current stays
         current, one that was not stays marked so.  A noisy engine shifts ``sigma`` with the same rule and the masters alone (its mirror
-        holds the composed parameters, which the next step's compose rebuilds); another buffer of the layout: that buffer alone."""
+        holds the composed parameters, which the next step's compose rebuilds); another buffer of the layout: that buffer alone, master
+        only -- handing in the engine's own ``params`` that way marks the mirror stale."""
         own = params is None
         p = self.params if own else params
         ws = _hip.ptr(self.workspace) if own and not self.noisy else 0
         _hip.check(self.lib.isdqn_net_soft_shift(ctypes.byref(self.cfg), _hip.ptr(p), float(tau), ws, _hip.stream_ptr(self.device)),
                    "isdqn_net_soft_shift")
         if not own:
+            self._wrote_without_mirror(params)
             return
         if self.noisy:
             _hip.check(self.lib.isdqn_net_soft_shift(ctypes.byref(self.cfg), _hip.ptr(self.sigma), float(tau), 0, _hip.stream_ptr(self.device)),
@@ -1005,8 +1009,9 @@ class QNetEngine:
         layer >= ``split_layer`` (default: the first Dense layer) take the upper factor pair, the others the lower one.  ``params`` None:
         the engine's own parameters, with ``adam_m`` / ``adam_v`` cleared where written (``moments``), ``adam_count`` zeroed (``count``)
         and the weight mirror rebuilt.  Another buffer of the layout (a target copy, a sigma buffer): that buffer alone -- no moments, no
-        count, no mirror; a noisy engine's own ``sigma`` is recognised and takes ``sigma_m`` / ``sigma_v`` as its moments.  One
-        stream-ordered call; no pointer moves."""
+        count, no mirror (the engine's own ``params`` handed in that way are written as any buffer is, and the mirror is marked stale); a
+        noisy engine's own ``sigma`` is recognised and takes ``sigma_m`` / ``sigma_v`` as its moments.  One stream-ordered call; no
+        pointer moves."""
         assert fresh.dtype == torch.float32 and fresh.numel() == self.n_param_floats and fresh.is_contiguous() and fresh.device == self.params.device
         if split_layer is None:
             split_layer = self.reset_layout()[1]
@@ -1031,14 +1036,18 @@ class QNetEngine:
             # as in redo: the raw-pointer write does not move torch's version counter and the call's last launch rebuilt the mirror from
             # the new parameters (a noisy engine: the mirror no longer holds eff, and _mirror_holds marks it as not holding params)
             self._mirror_holds(None)
+        else:
+            self._wrote_without_mirror(params)
 
     def ema(self, target: torch.Tensor, tau: float, online: torch.Tensor | None = None) -> None:
         """target <- (1 - tau) * target + tau * online (include/isdqn_hip.h, isdqn_net_ema; ``online`` None: the engine's parameters) over
-        two buffers of the parameter layout, one stream-ordered launch."""
+        two buffers of the parameter layout, one stream-ordered launch.  The weight mirror is not written: a ``target`` that is the
+        engine's own ``params`` marks it stale."""
         online = self.params if online is None else online
         assert target.dtype == torch.float32 and target.numel() == self.n_param_floats and online.numel() == self.n_param_floats
         _hip.check(self.lib.isdqn_net_ema(ctypes.byref(self.cfg), _hip.ptr(target), _hip.ptr(online), float(tau), _hip.stream_ptr(self.device)),
                    "isdqn_net_ema")
+        self._wrote_without_mirror(target)
 
     def fresh_sigma(self) -> torch.Tensor:
         """A new device tensor holding what ``init_sigma`` writes into ``sigma``: the source of a reset of sigma."""
@@ -1076,6 +1085,15 @@ class QNetEngine:
     def invalidate_mirror(self) -> None:
         """Force the next call to rebuild the weight mirror from ``params`` (for writers that bypass torch's version counter)."""
         self._mirror_version = None
+
+    def _wrote_without_mirror(self, buffer: torch.Tensor) -> None:
+        """The call just enqueued wrote ``buffer`` through its raw pointer and was handed no workspace.  A buffer of the caller's is
+        none of the mirror's business; one whose bytes overlap the engine's own parameter storage (``params=eng.params``, a view or
+        a slice of it: the addresses decide, not the object) moved the master alone, and the mirror no longer holds it."""
+        lo = self.params.data_ptr()
+        at = buffer.data_ptr()
+        if at < lo + self.params.numel() * self.params.element_size() and lo < at + buffer.numel() * buffer.element_size():
+            self._mirror_version = None
 
     def _mirror_made_current(self) -> None:
         self._mirror_version = self.params._version
