@@ -74,6 +74,13 @@ __device__ __forceinline__ float hl_soft_value(const float* __restrict__ row, in
     return m + tau * logf(s);
 }
 
+// The butterfly of wave_sum on doubles, for the one place that needs a normaliser without float32's rounding (hl_loss_kernel's dL/dl).
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // q[row][c] = Q of column c = h * A + a (c < nha) from logits[row][c * nb .. c * nb + nb); the padding columns of q are not written.
 __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict__ logits, int n_rows, int nha, int nb, int nlog_p,
                                                         int nha_p, float vmin, float eta, float* __restrict__ q) {
@@ -90,6 +97,10 @@ __global__ __launch_bounds__(256) void hl_expect_kernel(const float* __restrict_
 //   target = r + (1 - terminal) gamma^n max_a' Q_{tg0+k}(s', a');  y = clamp(target, v_min, v_max)
 //   u_i = erf((e_i - y) / (sqrt(2) sigma)),  p_j = (u_{j+1} - u_j) / (u_nb - u_0)   (the clamp keeps u_nb - u_0 away from 0/0)
 //   CE = w_b (logsumexp(l) - sum_j p_j l_j),  dL/dl_j = w_b (softmax(l)_j - p_j) / B on the taken action's nb logits, 0 elsewhere.
+// dL/dl is rounded once: softmax(l)_j - p_j is formed in double from the float32 e_j and u_i, each histogram divided by the double sum of
+// its own float32 terms, so both sum to one to 1e-16 and the nb entries of a pair sum to zero within nb 2^-24 of the largest -- also
+// where the two histograms nearly agree (at two bins both are near 1/2, and float32 roundings of each would be what is left of their
+// difference).  The loss, q_values, targets and priorities keep their float32 arithmetic and their bits.
 // a.sel != null: max_a' becomes the value head's expectation at the first argmax of the expectations of the selector head.
 // a.mun != null: the target is the Munchausen one on the expectations of the value head -- its state row for the bonus, the soft
 // value of its next-state row.  q_values / targets: the expectation and the unclamped scalar target.
@@ -144,15 +155,22 @@ __global__ __launch_bounds__(256) void hl_loss_kernel(const HeadLossArgs a) {
         const float qv = w / s;
         const float y = fminf(fmaxf(tg, vmin), vmin + (float)nb * eta);
         const float u0 = erff((vmin - y) * inv_s), un = erff((vmin + (float)nb * eta - y) * inv_s);
-        const float inv_norm = 1.f / (un - u0), inv_sum = 1.f / s;
+        const float inv_norm = 1.f / (un - u0);
+        double es = 0.0;
+#pragma unroll
+        for (int t = 0; t < PER_LANE; ++t) es += (double)e[t];  // (0 past nb)
+        const double inv_sum_d = 1.0 / wave_sum_f64(es), inv_norm_d = 1.0 / ((double)un - (double)u0);
+        const double scale_d = (double)inv_b * (double)st.w[bl];
         float pl = 0.f;
 #pragma unroll
         for (int t = 0; t < PER_LANE; ++t) {
             const int j = lane + 64 * t;
             if (j < nb) {
-                const float p = (erff((vmin + (float)(j + 1) * eta - y) * inv_s) - erff((vmin + (float)j * eta - y) * inv_s)) * inv_norm;
+                const float uh = erff((vmin + (float)(j + 1) * eta - y) * inv_s), ul = erff((vmin + (float)j * eta - y) * inv_s);
+                const float p = (uh - ul) * inv_norm;
                 pl += p * v[t];
-                s_dl[(int64_t)pr * nb + j] = (e[t] * inv_sum - p) * inv_b * st.w[bl];
+                // (uh of bin j is ul of bin j + 1 bit for bit: the double differences telescope to un - u0)
+                s_dl[(int64_t)pr * nb + j] = (float)(((double)e[t] * inv_sum_d - ((double)uh - (double)ul) * inv_norm_d) * scale_d);
             }
         }
         pl = wave_sum(pl);

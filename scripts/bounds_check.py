@@ -53,7 +53,7 @@ def report(case, omit=None):
     print(json.dumps({"case": case, "bad": bad, "site": site, "addr": hex(addr), "omitted": omit}), flush=True)
 
 
-def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False, n_quantiles=0, categorical=False, dueling=False, max_grad_norm=0.0):
+def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, grad=True, omit=None, double_q=False, n_bins=0, munchausen=False, n_quantiles=0, categorical=False, dueling=False, max_grad_norm=0.0, cql=False):
     n_heads = 1 + K if K > 0 else 1
     eng = QNetEngine(obs, A, n_heads, feats, arch, ln, B, batch_norm=bn, double_q=double_q, n_bins=n_bins, min_value=-10.0, max_value=10.0, sigma=0.3,
                      munchausen_tau=0.03 if munchausen else 0.0, n_quantiles=n_quantiles, huber_delta=1.0 if n_quantiles else 0.0, categorical=categorical, dueling=dueling,
@@ -120,6 +120,13 @@ def run_case(name, arch, obs, feats, K, A, B, ln=True, bn=False, target=False, g
     eng.loss_on_batch(wbatch)
     if grad:
         eng.grad_on_batch(wbatch, grad_out)
+    if cql:  # the conservative term on the loss kernel's row partition (conservative_kernels.hip), after everything else, as the weights are
+        eng.set_conservative(0.7)
+        cbatch = eng.make_batch(**inputs, action=action, reward=reward, terminal=terminal, loss_weights=weights)
+        eng.learn_on_batch(cbatch)
+        eng.loss_on_batch(cbatch)
+        if grad:
+            eng.grad_on_batch(cbatch, grad_out)
     report(name, omit)
     del eng
     torch.cuda.empty_cache()
@@ -190,10 +197,17 @@ if __name__ == "__main__":
         # workspace): the headline plan (Dense_0 through its one slab, per-image conv slabs) and dueling heads (the live mask)
         dict(name="gc-cnn-headline-B8", arch="cnn", obs=(84, 84, 4), feats=HL, K=9, A=9, B=8, max_grad_norm=10.0),
         dict(name="gc-dueling-cnn-tiny-B6", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 14), K=3, A=5, B=6, dueling=True, max_grad_norm=1e-3),
+        # the distributional loss kernels off R = 4 transitions per workgroup (head_loss.h, rows_per_wg; tests/helpers/head_geometry.py's
+        # table): 3 + 2 rows with the conservative term on the same partition, 2 + 2 + 1 rows and one row per workgroup at A = 1, and the
+        # widest head row the plan takes (11 * 2 * 248 = 5456 outputs: dense_post_kernel's three staged rows fill its 64 KB of LDS)
+        dict(name="geo-hl-r3-ragged", arch="fc", obs=(8,), feats=(16, 16), K=9, A=2, B=5, n_bins=256, cql=True),
+        dict(name="geo-c51-r2", arch="fc", obs=(8,), feats=(16, 16), K=12, A=1, B=5, n_bins=256, categorical=True),
+        dict(name="geo-qr-r1", arch="fc", obs=(8,), feats=(16, 16), K=20, A=1, B=3, n_quantiles=256),
+        dict(name="geo-hl-widest", arch="fc", obs=(8,), feats=(16, 16), K=10, A=2, B=4, n_bins=248),
         # negative control: the checker must notice a tensor that was not registered
         dict(name="control-action-not-registered", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, omit="action"),
     ]
     for c in cases:
-        if which != "all" and which not in c["name"]:
+        if which != "all" and not c["name"].startswith(which):  # (a prefix: "qr-" must not take "geo-qr-r1" along)
             continue
         run_case(**c)

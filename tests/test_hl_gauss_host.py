@@ -110,6 +110,89 @@ def test_softmax_minus_p_is_the_autograd_gradient_of_the_cross_entropy():
     assert torch.allclose(out["q"], ex[torch.arange(B)[:, None], torch.arange(1, 1 + K)[None, :], torch.as_tensor(action)[:, None]])
 
 
+# ------------------------------------------------------------------ the helper's keyword arguments
+def _rows_case(seed, B, K, A, nb, n_heads):
+    rng = np.random.default_rng(seed)
+    return dict(rows=torch.tensor(rng.normal(0, 1.5, (2 * B, n_heads * A * nb)), dtype=torch.float64),
+                value_rows=torch.tensor(rng.normal(0, 1.5, (B, n_heads * A * nb)), dtype=torch.float64),
+                action=rng.integers(0, A, B), reward=rng.normal(0, 8, B), terminal=(rng.random(B) < 0.4).astype(np.uint8),
+                weights=rng.uniform(0.2, 1.7, B), discount=rng.uniform(0.3, 0.99, B))
+
+
+@pytest.mark.parametrize("A", [1, 4])
+def test_keyword_defaults_leave_the_result_unchanged_and_equal_double_q(A):
+    """With every keyword at its default the result is the bits of the call without them; selector_rows / value_rows / weights give
+    what tests/helpers/double_q.py gives with ``hist`` -- an independent writing of the same definition."""
+    from tests.helpers import double_q as dq
+
+    B, K, n_heads, nb = 6, 3, 4, 17
+    c = _rows_case(3, B, K, A, nb, n_heads)
+    args = (c["action"], c["reward"], c["terminal"], 0.97, K, 1, 0, A, nb, VMIN, VMAX, SIGMA)
+    plain = hl.hl_loss(c["rows"], *args)
+    same = hl.hl_loss(c["rows"], *args, value_rows=None, selector_rows=None, weights=None, discount=None, y=None)
+    ones = hl.hl_loss(c["rows"], *args, value_rows=c["rows"][B:], weights=np.ones(B), discount=np.full(B, 0.97), y=plain["targets"])
+    for k in ("losses", "q", "targets", "priorities", "dlogits", "ce"):
+        assert torch.equal(plain[k], same[k]) and torch.equal(plain[k], ones[k]), k
+    hist = dict(nb=nb, vmin=VMIN, vmax=VMAX, sigma=SIGMA)
+    for vr in (None, c["value_rows"]):
+        want = dq.double_q(c["rows"], c["action"], c["reward"], c["terminal"], 0.97, K, 1, 0, A, value_rows=vr, weights=c["weights"], hist=hist)
+        got = hl.hl_loss(c["rows"], *args, value_rows=vr, selector_rows=c["rows"][B:], weights=c["weights"])
+        for mine, theirs in (("targets", "targets"), ("q", "q"), ("losses", "losses"), ("priorities", "priorities"), ("dlogits", "dq")):
+            np.testing.assert_allclose(got[mine].numpy(), want[theirs], rtol=1e-13, atol=1e-15, err_msg=mine)
+        if A > 1:  # the selector bites: a* leaves the value head's own greedy action somewhere
+            assert (want["a_star"] != want["greedy"]).any()
+            assert not torch.equal(got["targets"], hl.hl_loss(c["rows"], *args, value_rows=vr)["targets"])
+
+
+def test_selector_takes_the_first_of_two_equal_expectations():
+    B, K, A, n_heads, nb = 3, 1, 3, 2, 5
+    c = _rows_case(5, B, K, A, nb, n_heads)
+    sel = c["rows"][B:].clone().reshape(B, n_heads, A, nb)
+    sel[:, 1, 0] = 0.0
+    sel[:, 1, 0, 0] = 30.0  # a poor action 0 (all mass on the lowest bin), then two bit-equal better ones
+    sel[:, 1, 2] = sel[:, 1, 1]
+    val = c["value_rows"].reshape(B, n_heads, A, nb)
+    got = hl.hl_loss(c["rows"], c["action"], c["reward"], c["terminal"], 0.9, K, 1, 0, A, nb, VMIN, VMAX, SIGMA, value_rows=c["value_rows"],
+                     selector_rows=sel.reshape(B, -1))
+    want = torch.as_tensor(c["reward"]) + (1.0 - torch.as_tensor(c["terminal"], dtype=torch.float64)) * 0.9 * hl.expectations(val[:, 0, 1], nb, VMIN, VMAX)[:, 0]
+    assert torch.allclose(got["targets"][:, 0], want, rtol=1e-14, atol=0)
+
+
+@pytest.mark.parametrize("A", [1, 4])
+def test_dlogits_is_autograd_of_the_helpers_own_loss_with_every_keyword(A):
+    B, K, n_heads, nb = 5, 2, 3, 9
+    c = _rows_case(7, B, K, A, nb, n_heads)
+    rows = c["rows"].clone().requires_grad_(True)
+    y = torch.tensor(np.random.default_rng(1).uniform(VMIN - 3, VMAX + 3, (B, K)))
+    for kw in (dict(), dict(y=y)):
+        rows.grad = None
+        out = hl.hl_loss(rows, c["action"], c["reward"], c["terminal"], 0.97, K, 1, 0, A, nb, VMIN, VMAX, SIGMA, value_rows=c["value_rows"],
+                         selector_rows=rows[B:], weights=c["weights"], discount=c["discount"], **kw)
+        out["losses"].sum().backward()
+        assert torch.allclose(rows.grad[:B], out["dlogits"], rtol=1e-12, atol=1e-15)
+        assert (rows.grad[B:] == 0).all()
+        assert torch.allclose(out["p"].sum(-1), torch.ones(B, K, dtype=torch.float64), atol=1e-12)
+    # per-row discount and y are what they say: the targets follow the discount, the projection follows y
+    nt = 1.0 - torch.as_tensor(c["terminal"], dtype=torch.float64)
+    base = hl.hl_loss(rows.detach(), c["action"], c["reward"], c["terminal"], 1.0, K, 1, 0, A, nb, VMIN, VMAX, SIGMA)
+    disc = hl.hl_loss(rows.detach(), c["action"], c["reward"], c["terminal"], 1.0, K, 1, 0, A, nb, VMIN, VMAX, SIGMA, discount=c["discount"])
+    r = torch.as_tensor(c["reward"])[:, None]
+    assert torch.allclose(disc["targets"] - r, (base["targets"] - r) * torch.as_tensor(c["discount"])[:, None] * nt[:, None], rtol=1e-13, atol=1e-15)
+    assert torch.equal(out["p"], hl.projection(y, nb, VMIN, VMAX, SIGMA)) and torch.equal(out["targets"], hl.hl_loss(
+        rows.detach(), c["action"], c["reward"], c["terminal"], 0.97, K, 1, 0, A, nb, VMIN, VMAX, SIGMA, value_rows=c["value_rows"],
+        selector_rows=rows[B:].detach(), discount=c["discount"])["targets"])
+
+
+def test_float32_evaluation_of_the_helper_stays_float32_and_close():
+    B, K, A, n_heads, nb = 4, 2, 3, 3, 64
+    c = _rows_case(9, B, K, A, nb, n_heads)
+    rows = c["rows"].float().double()
+    args = (c["action"], c["reward"].astype(np.float32), c["terminal"], 0.97, K, 1, 0, A, nb, -8.0, 8.0, 0.75 * 0.25)
+    lo, hi = hl.hl_loss(rows, *args, dtype=torch.float32), hl.hl_loss(rows, *args)
+    assert lo["dlogits"].dtype == torch.float32 and lo["losses"].dtype == torch.float32 and hi["dlogits"].dtype == torch.float64
+    assert float((lo["dlogits"].double() - hi["dlogits"]).abs().max()) < 1e-6 and float((lo["losses"].double() - hi["losses"]).abs().max()) < 1e-5
+
+
 # ------------------------------------------------------------------ C ABI, host-only
 @pytest.fixture(scope="module")
 def lib():
