@@ -883,6 +883,42 @@ int isdqn_net_ema(const isdqn_net_config* cfg, float* target, const float* onlin
  * bytes wide: there is no scalar path, a view at an odd offset is refused). */
 int isdqn_net_soft_shift(const isdqn_net_config* cfg, float* params, float tau, void* workspace, void* stream);
 
+/* Gradual magnitude pruning (Zhu & Gupta 2017; Graesser et al. 2022; Obando-Ceron et al. 2024; the behaviour of JaxPruner's GMP): a bit
+ * mask over the parameter buffer, chosen per tensor by magnitude and applied after every optimizer update; gradients and Adam moments stay
+ * dense.  The reference has no counterpart.  Built BESIDE the plan, like the resets and the soft shift: no field of isdqn_net_config, no
+ * workspace region, no launch of any existing entry point.  On the device, stream-ordered, capturable, without a host synchronisation or
+ * an allocation; integer atomics only (sums of counts and disjoint bits of a word: the same result in every order).  THE definition:
+ * Prunable tensors: every conv kernel and every Dense kernel (isdqn_tensor_info kinds 0 and 1) except the LAST Dense, in layout order (the
+ *   head blocks of the last Dense are moved by isdqn_net_shift_params / isdqn_net_soft_shift, which a per-element mask would not survive).
+ *   Only REAL elements count: out < the Flax output width, and the input lane inside its group of `in padded to 8` below the true input
+ *   width (conv: in < cin of every tap; the first Dense behind a conv torso: c < cout of every pixel; any other Dense: in < in_f; Conv_0's
+ *   [out][plane][ky][kx] form has no padded input lane).  Padding is never counted, never selected and never written.
+ * Mask: one bit per float of the parameter buffer, bit (i & 31) of uint32 word (i >> 5), set = kept; mask_words = ceil(n_param_floats /
+ *   32).  The caller initialises it to all ones.  The update rewrites the bits of real prunable elements and no other bit.
+ * Selection of tensor i with n_i real elements and n_pruned[i] = k_i: the key of an element is 0 if its mask bit says pruned, otherwise
+ *   1 + (bits of w & 0x7fffffff): float order on |w|, -0.0 as 0.0, denormals not flushed, NaN above inf.  The k_i elements with the smallest
+ *   (key, flat internal index) are pruned (bit cleared), every other real element is kept (bit set): ties go to the lower index, masks are
+ *   nested while k_i does not decrease, and the result is a pure function of (params, old mask, k).
+ * Apply: wherever a bit is clear inside [offset of the first prunable tensor, end of the last one), the master element becomes +0.0f and,
+ *   with a workspace, so does its half-group entry of the S8 weight mirror (region "wsplit": the bits isdqn_net_refresh_mirror would make
+ *   of the new master).  Nothing is loaded from the parameters; every other element, lane and moment keeps its bits.  A mirror that was
+ *   current before the call is current after it.
+ * isdqn_net_prune_layout (host arithmetic on the plan, no GPU): *n_tensors = the number of prunable tensors; infos (may be NULL to query)
+ *   receives for each of the first max_infos four int64: {index into isdqn_net_param_layout's table, offset, internal size, n_i};
+ *   *mask_words as above; *scratch_bytes = what isdqn_net_prune_update needs (per tensor four histograms of 256 uint32 and one uint32 per
+ *   chunk of 4096 floats; contents between calls do not matter).  Any output pointer may be NULL.
+ * isdqn_net_prune_update: clears the scratch, six launches of the radix select over all tensors (four digit histograms of 8 bits, the
+ *   tie counts, the mask bits), then the apply launch: mask, master and (with a workspace) mirror are final when it returns.
+ * isdqn_net_prune_apply: the apply launch alone -- the node behind every gradient step; one lane per 16-byte position, grid capped at 2048
+ *   workgroups, striding.
+ * ISDQN_ERR_UNSUPPORTED, nothing launched: the impala torso and batch_norm.  ISDQN_ERR_ARG, nothing launched: a NULL cfg / params / mask /
+ *   n_pruned / scratch; params not 16-byte aligned, mask or scratch not 4-byte aligned; a k_i outside [0, n_i]. */
+int isdqn_net_prune_layout(const isdqn_net_config* cfg, int32_t* n_tensors, int64_t* infos, int32_t max_infos, int64_t* mask_words,
+                           int64_t* scratch_bytes);
+int isdqn_net_prune_update(const isdqn_net_config* cfg, float* params, const int32_t* n_pruned, uint32_t* mask, void* scratch,
+                           void* workspace, void* stream);
+int isdqn_net_prune_apply(const isdqn_net_config* cfg, float* params, const uint32_t* mask, void* workspace, void* stream);
+
 /* Engine self-test: C[M][N] = A . B on the MFMA tile engine for every operand-layout
  * combination (a_tr/b_tr: 0 = operand stored [rows][K], 1 = stored [K][rows]).  Test hook. */
 int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int32_t a_tr,

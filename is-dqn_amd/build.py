@@ -19,6 +19,10 @@ EXTRA_SOURCES = ["conservative_kernels.hip"]
 # Further translation units of their own (tests/test_conservative_host.py holds the two lists above to what they are): compiled and linked
 # into every variant like the others; their assembly comes from emit_side_asm(), which tests/test_soft_shift_host.py lints.
 SIDE_SOURCES = ["soft_shift_kernels.hip"]
+# Gradual magnitude pruning, a translation unit of its own as well (tests/test_soft_shift_host.py holds the three lists above to what
+# they are): compiled and linked into every variant in the same loop; its assembly comes from emit_prune_asm(), which
+# tests/test_prune_host.py lints.
+PRUNE_SOURCES = ["prune_kernels.hip"]
 HEADERS = sorted(f for f in os.listdir(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")) if f.endswith(".h")) + [
     os.path.join("..", "..", "include", "isdqn_hip.h")]
 # -fno-slp-vectorize: hipcc's SLP vectoriser turns scalar fp32 epilogue math into packed v_pk_*_f32 sequences, and one of
@@ -46,7 +50,7 @@ def build(force=False, verbose=True, variant=None, defines=(), extra_flags=()):
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     objs = []
     procs = []
-    for src in SOURCES + EXTRA_SOURCES + SIDE_SOURCES:
+    for src in SOURCES + EXTRA_SOURCES + SIDE_SOURCES + PRUNE_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
@@ -94,6 +98,11 @@ def emit_side_asm(force=False, verbose=False):
     return emit_asm(force=force, verbose=verbose, sources=SIDE_SOURCES)
 
 
+def emit_prune_asm(force=False, verbose=False):
+    """emit_asm for PRUNE_SOURCES."""
+    return emit_asm(force=force, verbose=verbose, sources=PRUNE_SOURCES)
+
+
 if __name__ == "__main__":
     _variant = None
     _defs = []
@@ -105,4 +114,5 @@ if __name__ == "__main__":
     _extra = [_a for _a in sys.argv[1:] if _a.startswith("-f") or _a.startswith("-m")]
     print(build(force="--force" in sys.argv, variant=_variant, defines=_defs, extra_flags=_extra))
     if "--emit-asm" in sys.argv:
-        print("\n".join(emit_asm(force="--force" in sys.argv, verbose=True) + emit_side_asm(force="--force" in sys.argv, verbose=True)))
+        print("\n".join(emit_asm(force="--force" in sys.argv, verbose=True) + emit_side_asm(force="--force" in sys.argv, verbose=True)
+                        + emit_prune_asm(force="--force" in sys.argv, verbose=True)))

@@ -18,6 +18,7 @@
 #include "head_loss.h"
 #include "conservative.h"
 #include "soft_shift.h"
+#include "prune.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
 #include "quantile.h"
@@ -772,4 +773,90 @@ extern "C" int isdqn_net_soft_shift(const isdqn_net_config* cfg, float* params, 
     ISDQN_REQUIRE(l.w_off + (int64_t)l.out_p * l.in_p <= P.n_params && l.b_off + (int64_t)l.out_p <= P.n_params, ISDQN_ERR_SHAPE,
                   "soft head shift: the last Dense lies outside the parameter buffer");
     return launch_soft_shift(a, st);
+}
+
+// ---- gradual magnitude pruning (include/isdqn_hip.h, isdqn_net_prune_*): host code here, the kernels in prune_kernels.hip ----
+
+// the prunable tensors of a plan in layout order: every conv and Dense kernel but the last Dense's.  info_index (may be null): where
+// each of them sits in isdqn_net_param_layout's table
+static int prune_table(const isdqn_net_config* cfg, const Plan** plan_out, PruneTable& tab, int32_t* info_index) {
+    int rc;
+    const Plan* Pp = cached_plan(cfg, &rc);
+    if (!Pp) return rc;
+    const Plan& P = *Pp;
+    ISDQN_REQUIRE(cfg->arch != ISDQN_ARCH_IMPALA, ISDQN_ERR_UNSUPPORTED, "pruning is not built for the impala torso");
+    ISDQN_REQUIRE(!P.bn, ISDQN_ERR_UNSUPPORTED, "pruning is not built for batch_norm");
+    memset(&tab, 0, sizeof(tab));
+    for (int i = 0; i + 1 < P.n_layers; ++i) {
+        const Layer& l = P.L[i];
+        ISDQN_REQUIRE(tab.n < PRUNE_MAX_TENSORS && l.w_size < (1ll << 31), ISDQN_ERR_SHAPE, "pruning: too many or too large kernels");
+        PruneTensor& t = tab.t[tab.n];
+        t.offset = l.w_off;
+        t.size = (int32_t)l.w_size;
+        t.rows_real = l.out_f;
+        if (l.kind == 0) {
+            t.row_len = l.K;
+            t.period = l.is_u8 ? l.K : l.cin_p;  // Conv_0's [plane][ky][kx] rows have no padded lane
+            t.real_per = l.is_u8 ? l.K : l.cin;
+        } else {
+            const bool torso = i > 0 && P.L[i - 1].kind == 0;  // columns [pixel][c padded to 8]
+            t.row_len = l.in_p;
+            t.period = torso ? P.L[i - 1].cout_p : l.in_p;
+            t.real_per = torso ? P.L[i - 1].cout : l.in_f;
+        }
+        ISDQN_REQUIRE(l.w_off >= 0 && l.w_off + l.w_size <= P.n_params, ISDQN_ERR_SHAPE, "pruning: a kernel lies outside the parameter buffer");
+        if (info_index) {  // (for_each_param_tensor: kernel, bias and the LayerNorm pair of every layer in front)
+            int n = 0;
+            for (int j = 0; j < i; ++j) n += 2 + (P.L[j].has_ln ? 2 : 0);
+            info_index[tab.n] = n;
+        }
+        ++tab.n;
+    }
+    if ((rc = prune_table_finish(tab))) return rc;
+    *plan_out = Pp;
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_prune_layout(const isdqn_net_config* cfg, int32_t* n_tensors, int64_t* infos, int32_t max_infos, int64_t* mask_words,
+                                      int64_t* scratch_bytes) {
+    const Plan* Pp;
+    PruneTable tab;
+    int32_t index[PRUNE_MAX_TENSORS];
+    if (int rc = prune_table(cfg, &Pp, tab, index)) return rc;
+    if (n_tensors) *n_tensors = tab.n;
+    for (int i = 0; infos && i < tab.n && i < max_infos; ++i) {
+        infos[4 * i + 0] = index[i];
+        infos[4 * i + 1] = tab.t[i].offset;
+        infos[4 * i + 2] = tab.t[i].size;
+        infos[4 * i + 3] = tab.t[i].n_real;
+    }
+    if (mask_words) *mask_words = (Pp->n_params + 31) / 32;
+    if (scratch_bytes) *scratch_bytes = tab.hist_words * 4;
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_prune_update(const isdqn_net_config* cfg, float* params, const int32_t* n_pruned, uint32_t* mask, void* scratch,
+                                      void* workspace, void* stream) {
+    const Plan* Pp;
+    PruneArgs a;
+    if (int rc = prune_table(cfg, &Pp, a.tab, nullptr)) return rc;
+    ISDQN_REQUIRE(params && n_pruned && mask && scratch, ISDQN_ERR_ARG, "null pointer");
+    for (int i = 0; i < a.tab.n; ++i) a.tab.t[i].k = n_pruned[i];
+    a.p = params;
+    a.mirror = workspace != nullptr ? (float*)workspace + Pp->wsplit_off : nullptr;
+    a.mask = mask;
+    a.scratch = (uint32_t*)scratch;
+    return launch_prune_update(a, (hipStream_t)stream);
+}
+
+extern "C" int isdqn_net_prune_apply(const isdqn_net_config* cfg, float* params, const uint32_t* mask, void* workspace, void* stream) {
+    const Plan* Pp;
+    PruneArgs a;
+    if (int rc = prune_table(cfg, &Pp, a.tab, nullptr)) return rc;
+    ISDQN_REQUIRE(params && mask, ISDQN_ERR_ARG, "null pointer");
+    a.p = params;
+    a.mirror = workspace != nullptr ? (float*)workspace + Pp->wsplit_off : nullptr;
+    a.mask = const_cast<uint32_t*>(mask);
+    a.scratch = nullptr;
+    return launch_prune_apply(a, (hipStream_t)stream);
 }

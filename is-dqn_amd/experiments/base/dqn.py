@@ -80,6 +80,10 @@ def train(key, p: dict, agent, env, rb):
         if reset_frequency and step % reset_frequency == 0:
             agent.reset_parameters(**reset_kwargs(p))
             logs["reset"] = 1
+        if p.get("prune_sparsity"):
+            # Gradual pruning (-prune, not in the reference): behind ReDo and the reset, which write pruned positions -- a mask update
+            # when the step is a multiple of -prunef, else the mask applied once where one of them ran; "sparsity" in every log
+            logs.update(agent.prune_target_update(step, wrote="recycled_neurons" in logs or "reset" in logs))
         p["wandb"].log({"n_training_steps": step, **logs})
 
     # Replay ratio (-rr N > 1, not in the reference; SR-SPR, BBF): every environment step past n_initial_samples owes N gradient steps,

@@ -71,6 +71,10 @@ _ENGINE = [
     ("-resetl", "--reset_top_layers", dict(type=int, default=0, help="Number of top layers that are re-initialised fully; 0 = every Dense layer (BBF, SR-SPR). Means nothing without -reset.")),
     ("-ema", "--ema_tau", dict(type=float, default=0.0, help="EMA (Polyak) target network: target <- (1 - tau) * target + tau * online after every gradient step, on the device, instead of a copy every -tuf steps (BBF, SR-SPR: 0.005); 0 = off, in [0, 1]. DQN only: iS-DQN's target is a head of the online network, the target-free agents have none.")),
     ("-sst", "--soft_shift_tau", dict(type=float, default=0.0, help="Soft head shift of iS-DQN: after every gradient step head k <- (1 - tau) * head k + tau * head k+1 for every k < -nbi, on the device, instead of the hard shift every -tuf steps (the counterpart of -ema, whose usual 0.005 fits here too; -nbi 1 is DQN's Polyak target on a shared torso); -tuf keeps the cadence of the logs, -redo and -reset. 0 = off, in [0, 1]. iS-DQN and its analysis agent only.")),
+    ("-prune", "--prune_sparsity", dict(type=float, default=0.0, help="Gradual magnitude pruning (Zhu & Gupta 2017; Graesser et al. 2022; Obando-Ceron et al. 2024, with wide torsos such as -f 32 64 64 2048: -prune 0.95): final sparsity in [0, 1) of every conv and dense kernel but the last Dense, reached on the cubic schedule between -prunes and -prunee; the mask is chosen by magnitude on the device every -prunef steps and applied after every gradient step, gradients and Adam moments stay dense; 'sparsity' is logged at every target update. 0 = off (the calls and the bits of a run without the flag). With every agent; not with -noisy, -bn or -at impala.")),
+    ("-prunes", "--prune_start", dict(type=int, default=0, help="Gradient step at which the sparsity of -prune leaves 0; 0 <= -prunes < -prunee. Means nothing without -prune.")),
+    ("-prunee", "--prune_end", dict(type=int, default=100000, help="Gradient step from which the sparsity of -prune is the final one. Means nothing without -prune.")),
+    ("-prunef", "--prune_frequency", dict(type=int, default=0, help="Steps between two mask updates of -prune, at target updates behind -redo and -reset: a positive multiple of -tuf (0 = -tuf). Means nothing without -prune.")),
     ("-rr", "--replay_ratio", dict(type=int, default=1, help="Gradient steps per environment step past -nis (SR-SPR, BBF: 2 to 16), issued together as one captured update where the agent has one. Above 1, -tuf, -redo, -reset and the step of their logs count gradient steps, as -anneal and the -isb schedule always do. 1 = the loop without the flag. Above 1: -utd must be 1, -tuf a multiple of -rr, not with -offline.")),
     ("-wd", "--weight_decay", dict(type=float, default=0.0, help="AdamW (optax.adamw; BBF, SR-SPR: 0.1): decoupled weight decay -- every learn step also takes learning_rate * weight_decay of its value off every element of the conv and dense kernels, on the device, in every Adam kernel. 0 = off (plain Adam, the bits of a run without the flag); finite and >= 0. With every agent, torso, loss and -gc; not with -noisy.")),
     ("-wdall", "--weight_decay_all", dict(default=False, action="store_true", help="-wd also decays the biases and the LayerNorm / BatchNorm scales and biases (never the running statistics). Means nothing without -wd.")),
@@ -323,6 +327,30 @@ def check_soft_shift(p: dict, algo_name: str) -> None:
 def soft_shift_kwargs(p) -> dict:
     """The agents' soft-shift keyword from parsed parameters; without -sst the keywords are the ones they were before the flag existed."""
     return dict(soft_shift_tau=float(p["soft_shift_tau"])) if p.get("soft_shift_tau") else {}
+
+
+# (-prune, -prunes, -prunee and -prunef stay out of parameters.json like -sst)
+def check_pruning(p: dict) -> None:
+    """-prune outside [0, 1), a schedule that is not 0 <= -prunes < -prunee, a -prunef that is no positive multiple of -tuf, or -prune
+    together with -noisy, -bn or -at impala fails before anything is written, with the agents' own messages (slimdqn/_sparsity.py).
+    Without -prune the other three flags mean nothing and are not looked at."""
+    from slimdqn import _sparsity
+
+    if _sparsity.check_sparsity(p.get("prune_sparsity", 0.0)) == 0.0:
+        return
+    _sparsity.check_network(noisy=bool(p.get("noisy_nets", False)), batch_norm=bool(p.get("batch_norm", False)),
+                            architecture_type=p.get("architecture_type", "cnn"))
+    _sparsity.check_schedule(p["prune_start"], p["prune_end"])
+    _sparsity.check_period(p["prune_frequency"] or p["target_update_frequency"], p["target_update_frequency"])
+
+
+def prune_kwargs(p) -> dict:
+    """The agents' pruning keywords from parsed parameters; without -prune (or with -prune 0) the keywords are the ones they were before
+    the flag existed."""
+    if not p.get("prune_sparsity"):
+        return {}
+    return dict(prune_sparsity=float(p["prune_sparsity"]), prune_start=int(p["prune_start"]), prune_end=int(p["prune_end"]),
+                prune_period=int(p["prune_frequency"] or p["target_update_frequency"]))
 
 
 # (-rr stays out of parameters.json like -sst)

@@ -16,6 +16,7 @@ import torch
 from slimdqn import _hip
 from slimdqn import _conservative
 from slimdqn import _optimizer
+from slimdqn import _sparsity
 
 
 def _round_up(a, b):
@@ -928,6 +929,61 @@ class QNetEngine:
         elif tau == 1:
             self._mirror_holds(None)  # the hard shift's route ends by rebuilding the mirror from the new parameters
         # otherwise the raw-pointer write moved neither torch's version counter nor the relation between master and mirror
+
+    prune_mask = None     # set_pruning: int32 words of the bit mask over the parameter buffer (bit set = kept), all ones at first
+    prune_scratch = None  # set_pruning: what the selection counts in
+    prune_infos = ()      # set_pruning: per prunable tensor (index into ``infos``, offset, internal size, real element count)
+
+    def set_pruning(self) -> list:
+        """Gradual magnitude pruning (include/isdqn_hip.h, isdqn_net_prune_*) for this engine: allocates the bit mask over the parameter
+        buffer (all ones: nothing pruned) and the selection's scratch, and returns the real element count of every prunable tensor --
+        every conv and Dense kernel but the last Dense's, in layout order.  Nothing else changes: learn steps, batches and captured
+        updates are those of an engine that never heard of it until ``prune_update`` / ``prune_apply`` are called.  Calling it again
+        starts from a full mask.  Noisy engines, batch_norm and the impala torso are refused (ValueError)."""
+        _sparsity.check_network(noisy=self.noisy, batch_norm=self.batch_norm, architecture_type=self.architecture_type)
+        n, words, scratch = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        _hip.check(self.lib.isdqn_net_prune_layout(ctypes.byref(self.cfg), ctypes.byref(n), None, 0, ctypes.byref(words), ctypes.byref(scratch)),
+                   "isdqn_net_prune_layout")
+        infos = (ctypes.c_int64 * (4 * n.value))()
+        _hip.check(self.lib.isdqn_net_prune_layout(ctypes.byref(self.cfg), ctypes.byref(n), infos, n.value, None, None), "isdqn_net_prune_layout")
+        self.prune_infos = tuple(tuple(int(x) for x in infos[4 * i:4 * i + 4]) for i in range(n.value))
+        self.prune_mask = torch.full((int(words.value),), -1, dtype=torch.int32, device=self.device)
+        self.prune_scratch = torch.zeros(max(int(scratch.value) // 4, 1), dtype=torch.int32, device=self.device)
+        return [i[3] for i in self.prune_infos]
+
+    def _prune_target(self, params):
+        """(buffer, workspace pointer or 0) of a pruning call: the engine's own parameters go with their mirror."""
+        if self.prune_mask is None:
+            raise ValueError(_sparsity.PRUNE_NOT_SET_REFUSED)
+        own = params is None
+        p = self.params if own else params
+        assert p.dtype == torch.float32 and p.numel() == self.n_param_floats and p.is_contiguous() and p.device == self.params.device
+        return p, (_hip.ptr(self.workspace) if own else 0)
+
+    def prune_update(self, counts, params=None) -> None:
+        """Mask update (include/isdqn_hip.h, isdqn_net_prune_update): of every prunable tensor the ``counts[i]`` real elements of smallest
+        (already pruned, |w|, index) are pruned from here on, then the mask is applied.  ``params`` None: the engine's own parameters,
+        and the apply launch stores the weight mirror of what it wrote -- a mirror that was current stays current, one that was not stays
+        marked so.  Another buffer of the layout: the magnitudes are read there, that buffer alone is written, master only -- handing in
+        the engine's own ``params`` that way marks the mirror stale.  Stream-ordered, no host synchronisation."""
+        p, ws = self._prune_target(params)
+        if len(counts) != len(self.prune_infos) or any(int(k) != k or not 0 <= int(k) <= i[3] for k, i in zip(counts, self.prune_infos)):
+            raise ValueError(_sparsity.PRUNE_COUNTS_REFUSED)
+        k = (ctypes.c_int32 * len(self.prune_infos))(*[int(c) for c in counts])
+        _hip.check(self.lib.isdqn_net_prune_update(ctypes.byref(self.cfg), _hip.ptr(p), k, _hip.ptr(self.prune_mask), _hip.ptr(self.prune_scratch),
+                                                   ws, _hip.stream_ptr(self.device)), "isdqn_net_prune_update")
+        if params is not None:
+            self._wrote_without_mirror(params)
+        # otherwise the raw-pointer write moved neither torch's version counter nor the relation between master and mirror
+
+    def prune_apply(self, params=None) -> None:
+        """+0.0 wherever the mask says pruned (include/isdqn_hip.h, isdqn_net_prune_apply): one stream-ordered launch, the node behind
+        every gradient step.  ``params`` as in ``prune_update``."""
+        p, ws = self._prune_target(params)
+        _hip.check(self.lib.isdqn_net_prune_apply(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.prune_mask), ws, _hip.stream_ptr(self.device)),
+                   "isdqn_net_prune_apply")
+        if params is not None:
+            self._wrote_without_mirror(params)
 
     def best_action(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, idx_network: int, params=None) -> torch.Tensor:
         p = self._acting_params(params)

@@ -233,6 +233,12 @@ _SIGNATURES = {
     "isdqn_net_ema": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_float, c_void_p]),
     # soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift): cfg, params, tau, workspace or NULL, stream
     "isdqn_net_soft_shift": (c_int32, [POINTER(NetConfig), c_void_p, c_float, c_void_p, c_void_p]),
+    # gradual magnitude pruning (include/isdqn_hip.h, isdqn_net_prune_*): layout: cfg, &n_tensors, infos [n][4] int64, max_infos,
+    # &mask_words, &scratch_bytes; update: cfg, params, n_pruned, mask, scratch, workspace or NULL, stream; apply: cfg, params, mask,
+    # workspace or NULL, stream
+    "isdqn_net_prune_layout": (c_int32, [POINTER(NetConfig), POINTER(c_int32), c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
+    "isdqn_net_prune_update": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isdqn_net_prune_apply": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
     "isdqn_selftest_gemm": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],

@@ -7,7 +7,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from slimdqn import _conservative, _hip, _optimizer
+from slimdqn import _conservative, _hip, _optimizer, _sparsity
 from slimdqn._engine import NetOptions, QNetEngine, check_augment, check_noisy, check_redo
 
 
@@ -231,6 +231,8 @@ class EngineAgent:
 
     def _run_graph(self, g) -> None:
         """One replay of the captured update ``g``: the betas and the (horizon, discount) pairs of its S steps are its input."""
+        if self._prune is not None:
+            self._prune_t += g.S
         betas = self._next_betas(g.S)
         pairs = self._next_horizons(g.S, g.rb)
         g.run(betas) if pairs is None else g.run(betas, horizons=pairs[0], gammas=pairs[1])
@@ -266,7 +268,8 @@ class EngineAgent:
 
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options: NetOptions,
-                           batch_norm=False, augment_pad=0, weight_decay=0.0, weight_decay_all=False, cql_alpha=0.0):
+                           batch_norm=False, augment_pad=0, weight_decay=0.0, weight_decay_all=False, cql_alpha=0.0,
+                           prune_sparsity=0.0, prune_start=0, prune_end=0, prune_period=0):
         """``options``: what the constructor picked and checked (NetOptions.check, behind its own rules); the two rules that stand
         behind it follow here.  Every option becomes a plain attribute of the agent and goes to every engine it builds.
         ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
@@ -281,9 +284,13 @@ class EngineAgent:
         ``cql_alpha`` > 0: the conservative term of CQL(H) (Kumar et al. 2020; include/isdqn_hip.h, isdqn_batch_conservative) -- every
         loss and every learn step of every engine the agent builds adds ``cql_alpha * (logsumexp_a Q(s, a) - Q(s, a_b))`` per regressed
         head (QNetEngine.set_conservative): the offline recipe with ``n_quantiles`` is QR-DQN + CQL.  0 is off: the bits of an agent
-        built without the argument.  Negative, NaN or infinite: ValueError, before anything is built."""
+        built without the argument.  Negative, NaN or infinite: ValueError, before anything is built.
+        ``prune_sparsity`` > 0: gradual magnitude pruning (``_init_pruning`` below) from gradient step ``prune_start`` to ``prune_end``,
+        the mask updated every ``prune_period`` steps.  0 is off: the calls and the bits of an agent built without the argument."""
         check_augment(augment_pad, architecture_type)
         check_noisy(options.noisy, architecture_type, batch_norm, options.max_grad_norm)
+        self._init_pruning(prune_sparsity, prune_start, prune_end, prune_period, noisy=options.noisy, batch_norm=batch_norm,
+                           architecture_type=architecture_type)
         self.weight_decay = _optimizer.check_weight_decay(weight_decay, noisy=options.noisy)
         self.weight_decay_all = bool(weight_decay_all)
         self.cql_alpha = _conservative.check_cql_alpha(cql_alpha)
@@ -334,6 +341,12 @@ class EngineAgent:
             eng.init_params(self._seed)
         else:  # a batch of another size arrived: same parameter layout, new workspace
             eng.copy_state_from(old)
+        if self._prune_args is not None:  # (off: no buffer, no call -- the engine is the one built without the option)
+            n_real = eng.set_pruning()
+            if self._prune is None:
+                self._prune = _sparsity.Schedule(*self._prune_args, n_real)
+            if old is not None and old.prune_mask is not None:
+                eng.prune_mask.copy_(old.prune_mask)
         self._drop_graph()  # captured against the old engine's buffers
         self._engine = eng
         if self._trust_mirror is not None:
@@ -714,6 +727,79 @@ class EngineAgent:
         self._recycles += 1
         _, _, n_recycled = eng.redo(n_rows=n, tau=float(tau), fresh=fresh, **inputs)
         return [int(c) for c in n_recycled.cpu().numpy()]
+
+    # ------------------------------------------------------------------ gradual magnitude pruning
+    _prune_args = None  # (final sparsity, start, end) once the option is on; None: off, call for call
+    _prune = None       # _sparsity.Schedule of the run, made with the first engine
+    prune_period = 0    # gradient steps between two mask updates
+    _prune_t = 0        # gradient steps taken under the option: the schedule's clock
+
+    def _init_pruning(self, sparsity, start, end, period, *, noisy, batch_norm, architecture_type) -> None:
+        """Gradual magnitude pruning (Zhu & Gupta 2017; Obando-Ceron et al. 2024; include/isdqn_hip.h, isdqn_net_prune_*; the rules:
+        slimdqn/_sparsity.py).  Every conv and Dense kernel but the last Dense's is pruned by magnitude towards ``sparsity`` on the
+        cubic schedule between gradient steps ``start`` and ``end``; the mask is chosen on the device at target updates whose step is
+        a multiple of ``period`` (``prune_target_update``), and once anything is pruned every gradient step is followed by the apply
+        launch -- right behind the learn call in the eager step, one more node on the same stream in the captured one (the graph's
+        key says whether it is there: until the schedule starts the captured step is the one without the option).  Gradients and
+        Adam moments stay dense.  A target buffer (DQN) is masked at every mask update, so its zeros survive the hard copy and the
+        EMA.  Refused with noisy layers, batch_norm and the impala torso, before anything is built."""
+        if _sparsity.check_sparsity(sparsity) == 0.0:
+            return
+        _sparsity.check_network(noisy=bool(noisy), batch_norm=bool(batch_norm), architecture_type=architecture_type)
+        start, end = _sparsity.check_schedule(start, end)
+        self.prune_period = _sparsity.check_period(period, self.target_update_frequency)
+        self._prune_args = (float(sparsity), start, end)
+
+    @property
+    def prune_active(self) -> bool:
+        """Whether a gradient step is followed by the apply launch: the option is on and the last mask update pruned something."""
+        return self._prune is not None and self._prune.active
+
+    def _prune_learn(self, eng, learn=None):
+        """``learn`` (default: the engine's learn_on_batch) with the apply launch behind it on the same stream."""
+        learn = eng.learn_on_batch if learn is None else learn
+
+        def pruned(cb):
+            learn(cb)
+            eng.prune_apply()
+
+        return pruned
+
+    def _prune_step(self, kw: dict, eng) -> dict:
+        """What _graphed_update is handed (``learn`` / ``key`` / ``state``; {}: the engine's own learn call) with the apply node behind
+        the learn call and a key that says so.  Unchanged while nothing is pruned."""
+        if not self.prune_active:
+            return kw
+        return dict(kw, learn=self._prune_learn(eng, kw.get("learn")), key=(kw.get("key"), "prune"))
+
+    def _prune_eager(self, eng) -> None:
+        """Behind the learn call of an eager gradient step."""
+        if self._prune is None:
+            return
+        self._prune_t += 1
+        if self._prune.active:
+            eng.prune_apply()
+
+    def prune_target_update(self, step: int, wrote: bool = False) -> dict:
+        """Behind the -redo and -reset hooks of the target update at ``step``: a multiple of ``prune_period`` updates the mask with the
+        schedule's counts at the agent's own count of gradient steps (select, write the mask, apply: one stream-ordered call, no host
+        read) and masks the target buffer; any other target update at which a hook wrote the parameters (``wrote``) applies the mask
+        once, to the target buffer too (a reset moves it).  Returns the logs: ``sparsity``, the pruned share of all real prunable
+        elements from the host's own counts.  {} while the option is off."""
+        if self._prune is None:
+            return {}
+        eng = self._engine
+        target = getattr(self, "target_params", None)
+        target = target.tensor if target is not None and target.tensor is not eng.params else None
+        if step % self.prune_period == 0 and any(self._prune.step(self._prune_t)):
+            eng.prune_update(self._prune.counts)
+            if target is not None:
+                eng.prune_apply(params=target)  # (no workspace: the target has no persistent mirror)
+        elif wrote and self._prune.active:
+            eng.prune_apply()
+            if target is not None:
+                eng.prune_apply(params=target)
+        return {"sparsity": self._prune.sparsity}
 
     # ------------------------------------------------------------------ periodic resets
     _resets = 0  # resets done so far: selects the seed of the next fresh parameters

@@ -52,6 +52,7 @@ class AnalysisDQN(iSDQN):
                 self.params, self.target_params, self.optimizer_state, batch_samples, batch_samples_eval)
             if self.soft_shift_tau > 0.0:  # (behind the step and its diagnostics, as in iSDQN's eager step)
                 self._engine.soft_shift(self.soft_shift_tau)
+            self._prune_eager(self._engine)
             # (the step accumulates `losses` on the device as iSDQN does; the diagnostics are host sums like the reference's)
             self.cumulated_target_churns_train += churn_train
             self.cumulated_target_churns_eval += churn_eval

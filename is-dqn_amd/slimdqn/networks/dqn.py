@@ -56,6 +56,10 @@ class DQN(EngineAgent):
         weight_decay_all: bool = False,
         cql_alpha: float = 0.0,
         soft_shift_tau: float = 0.0,
+        prune_sparsity: float = 0.0,
+        prune_start: int = 0,
+        prune_end: int = 0,
+        prune_period: int = 0,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
@@ -71,7 +75,10 @@ class DQN(EngineAgent):
         ``weight_decay`` / ``weight_decay_all``: AdamW (EngineAgent._init_engine_agent) on the online parameters; the target parameters
         are never the optimizer's and never decay.
         ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent) on the online parameters' state rows.
-        ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head; the soft target here is ``ema_tau``."""
+        ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head; the soft target here is ``ema_tau``.
+        ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning) of
+        the online parameters; the target buffer is masked at every mask update, and the apply launch of a gradient step comes in front
+        of the EMA, so the target's zeros stay zero under the hard copy and under ``ema_tau``."""
         options = NetOptions.pick(locals())
         check_munchausen(double_q, munchausen_tau)  # (in front of the other rules, where this constructor has always asked it)
         options.check(architecture_type, features)
@@ -84,7 +91,8 @@ class DQN(EngineAgent):
         self.target_params = None
         self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
-                                cql_alpha=cql_alpha)
+                                cql_alpha=cql_alpha, prune_sparsity=prune_sparsity, prune_start=prune_start, prune_end=prune_end,
+                                prune_period=prune_period)
         self.target_params = self.params.copy()  # dqn.py:34
         self.target_sigma = self._engine.sigma.clone() if self.noisy else None  # (one persistent buffer, refreshed in place like the target)
         self.cumulated_loss = 0
@@ -98,22 +106,28 @@ class DQN(EngineAgent):
         if step % self.data_to_update == 0:
             target = self._target_tensor(self.target_params)
             eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
+            step_learn = lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw())
+            pruned = self.prune_active  # (the apply launch right behind the learn call, in front of the EMA; the key says it is there)
+            if pruned:
+                step_learn = self._prune_learn(eng, step_learn)
             if self.ema_tau > 0.0:
                 # the learn call and the EMA of the target behind it, enqueued on one stream: the captured step gets no new branch.
                 # (the target buffers are state of the step now: a capture's warm-up must not move them)
                 def learn(cb):
-                    eng.learn_on_batch_target(cb, target, **self._target_sigma_kw())
+                    step_learn(cb)
                     self._ema_target(eng, target)
 
-                g = self._graphed_update(replay_buffer, learn=learn, key=(target.data_ptr(), self.ema_tau),
+                key = (target.data_ptr(), self.ema_tau)
+                g = self._graphed_update(replay_buffer, learn=learn, key=(key, "prune") if pruned else key,
                                          state=[target] + ([self.target_sigma] if self.noisy else []))
             else:
-                g = self._graphed_update(replay_buffer, learn=lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw()), key=target.data_ptr())
+                g = self._graphed_update(replay_buffer, learn=step_learn, key=(target.data_ptr(), "prune") if pruned else target.data_ptr())
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
                 self._run_graph(g)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.target_params, self.optimizer_state, batch_samples)
+            self._prune_eager(self._engine)
             if self.ema_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
                 self._ema_target(self._engine, target)
             if getattr(self, "priority_writeback", False) and hasattr(replay_buffer, "update_device"):  # (as the captured step does)

@@ -68,6 +68,10 @@ class iSDQN(EngineAgent):
         weight_decay_all: bool = False,
         cql_alpha: float = 0.0,
         soft_shift_tau: float = 0.0,
+        prune_sparsity: float = 0.0,
+        prune_start: int = 0,
+        prune_end: int = 0,
+        prune_period: int = 0,
     ):
         """The option keywords from ``huber_delta`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Here ``double_q`` lets online head 1 + k pick the next action that head k values, and
@@ -76,7 +80,9 @@ class iSDQN(EngineAgent):
         ``soft_shift_tau`` > 0: the soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift) -- every gradient step is followed by
         head k <- (1 - tau) * head k + tau * head k+1 on the device (noisy: sigma likewise), in the eager step and inside the captured
         one, on the step's own stream; ``update_target_params`` then shifts nothing and only reports its logs.  0 keeps the hard shift
-        every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError."""
+        every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
+        ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning);
+        the apply launch comes behind the soft shift where both are on."""
         options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
         self.soft_shift_tau = check_soft_shift_tau(soft_shift_tau, supported=True)
@@ -94,7 +100,8 @@ class iSDQN(EngineAgent):
         self._init_engine_agent(key, observation_dim, n_actions, 1 + n_bellman_iterations, features, layer_norm, architecture_type,
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options,
                                 batch_norm=batch_norm, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
-                                cql_alpha=cql_alpha)
+                                cql_alpha=cql_alpha, prune_sparsity=prune_sparsity, prune_start=prune_start, prune_end=prune_end,
+                                prune_period=prune_period)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 
@@ -135,23 +142,27 @@ class iSDQN(EngineAgent):
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
             if self.soft_shift_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
                 self._engine.soft_shift(self.soft_shift_tau)
+            self._prune_eager(self._engine)
             if self.priority_writeback and hasattr(replay_buffer, "update_device"):
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_losses += losses` (isdqn.py:62) happens on the device inside the step
 
     def _soft_shift_step(self, replay_buffer) -> dict:
         """What _graphed_update is handed under ``soft_shift_tau`` > 0: the learn call and the soft shift behind it, enqueued on one
-        stream -- the captured step gets one more node and no new branch -- and a key that holds the tau.  {} without."""
-        if not self.soft_shift_tau > 0.0:
+        stream -- the captured step gets one more node and no new branch -- and a key that holds the tau.  {} without.  With pruning
+        active the apply launch follows as one more node (EngineAgent._prune_step)."""
+        if not (self.soft_shift_tau > 0.0 or self.prune_active):
             return {}
         eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
+        if not self.soft_shift_tau > 0.0:
+            return self._prune_step({}, eng)
         tau = self.soft_shift_tau
 
         def learn(cb):
             eng.learn_on_batch(cb)
             eng.soft_shift(tau)
 
-        return dict(learn=learn, key=("soft_shift", tau))
+        return self._prune_step(dict(learn=learn, key=("soft_shift", tau)), eng)
 
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:
