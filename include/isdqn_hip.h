@@ -626,6 +626,57 @@ typedef struct isdqn_batch_conservative {
     int32_t reserved;       /* 0 */
 } isdqn_batch_conservative;
 
+/* The batch is the first member of the struct isdqn_batch_mixture below (through its isdqn_batch_conservative). */
+#define ISDQN_BATCH_MIXTURE 16
+
+/* REM, the random ensemble mixture (Agarwal, Schuurmans, Norouzi, "An Optimistic Perspective on Offline Reinforcement Learning", ICML
+ * 2020): a DQN with H = cfg->n_heads scalar heads on one torso, trained on a random convex combination of the heads that is drawn anew
+ * for every gradient step.  THE definition.  A = n_actions; head-output rows have the layout q[row][h * A + a].
+ *
+ * The draw, isdqn_mixture_draw(n_heads, seed, draw_count, alpha, stream): 1 <= n_heads <= 1024 and no NULL pointer, else ISDQN_ERR_ARG
+ * and nothing is launched.  With c = *draw_count (device int64, read on the device when the kernel runs), for h < H:
+ *     x    = Philox4x32-10(counter = {h, 0x52454D00, lo32(c), hi32(c)}, key = {lo32(seed), hi32(seed)}), its first output word
+ *     u_h  = (float)((x >> 8) + 1) * 2^-24          exact, in (0, 1]
+ *     s    = the fp32 sum of u_h in ascending h
+ *     alpha_h = u_h / s                              an IEEE fp32 division
+ * alpha [n_heads] device floats.  The call ends by storing c + 1 the way isdqn_noisy_sample does: one thread, an ordinary store, in a
+ * launch of its own behind the reader, so a captured graph advances the draw without a second capture.  alpha depends on (seed, c, h,
+ * H) alone; H = 1 gives alpha = {1.0f}.
+ *
+ * The loss.  A call whose batch carries ISDQN_BATCH_MIXTURE regresses ONE "pair" (the loss count K is 1: losses[1], q_values[B][1],
+ * targets[B][1]) in which all H heads take part.  With g_b the row's discount (isdqn_batch_discount, else cfg->gamma_n), w_b its loss
+ * weight (isdqn_batch::loss_weights, else 1) and Q^val the value network the call uses without the flag (target_params where given,
+ * else the next-state rows of the one forward):
+ *     Qmix(x, a)  = sum_h alpha_h * Q_h(x, a)         fp32, in a fixed order, product and add rounded separately
+ *     q_b         = Qmix^online(s_b, a_b)
+ *     a*          = first argmax_a Qmix^val(s'_b, a)  (strict >, the lowest index wins);
+ *                   cfg->double_q = 1: first argmax_a of Qmix^online(s'_b, .) under the same alpha, the value read from Qmix^val at a*
+ *     target_b    = r_b + (1 - terminal_b) * g_b * Qmix^val(s'_b, a*)
+ *     d_b         = q_b - target_b
+ *     losses[0]   = (1 / B) sum_b w_b l(d_b)          l: squared error, or Huber with cfg->huber_delta > 0, as without the flag
+ *     dL/dQ_h(s_b, a_b) = fl32( alpha_h * fl32( l'(d_b) * (1 / B) * w_b ) )   for h = 0 .. H - 1, zero elsewhere
+ * The fixed order of Qmix: with G = 64 / A (integer division; 1 when A > 64), partial g < G is the sum of fl32(alpha_h * Q_h) over
+ * h = g, g + G, ... in ascending h, starting from its first product; Qmix is partial 0 + partial 1 + ... in ascending g.  priorities[b] =
+ * sqrt(l(d_b) + 1e-10), unweighted, as without the flag at K = 1; losses_accum follows losses; the head-bias gradient is the
+ * column sum of dL/dQ in ascending b.  Nothing flows through the target.  A learn step with the flag takes the generic loss and head
+ * backward, never the head chain (as with cql_alpha > 0).  With H = 1 and alpha = {1.0f} the *_target learn call leaves the bits of the
+ * same call without the flag: losses, q_values, targets, priorities, parameters, moments.
+ * As with the conservative term, isdqn_batch keeps its size: a caller hands the entry points &x.base.base.base.batch and sets
+ * ISDQN_BATCH_MIXTURE in its flags; the inner slots (discount, decay, cql_alpha) are read only under their own flags.  Without the flag
+ * nothing behind the batch is read and every bit is as before the option existed.  Honoured by learn / loss / their _target and debug
+ * forms and by isdqn_net_grad_on_batch with n_pairs <= 0; every torso those run, both precisions, dueling heads (the combined rows have
+ * the plain layout), max_grad_norm, weight decay, loss weights and discounts as without the flag.
+ * Refusals, nothing launched.  ISDQN_ERR_ARG: alpha NULL, n_mix != cfg->n_heads.  ISDQN_ERR_UNSUPPORTED: n_heads > 1024, n_bins > 0,
+ * n_quantiles > 0, munchausen_tau > 0, batch_norm, ISDQN_BATCH_CONSERVATIVE with cql_alpha > 0 (a conservative term on the mixture is a
+ * follow-up), isdqn_net_grad_on_batch with n_pairs > 0, isdqn_noisy_learn_on_batch. */
+typedef struct isdqn_batch_mixture {
+    isdqn_batch_conservative base; /* base.base.base.batch.flags carries ISDQN_BATCH_MIXTURE */
+    const float* alpha;            /* [n_mix] device floats: the step's mixture weights (isdqn_mixture_draw) */
+    int32_t n_mix;                 /* == cfg->n_heads */
+    int32_t reserved;              /* 0 */
+} isdqn_batch_mixture;
+int isdqn_mixture_draw(int32_t n_heads, uint64_t seed, int64_t* draw_count, float* alpha, void* stream);
+
 /* DQNNet.apply on `n_rows` observations (dqn.py:47-103) -> q [n_rows][n_heads*n_actions].
  * cnn: image j reads frame_ids[j*stack .. j*stack+stack-1]; fc: obs [n_rows][obs_c]. */
 int isdqn_net_forward(const isdqn_net_config* cfg, const float* params, const uint8_t* frames, int64_t frame_stride,
@@ -698,7 +749,11 @@ int isdqn_net_best_action(const isdqn_net_config* cfg, const float* params, cons
 
 /* best_action for `n_rows` observations at once (vectorised host environments: one forward, one argmax launch):
  * out_actions[i] = argmax_a of online head idx_networks[i] (device int32 arrays) of observation i.  n_rows <= 2 * batch_size.
- * flags: ISDQN_BATCH_MIRROR_CURRENT when the caller knows the workspace's weight mirror matches `params`. */
+ * flags: ISDQN_BATCH_MIRROR_CURRENT when the caller knows the workspace's weight mirror matches `params`;
+ * ISDQN_ACT_MEAN_HEADS: out_actions[i] = first argmax_a of sum_h Q_h(row i, a) over all n_heads heads, the sum in fp32 in ascending h,
+ * read from the "q" rows (REM's evaluation policy is the head average, and the sum has its argmax); idx_networks is ignored and may
+ * be NULL. */
+#define ISDQN_ACT_MEAN_HEADS 32
 int isdqn_net_best_actions(const isdqn_net_config* cfg, const float* params, const uint8_t* frames, int64_t frame_stride,
                            const int32_t* frame_ids, const float* obs, int32_t n_rows, const int32_t* idx_networks,
                            int32_t* out_actions, int32_t flags, void* workspace, void* stream);

@@ -70,6 +70,8 @@ static void head_chain_plan(LearnCtx& c, bool plan_heads) {
     if (P.dueling) return;
     // (the conservative term too: its dL/dq is dense over the actions, the chain exploits one non-zero per row and pair)
     if (c.cql_alpha > 0.f) return;
+    // (the mixture too: H non-zeros per row of dL/dq, and a loss kernel of its own)
+    if (c.mixture) return;
     if (!(c.update() && plan_heads && !hc_disabled && c.target_params == nullptr && P.head_nb == 0 && P.n_layers >= 2 && hid.kind == 1 &&
           !hid.is_head && hid.has_relu && hid.out_p <= HC_THREADS * HC_MAX_COLS && hid.out_p % 8 == 0))
         return;
@@ -611,6 +613,21 @@ static int learn_optimizer(const LearnCtx& c, const BackwardSchedule& sched, con
     return ISDQN_OK;
 }
 
+// What a call that carries ISDQN_BATCH_MIXTURE must be (include/isdqn_hip.h, isdqn_batch_mixture: the refusals, in this order)
+static int check_mixture(const Plan& P, const LearnCall& call) {
+    const isdqn_net_config* cfg = call.cfg;
+    ISDQN_REQUIRE(call.mix_alpha != nullptr, ISDQN_ERR_ARG, "isdqn_batch_mixture: null alpha");
+    ISDQN_REQUIRE(call.n_mix == cfg->n_heads, ISDQN_ERR_ARG, "isdqn_batch_mixture: n_mix must equal cfg->n_heads");
+    ISDQN_REQUIRE(cfg->n_heads <= MIX_MAX_HEADS, ISDQN_ERR_UNSUPPORTED, "the mixture is built for at most 1024 heads");
+    ISDQN_REQUIRE(cfg->n_bins == 0, ISDQN_ERR_UNSUPPORTED, "the mixture on histogram heads is not built (scalar heads only)");
+    ISDQN_REQUIRE(cfg->n_quantiles == 0, ISDQN_ERR_UNSUPPORTED, "the mixture on quantile heads is not built (scalar heads only)");
+    ISDQN_REQUIRE(!(cfg->munchausen_tau > 0.f), ISDQN_ERR_UNSUPPORTED, "the mixture with Munchausen targets is not built");
+    ISDQN_REQUIRE(!P.bn, ISDQN_ERR_UNSUPPORTED, "the mixture on BatchNorm networks is not built");
+    ISDQN_REQUIRE(!(call.cql_alpha > 0.f), ISDQN_ERR_UNSUPPORTED, "a conservative term on the mixture is a follow-up");
+    ISDQN_REQUIRE(call.sel.K <= 0, ISDQN_ERR_UNSUPPORTED, "the mixture regresses all heads: isdqn_net_grad_on_batch with n_pairs > 0 is refused");
+    return ISDQN_OK;
+}
+
 // (`call`: by value -- the moments of a gradient-only pass, the resolved heads and the destinations of q_values / targets are filled in here)
 static int learn_or_loss(LearnCall call) {
     const isdqn_net_config* cfg = call.cfg;
@@ -643,6 +660,10 @@ static int learn_or_loss(LearnCall call) {
         ISDQN_REQUIRE(call.target_params == nullptr || !P.munchausen, ISDQN_ERR_UNSUPPORTED,
                       "BatchNorm networks: Munchausen targets with separate target parameters are not defined (no statistics for a target "
                       "forward of the states)");
+    }
+    if (call.mixture) {  // (in front of the first launch: a refused call launches nothing)
+        if ((rc = check_mixture(P, call))) return rc;
+        call.sel = HeadSel{0, 0, 1};  // one regressed "pair": the mixture of all heads on the mixture of all heads
     }
     const bool plan_heads = call.sel.K <= 0;
     rc = resolve_heads(P, call.sel);

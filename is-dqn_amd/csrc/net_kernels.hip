@@ -19,6 +19,7 @@
 #include "conservative.h"
 #include "soft_shift.h"
 #include "prune.h"
+#include "mixture.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
 #include "quantile.h"
@@ -183,6 +184,7 @@ static LearnCall learn_call(const isdqn_net_config* cfg, LearnMode mode, const f
     // (the loss-only and the gradient-only calls update nothing: a decay behind their batch is not read)
     if (mode == LearnMode::Learn) batch_decay(batch, &c.weight_decay, &c.decay_kinds);
     c.cql_alpha = batch_conservative(batch);  // (a loss term: every mode takes it)
+    c.mixture = batch_mixture(batch, &c.mix_alpha, &c.n_mix);  // (and so is the mixture)
     return c;
 }
 
@@ -306,7 +308,7 @@ extern "C" int isdqn_net_best_actions(const isdqn_net_config* cfg, const float* 
                                       void* stream) {
     Inference c;
     int rc = c.begin(cfg, frames, frame_stride, frame_ids, obs, workspace, stream, [&](const Plan& P) -> int {
-        ISDQN_REQUIRE(params && idx_networks && out_actions && workspace, ISDQN_ERR_ARG, "null pointer");
+        ISDQN_REQUIRE(params && (idx_networks || (flags & ISDQN_ACT_MEAN_HEADS)) && out_actions && workspace, ISDQN_ERR_ARG, "null pointer");
         ISDQN_REQUIRE(n_rows >= 1 && n_rows <= P.N2, ISDQN_ERR_SHAPE, "n_rows must be in [1, 2 * batch_size] (workspace rows)");
         return ISDQN_OK;
     });
@@ -318,8 +320,11 @@ extern "C" int isdqn_net_best_actions(const isdqn_net_config* cfg, const float* 
     if (rc) return rc;
     rc = head_expect(P, ws, n_rows, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, st, ws + P.q_off, n_rows, P.nha_p, P.n_actions,
-                       P.oh, P.K, idx_networks, out_actions);
+    if (flags & ISDQN_ACT_MEAN_HEADS)  // the head average's greedy action (mixture.h): every head, idx_networks is not read
+        return launch_argmax_mean(ws + P.q_off, n_rows, P.nha_p, P.n_actions, P.n_heads, out_actions, st);
+    else
+        hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, st, ws + P.q_off, n_rows, P.nha_p, P.n_actions,
+                           P.oh, P.K, idx_networks, out_actions);
     ISDQN_HIP_CHECK(hipGetLastError());
     return ISDQN_OK;
 }
@@ -606,6 +611,7 @@ extern "C" int isdqn_noisy_learn_on_batch(const isdqn_net_config* cfg, float* mu
         ISDQN_REQUIRE(weight_decay == 0.f, ISDQN_ERR_UNSUPPORTED, "weight decay under NoisyNet exploration is not built");
     }
     if ((rc = check_conservative(batch_conservative(batch)))) return rc;  // (in front of the first launch)
+    ISDQN_REQUIRE(!(batch->flags & ISDQN_BATCH_MIXTURE), ISDQN_ERR_UNSUPPORTED, "the mixture under NoisyNet exploration is not built");
     NoisyTable tab;
     noisy_tables(P, &tab, nullptr);
     float* ws = (float*)workspace;
@@ -859,4 +865,11 @@ extern "C" int isdqn_net_prune_apply(const isdqn_net_config* cfg, float* params,
     a.mask = const_cast<uint32_t*>(mask);
     a.scratch = nullptr;
     return launch_prune_apply(a, (hipStream_t)stream);
+}
+
+// ---- random ensemble mixture (mixture.h, mixture_kernels.hip; include/isdqn_hip.h, isdqn_mixture_draw / isdqn_batch_mixture) ----
+extern "C" int isdqn_mixture_draw(int32_t n_heads, uint64_t seed, int64_t* draw_count, float* alpha, void* stream) {
+    ISDQN_REQUIRE(n_heads >= 1 && n_heads <= MIX_MAX_HEADS, ISDQN_ERR_ARG, "isdqn_mixture_draw: n_heads must be in [1, 1024]");
+    ISDQN_REQUIRE(draw_count != nullptr && alpha != nullptr, ISDQN_ERR_ARG, "null pointer");
+    return launch_mixture_draw((int)n_heads, seed, draw_count, alpha, (hipStream_t)stream);
 }

@@ -591,6 +591,9 @@ struct LearnCall {
     int32_t decay_kinds = 0;   // bit k: tensors of isdqn_tensor_info::kind k decay
     float wd(int kind) const { return ((decay_kinds >> kind) & 1) ? weight_decay : 0.f; }  // what an optimizer entry of that kind carries
     float cql_alpha = 0.f;     // the conservative term (isdqn_batch_conservative, read by learn_call in every mode; 0: none, nothing launched)
+    bool mixture = false;      // the call carries ISDQN_BATCH_MIXTURE (isdqn_batch_mixture, read by learn_call in every mode; mixture.h)
+    const float* mix_alpha = nullptr;  // ... its [n_mix] device weights, checked by check_mixture (learn_step.h)
+    int32_t n_mix = 0;
     bool learn() const { return mode != LearnMode::Loss; }  // a backward pass follows the loss
     bool update() const { return mode == LearnMode::Learn; }
 };
@@ -681,6 +684,14 @@ static inline float batch_conservative(const isdqn_batch* batch) {
     const bool has = batch != nullptr && (batch->flags & ISDQN_BATCH_CONSERVATIVE);
     return has ? reinterpret_cast<const isdqn_batch_conservative*>(batch)->cql_alpha : 0.f;
 }
+// The mixture weights behind a batch that says it has them (include/isdqn_hip.h, isdqn_batch_mixture); unchecked (check_mixture).
+static inline bool batch_mixture(const isdqn_batch* batch, const float** alpha, int32_t* n_mix) {
+    const bool has = batch != nullptr && (batch->flags & ISDQN_BATCH_MIXTURE);
+    const isdqn_batch_mixture* m = reinterpret_cast<const isdqn_batch_mixture*>(batch);
+    *alpha = has ? m->alpha : nullptr;
+    *n_mix = has ? m->n_mix : 0;
+    return has;
+}
 static int check_conservative(float cql_alpha) {
     ISDQN_REQUIRE(cql_alpha >= 0.f && cql_alpha <= 3.4028234e38f, ISDQN_ERR_ARG, "cql_alpha must be finite and >= 0");  // (NaN fails both)
     return ISDQN_OK;
@@ -745,6 +756,10 @@ static int loss_and_finalize(const Plan& P, const LearnCall& c, bool double_q = 
         with_nt([&](auto nt) { launch(c51_loss_kernel<decltype(nt)::value>, C51_THREADS, dl_bytes); });
     else if (R)
         launch(hl_loss_kernel, 256, dl_bytes);
+    else if (c.mixture)  // random ensemble mixture (mixture.h): K = 1, every head takes part under c.mix_alpha (mixture_kernels.hip)
+    {
+        if (int rc = launch_mix_td(a, n_blk, c.mix_alpha, (int)c.n_mix, c.st)) return rc;
+    }
     else
         launch(td_kernel, 256, 2 * TD_ROWS * K * sizeof(float));
     ISDQN_HIP_CHECK(hipGetLastError());

@@ -320,15 +320,7 @@ __global__ __launch_bounds__(256) void ln_bwd_wide_kernel(const float* __restric
 // (pitch sq_pitch; they may come from another forward than the value rows); null: the max form.  `mq` != null: Munchausen targets
 // (munchausen.h) -- the value head th + k (mh + k in `mq`) of the STATE rows `mq` (pitch mq_pitch; rows [0, B) of `q`, or the target
 // network's own rows) supplies the bonus, and the bootstrap value is the soft value of the value rows; null: off.
-// Per-element loss and its derivative w.r.t. q for d = q - target: squared error (the reference, isdqn.py:102) or, with
-// huber_delta > 0, the Huber loss (0.5 d^2 inside, delta (|d| - delta / 2) outside; derivative clip(d, -delta, delta)).
-__device__ __forceinline__ float td_loss(float d, float huber_delta) {
-    const float a = fabsf(d);
-    return huber_delta > 0.f ? (a <= huber_delta ? 0.5f * d * d : huber_delta * (a - 0.5f * huber_delta)) : d * d;
-}
-__device__ __forceinline__ float td_dloss(float d, float huber_delta) {
-    return huber_delta > 0.f ? fminf(fmaxf(d, -huber_delta), huber_delta) : 2.f * d;
-}
+#include "td_loss.h"  // td_loss / td_dloss, shared with mix_td_kernel (mixture_kernels.hip)
 // first index attaining the maximum of v[0..n): strict >, the lowest index wins (argmax_kernel's rule)
 __device__ __forceinline__ int argmax_first(const float* v, int n) {
     int best = 0;

@@ -79,6 +79,7 @@ _ENGINE = [
     ("-wd", "--weight_decay", dict(type=float, default=0.0, help="AdamW (optax.adamw; BBF, SR-SPR: 0.1): decoupled weight decay -- every learn step also takes learning_rate * weight_decay of its value off every element of the conv and dense kernels, on the device, in every Adam kernel. 0 = off (plain Adam, the bits of a run without the flag); finite and >= 0. With every agent, torso, loss and -gc; not with -noisy.")),
     ("-wdall", "--weight_decay_all", dict(default=False, action="store_true", help="-wd also decays the biases and the LayerNorm / BatchNorm scales and biases (never the running statistics). Means nothing without -wd.")),
     ("-cql", "--cql_alpha", dict(type=float, default=0.0, help="CQL(H) (Kumar et al. 2020; offline QR-DQN + CQL: -qr -nq 200 -hd 1 -cql 1.0 -offline DIR): every loss also carries cql_alpha * (logsumexp_a Q(s, a) - Q(s, a_b)) per regressed head, on the device, its gradient dense over the actions. 0 = off (the bits of a run without the flag); finite and >= 0. With every agent, torso, head type, target flag, -gc, -noisy, -wd, -per, -aug and -anneal.")),
+    ("-rem", "--rem_heads", dict(type=int, default=0, help="REM, the random ensemble mixture (Agarwal et al. 2020; offline: dqn.py ... -rem 200 -hd 1 -offline DIR): a DQN with this many heads on one torso, trained on a random convex combination of the heads drawn anew on the device for every gradient step, acting on the head average. 0 = off (a plain DQN, the bits of a run without the flag); at most 1024. dqn.py only; with -dq, -hd, -duel, -ema, -reset, -redo, -prune, -wd, -gc, -per / -isb, -anneal, -aug, -rr, -offline and -evals; not with -noisy, -hl, -qr, -mq or -cql.")),
     ("-logrb", "--log_replay", dict(type=str, default=None, help="Directory that receives every transition handed to the replay, in arrival order, as shard_%%06d.npz files (experiments/base/offline.py: TransitionLog) -- the dataset of a later -offline run. Single environment only: refused with -nenvs > 1.")),
     ("-offline", "--offline_dir", dict(type=str, default=None, help="Train from the transition log in this directory instead of an environment: the replay is filled once through its own add, then every epoch issues -ntspe gradient steps, with the target updates and their hooks (ReDo, resets, anneal, logs) counted in gradient steps. -utd must be 1; a dataset larger than -rbc is refused. Offline QR-DQN + CQL: -qr -nq 200 -hd 1 -cql 1.0 -offline DIR.")),
     ("-evals", "--evaluation_steps", dict(type=int, default=0, help="With -offline: environment steps of evaluation behind every epoch (epsilon = -ee, the running episode is finished, nothing enters the replay); 0 = none, and no environment is built.")),
@@ -403,6 +404,31 @@ def conservative_kwargs(p) -> dict:
     """The agents' keyword of the conservative term from parsed parameters; without -cql the keywords are the ones they were before the
     flag existed."""
     return dict(cql_alpha=float(p["cql_alpha"])) if p.get("cql_alpha") else {}
+
+
+# (-rem stays out of parameters.json like -cql)
+REM_ALGOS = ("dqn",)
+
+
+def check_rem(p: dict, algo_name: str) -> None:
+    """-rem outside [0, 1024], > 0 on any entry point but dqn.py, or together with -noisy, -hl, -qr, -mq or -cql fails before anything
+    is written, with the agents' own messages (slimdqn/_mixture.py)."""
+    from slimdqn import _mixture
+
+    H = _mixture.check_rem_heads(p.get("rem_heads", 0))
+    if H == 0:
+        return
+    if algo_name not in REM_ALGOS:
+        raise ValueError(_mixture.REM_AGENT_REFUSED)
+    _mixture.check_rem_heads(H, noisy=bool(p.get("noisy_nets", False)), n_bins=1 if p.get("histogram_loss") else 0,
+                             n_quantiles=1 if p.get("quantile_regression") else 0, munchausen_tau=1.0 if p.get("munchausen") else 0.0,
+                             cql_alpha=float(p.get("cql_alpha", 0.0) or 0.0))
+
+
+def rem_kwargs(p) -> dict:
+    """The DQN agent's mixture keyword from parsed parameters; without -rem the keywords are the ones they were before the flag
+    existed."""
+    return dict(rem_heads=int(p["rem_heads"])) if p.get("rem_heads") else {}
 
 
 # (-logrb, -offline and -evals stay out of parameters.json like -cql)

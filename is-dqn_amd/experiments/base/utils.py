@@ -46,6 +46,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     parser_argument.check_replay_ratio(p)
     parser_argument.check_weight_decay(p)
     parser_argument.check_conservative(p)
+    parser_argument.check_rem(p, algo_name)
     parser_argument.check_offline(p)
     parser_argument.check_anneal(p)
     parser_argument.check_dueling(p)

@@ -15,6 +15,7 @@ import torch
 
 from slimdqn import _hip
 from slimdqn import _conservative
+from slimdqn import _mixture
 from slimdqn import _optimizer
 from slimdqn import _sparsity
 
@@ -736,10 +737,38 @@ class QNetEngine:
         isdqn_batch_conservative: the definition).  q_values, targets and priorities stay those of the configured loss.  0 is off: the
         batches and the bits of an engine that never heard of it.  The weight travels in every batch ``make_batch`` builds from here on;
         every captured update of this engine is dropped and captures again at its next run, as ``set_weight_decay`` does.  Every
-        torso, head type, target form and the noisy learn step take it; a learn step on scalar heads leaves the head chain."""
-        self.cql_alpha = _conservative.check_cql_alpha(alpha)
+        torso, head type, target form and the noisy learn step take it; a learn step on scalar heads leaves the head chain.  Refused
+        with alpha > 0 on an engine with a mixture (``set_mixture``): ValueError."""
+        alpha = _conservative.check_cql_alpha(alpha)
+        if alpha > 0.0 and self.mix_alpha is not None:  # (the library refuses the two together at every call: refuse them here)
+            raise ValueError(_mixture.REM_CQL_REFUSED)
+        self.cql_alpha = alpha
         for g in list(self._captured or ()):
             g.destroy()
+
+    mix_alpha = None  # float32 [n_heads]: the mixture weights of the following loss / gradient / learn calls (set_mixture); None: none
+    mix_count = None  # int64 [1]: draws so far (selects the next draw; mixture_draw advances it on the device)
+
+    def set_mixture(self, seed: int) -> None:
+        """REM (Agarwal et al. 2020) for the following calls of this engine: every loss, gradient and learn call regresses the mixture
+        ``sum_h alpha_h Q_h`` of all ``n_heads`` heads on the same mixture of the value network and spreads the one TD error over the
+        heads (include/isdqn_hip.h, isdqn_batch_mixture: the definition).  Allocates ``mix_alpha`` -- uniform, 1 / n_heads, until the
+        first draw -- and the draw count; ``mixture_draw`` draws the next weights.  The weights travel in every batch ``make_batch``
+        builds from here on; every captured update of this engine is dropped, as ``set_conservative`` does.  Noisy engines, histogram
+        and quantile heads, Munchausen targets and a conservative term are refused (ValueError)."""
+        _mixture.check_rem_heads(self.n_heads, noisy=self.noisy, n_bins=self.n_bins, n_quantiles=self.n_quantiles,
+                                 munchausen_tau=self.munchausen_tau, cql_alpha=self.cql_alpha)
+        self.mix_seed = _mixture.mixture_seed(seed)
+        with torch.cuda.device(self.device):
+            self.mix_alpha = torch.full((self.n_heads,), 1.0 / self.n_heads, dtype=torch.float32, device=self.device)
+            self.mix_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        for g in list(self._captured or ()):
+            g.destroy()
+
+    def mixture_draw(self) -> None:
+        """The next mixture weights into ``mix_alpha`` on the current stream; the device count advances by one (nothing is read back)."""
+        _hip.check(self.lib.isdqn_mixture_draw(self.n_heads, self.mix_seed, _hip.ptr(self.mix_count), _hip.ptr(self.mix_alpha),
+                                               _hip.stream_ptr(self.device)), "isdqn_mixture_draw")
 
     # ------------------------------------------------------------------ C-ABI calls
     def make_batch(self, *, frames=None, frame_stride=0, frame_ids=None, state=None, next_state=None, action=None, reward=None, terminal=None,
@@ -767,6 +796,14 @@ class QNetEngine:
             if self.weight_decay > 0.0:
                 b.weight_decay, b.decay_kinds = inner.weight_decay, inner.decay_kinds
             b.cql_alpha = self.cql_alpha
+        if self.mix_alpha is not None:  # (isdqn_batch_mixture: the structs above, then the weights; the inner slots are read with their own flags)
+            inner, b = b, _hip.BatchMixture()
+            b.flags = inner.flags | _hip.BATCH_MIXTURE
+            if self.weight_decay > 0.0:
+                b.weight_decay, b.decay_kinds = inner.weight_decay, inner.decay_kinds
+            if self.cql_alpha > 0.0:
+                b.cql_alpha = inner.cql_alpha
+            b.alpha, b.n_mix = _hip.ptr(self.mix_alpha), self.n_heads
         b.priorities_ready = None if priorities_ready is None else int(priorities_ready.cuda_event)
         b.B = self.batch_size
         b.frames = _hip.ptr(frames)
@@ -1160,11 +1197,18 @@ class QNetEngine:
         self._mirror_version = self.params._version if params is None and not self.noisy else None  # (noisy: the mirror holds eff)
         self._mirror_ptr = self.params.data_ptr()
 
-    def best_actions(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, idx_networks: torch.Tensor, params=None,
-                     out: torch.Tensor | None = None, mirror_current: bool | None = None) -> torch.Tensor:
+    def best_actions(self, *, frames=None, frame_stride=0, frame_ids=None, obs=None, idx_networks: torch.Tensor | None = None, params=None,
+                     out: torch.Tensor | None = None, mirror_current: bool | None = None, mean_heads: bool = False,
+                     n_rows: int | None = None) -> torch.Tensor:
         """Greedy actions of n observations in one forward (isdqn.py:127-135 per row): int32 device tensor [n].
-        ``mirror_current``: None = decided by the engine's bookkeeping; a captured graph fixes it at capture time."""
-        n = int(idx_networks.numel())
+        ``mirror_current``: None = decided by the engine's bookkeeping; a captured graph fixes it at capture time.
+        ``mean_heads``: the greedy action of the sum of all heads (ISDQN_ACT_MEAN_HEADS: REM's evaluation policy); ``idx_networks`` is
+        then not read and may be None, with ``n_rows`` (or ``out``) giving the number of observations."""
+        if idx_networks is not None:
+            n = int(idx_networks.numel())
+        else:
+            assert mean_heads and (n_rows is not None or out is not None), "best_actions without idx_networks: mean_heads and n_rows"
+            n = int(n_rows) if n_rows is not None else int(out.numel())
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=self.device)
         p = self.params if params is None else params
@@ -1172,7 +1216,7 @@ class QNetEngine:
             mirror_current = self._mirror_is_current(params)
         if self.noisy and params is None:  # one draw serves all rows; compose leaves the mirror of eff in the workspace
             p, mirror_current = self.compose(), True
-        flags = _hip.BATCH_MIRROR_CURRENT if mirror_current else 0
+        flags = (_hip.BATCH_MIRROR_CURRENT if mirror_current else 0) | (_hip.ACT_MEAN_HEADS if mean_heads else 0)
         _hip.check(
             self.lib.isdqn_net_best_actions(
                 ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(frames), int(frame_stride), _hip.ptr(frame_ids), _hip.ptr(obs), n,

@@ -21,6 +21,8 @@ BATCH_MIRROR_CURRENT = 1  # include/isdqn_hip.h: ISDQN_BATCH_MIRROR_CURRENT
 BATCH_DISCOUNT = 2  # include/isdqn_hip.h: ISDQN_BATCH_DISCOUNT
 BATCH_WEIGHT_DECAY = 4  # include/isdqn_hip.h: ISDQN_BATCH_WEIGHT_DECAY
 BATCH_CONSERVATIVE = 8  # include/isdqn_hip.h: ISDQN_BATCH_CONSERVATIVE
+BATCH_MIXTURE = 16  # include/isdqn_hip.h: ISDQN_BATCH_MIXTURE
+ACT_MEAN_HEADS = 32  # include/isdqn_hip.h: ISDQN_ACT_MEAN_HEADS (isdqn_net_best_actions' flags)
 DECAY_KINDS_KERNELS, DECAY_KINDS_ALL = 0x03, 0x7F  # include/isdqn_hip.h: ISDQN_DECAY_KINDS_* (bit k: TensorInfo.kind k decays)
 TREE_MAX_BATCH = 4096
 ARCH_CNN, ARCH_FC, ARCH_IMPALA = 0, 1, 2
@@ -112,6 +114,10 @@ class BatchDecay(BatchDiscount):  # isdqn_batch_decay: the batch (and its discou
 
 class BatchConservative(BatchDecay):  # isdqn_batch_conservative: the batch (its discount and decay slots), then what flags & BATCH_CONSERVATIVE announces
     _fields_ = [("cql_alpha", c_float), ("reserved", c_int32)]  # the weight of the conservative term (include/isdqn_hip.h)
+
+
+class BatchMixture(BatchConservative):  # isdqn_batch_mixture: the batch (its discount, decay and cql slots), then what flags & BATCH_MIXTURE announces
+    _fields_ = [("alpha", c_void_p), ("n_mix", c_int32), ("reserved2", c_int32)]  # float32 [n_mix] mixture weights (include/isdqn_hip.h)
 
 
 _SIGNATURES = {
@@ -239,6 +245,8 @@ _SIGNATURES = {
     "isdqn_net_prune_layout": (c_int32, [POINTER(NetConfig), POINTER(c_int32), c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
     "isdqn_net_prune_update": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isdqn_net_prune_apply": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
+    # random ensemble mixture (include/isdqn_hip.h, isdqn_mixture_draw): n_heads, seed, draw count, alpha, stream
+    "isdqn_mixture_draw": (c_int32, [c_int32, c_uint64, c_void_p, c_void_p, c_void_p]),
     "isdqn_selftest_gemm": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],

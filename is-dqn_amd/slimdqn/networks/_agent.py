@@ -7,7 +7,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from slimdqn import _conservative, _hip, _optimizer, _sparsity
+from slimdqn import _conservative, _hip, _mixture, _optimizer, _sparsity
 from slimdqn._engine import NetOptions, QNetEngine, check_augment, check_noisy, check_redo
 
 
@@ -323,6 +323,12 @@ class EngineAgent:
         if self.augment_pad:  # (off: no buffer, no launch -- the agent is the one built without the argument)
             self._aug_state()
 
+    rem_heads = 0  # REM (DQN's ``rem_heads``): the engine has this many heads and a mixture; acting is on the head average.  0: off
+
+    def _act_kw(self) -> dict:
+        """What the acting calls add to ``best_actions``: nothing, or the head average of a mixture agent."""
+        return dict(mean_heads=True) if self.rem_heads else {}
+
     # ------------------------------------------------------------------ engine management
     def _make_engine(self, batch_size: int, init: bool = False) -> None:
         old = self._engine
@@ -337,6 +343,10 @@ class EngineAgent:
             eng.set_weight_decay(self.weight_decay, self.weight_decay_all)
         if self.cql_alpha > 0.0:
             eng.set_conservative(self.cql_alpha)
+        if self.rem_heads:  # (off: no buffer, no launch -- the engine is the one built without the option)
+            eng.set_mixture(_mixture.mixture_seed(self._seed))
+            if old is not None and old.mix_count is not None:
+                eng.mix_count.copy_(old.mix_count)
         if init:
             eng.init_params(self._seed)
         else:  # a batch of another size arrived: same parameter layout, new workspace
@@ -576,7 +586,7 @@ class EngineAgent:
                 g["dev_in"].copy_(g["pin_in"], non_blocking=True)
                 ring["planes"][slot].copy_(g["dev_in"][:hw])
                 eng.best_actions(frames=ring["planes"], frame_stride=hw, frame_ids=ids, idx_networks=idx_dev, out=g["out"],
-                                 mirror_current=current)
+                                 mirror_current=current, **self._act_kw())
                 g["pin_out"].copy_(g["out"], non_blocking=True)
 
             torch.cuda.synchronize(eng.device)
@@ -606,7 +616,8 @@ class EngineAgent:
         heads = getattr(self, "_head_ids", None)
         if heads is None or heads.device != eng.device:
             heads = self._head_ids = torch.arange(max(self._n_heads, 1), dtype=torch.int32, device=eng.device)
-        out = eng.best_actions(idx_networks=heads[idx_network : idx_network + 1], params=self._bind(params), **self._obs_to_device(state))
+        out = eng.best_actions(idx_networks=heads[idx_network : idx_network + 1], params=self._bind(params), **self._obs_to_device(state),
+                               **self._act_kw())
         return int(out.item())
 
     def _best_actions(self, params, states, idx_networks) -> np.ndarray:
@@ -614,7 +625,7 @@ class EngineAgent:
         eng = self._engine
         self._noisy_act(params)
         idx = torch.as_tensor(np.array(idx_networks, dtype=np.int32)).to(eng.device)
-        out = eng.best_actions(idx_networks=idx, params=self._bind(params), **self._states_to_device(states))
+        out = eng.best_actions(idx_networks=idx, params=self._bind(params), **self._states_to_device(states), **self._act_kw())
         return out.cpu().numpy()
 
     def _best_actions_planes(self, params, planes: np.ndarray, rows: np.ndarray, idx_networks, wait: bool = True):
@@ -641,7 +652,7 @@ class EngineAgent:
         hs[n * stack : n * stack + m] = np.asarray(idx_networks, np.int32)
         v["small"].copy_(v["host_small"], non_blocking=True)
         eng.best_actions(frames=v["dev"], frame_stride=hw, frame_ids=v["small"][: m * stack], idx_networks=v["small"][n * stack : n * stack + m],
-                         params=self._bind(params), out=v["out"][:m])
+                         params=self._bind(params), out=v["out"][:m], **self._act_kw())
         v["host_out"][:m].copy_(v["out"][:m], non_blocking=True)
         ev = v.setdefault("event", torch.cuda.Event())
         ev.record(torch.cuda.current_stream(eng.device))

@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from slimdqn import _mixture
 from slimdqn._engine import NetOptions, check_munchausen
 from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau, check_soft_shift_tau
 from slimdqn.networks.architectures.dqn import DQNNet
@@ -60,6 +61,7 @@ class DQN(EngineAgent):
         prune_start: int = 0,
         prune_end: int = 0,
         prune_period: int = 0,
+        rem_heads: int = 0,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
@@ -78,18 +80,26 @@ class DQN(EngineAgent):
         ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head; the soft target here is ``ema_tau``.
         ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning) of
         the online parameters; the target buffer is masked at every mask update, and the apply launch of a gradient step comes in front
-        of the EMA, so the target's zeros stay zero under the hard copy and under ``ema_tau``."""
+        of the EMA, so the target's zeros stay zero under the hard copy and under ``ema_tau``.
+        ``rem_heads`` = H > 0: REM, the random ensemble mixture (Agarwal et al. 2020; include/isdqn_hip.h, isdqn_batch_mixture) -- the
+        network has H heads on one torso, every gradient step (eager and captured: one more node in front of the learn call, on the
+        step's stream) draws a new convex combination of the heads on the device and regresses the mixture on the target network's
+        mixture; acting, ``q_values``, ``loss`` and ``compute_target`` use the head average.  0 is off: the agent built without the
+        argument.  Refused with ``noisy``, ``n_bins``, ``n_quantiles``, ``munchausen_tau`` and ``cql_alpha`` (slimdqn/_mixture.py)."""
         options = NetOptions.pick(locals())
         check_munchausen(double_q, munchausen_tau)  # (in front of the other rules, where this constructor has always asked it)
         options.check(architecture_type, features)
         self.ema_tau = check_ema_tau(ema_tau, supported=True)
         check_soft_shift_tau(soft_shift_tau)
+        H = _mixture.check_rem_heads(rem_heads, noisy=noisy, n_bins=n_bins, n_quantiles=n_quantiles, munchausen_tau=munchausen_tau, cql_alpha=cql_alpha)
+        if H:  # (off: the class default, and an engine of one head as ever)
+            self.rem_heads = H
         self.use_graph = bool(use_graph)  # update_online_params on a device replay replays a captured step (networks/_agent.py)
-        self.network = DQNNet([int(f) for f in features], architecture_type, (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
+        self.network = DQNNet([int(f) for f in features], architecture_type, max(H, 1) * (n_actions + (1 if dueling else 0)) * max(int(n_bins), int(n_quantiles), 1), layer_norm, False)
         self.data_to_update = data_to_update
         self.target_update_frequency = target_update_frequency
         self.target_params = None
-        self._init_engine_agent(key, observation_dim, n_actions, 1, features, layer_norm, architecture_type, learning_rate,
+        self._init_engine_agent(key, observation_dim, n_actions, max(H, 1), features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
                                 cql_alpha=cql_alpha, prune_sparsity=prune_sparsity, prune_start=prune_start, prune_end=prune_end,
                                 prune_period=prune_period)
@@ -107,6 +117,10 @@ class DQN(EngineAgent):
             target = self._target_tensor(self.target_params)
             eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
             step_learn = lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw())
+            if self.rem_heads:  # (the step's draw: one more node in front of the learn call; the key below says it is there)
+                step_learn = self._rem_learn(eng, step_learn)
+            # (what the draw writes is state of the step: a capture's warm-up must not advance the count)
+            rem_state = [eng.mix_count, eng.mix_alpha] if self.rem_heads else []
             pruned = self.prune_active  # (the apply launch right behind the learn call, in front of the EMA; the key says it is there)
             if pruned:
                 step_learn = self._prune_learn(eng, step_learn)
@@ -117,11 +131,12 @@ class DQN(EngineAgent):
                     step_learn(cb)
                     self._ema_target(eng, target)
 
-                key = (target.data_ptr(), self.ema_tau)
+                key = (target.data_ptr(), self.ema_tau) + (("rem",) if self.rem_heads else ())
                 g = self._graphed_update(replay_buffer, learn=learn, key=(key, "prune") if pruned else key,
-                                         state=[target] + ([self.target_sigma] if self.noisy else []))
+                                         state=[target] + ([self.target_sigma] if self.noisy else []) + rem_state)
             else:
-                g = self._graphed_update(replay_buffer, learn=step_learn, key=(target.data_ptr(), "prune") if pruned else target.data_ptr())
+                key = (target.data_ptr(), "rem") if self.rem_heads else target.data_ptr()
+                g = self._graphed_update(replay_buffer, learn=step_learn, key=(key, "prune") if pruned else key, state=rem_state)
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
                 self._run_graph(g)
                 return
@@ -133,6 +148,15 @@ class DQN(EngineAgent):
             if getattr(self, "priority_writeback", False) and hasattr(replay_buffer, "update_device"):  # (as the captured step does)
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_loss += loss` (dqn.py:47) happens on the device inside the step
+
+    @staticmethod
+    def _rem_learn(eng, learn):
+        """``learn`` with the step's mixture draw in front of it on the same stream."""
+        def drawn(cb):
+            eng.mixture_draw()
+            return learn(cb)
+
+        return drawn
 
     def _ema_target(self, eng, target: torch.Tensor) -> None:
         """target <- (1 - ema_tau) * target + ema_tau * online behind a gradient step (noisy: the target's sigma likewise)."""
@@ -171,6 +195,8 @@ class DQN(EngineAgent):
         """In-place gradient step; returns (params, optimizer_state, loss) like the reference (loss: device scalar)."""
         eng = self._engine_for(self._batch_len(batch_samples))
         self._load_bound(eng, self._bind(params))
+        if self.rem_heads:
+            eng.mixture_draw()
         losses = eng.learn_on_batch_target(self._c_batch(eng, batch_samples), self._target_tensor(params_target), **self._target_sigma_kw())
         return self.params, self.optimizer_state, losses[0]
 
@@ -181,15 +207,21 @@ class DQN(EngineAgent):
 
     def compute_target(self, params, sample):
         """reward + (1 - terminal) * gamma**n * max_a Q_params(next_state) for ONE sample (dqn.py:84-88); host helper."""
-        nq = self._q_row(params, sample.next_state).cpu().numpy().reshape(-1).astype(np.float64)
+        nq = self._mean_q(self._q_row(params, sample.next_state))
         return float(sample.reward) + (1.0 - float(sample.is_terminal)) * (self.gamma**self.update_horizon) * float(nq.max())
 
     def loss(self, params, params_target, sample):
-        q = self._q_row(params, sample.state).cpu().numpy().reshape(-1).astype(np.float64)
+        q = self._mean_q(self._q_row(params, sample.state))
         return float((q[int(sample.action)] - self.compute_target(params_target, sample)) ** 2)
 
     def q_values(self, params, state) -> np.ndarray:
-        return self._q_row(params, state).cpu().numpy().reshape(self.n_actions)
+        row = self._q_row(params, state).cpu().numpy()
+        return row.reshape(-1, self.n_actions).mean(axis=0, dtype=np.float32) if self.rem_heads else row.reshape(self.n_actions)
+
+    def _mean_q(self, row) -> np.ndarray:
+        """float64 action values of one device row: the row itself, or the head average of a mixture agent (uniform alpha)."""
+        q = row.cpu().numpy().reshape(-1).astype(np.float64)
+        return q.reshape(-1, self.n_actions).mean(axis=0) if self.rem_heads else q
 
     def best_action(self, params, state, **kwargs):
         return self._best_action(params, state, 0)
