@@ -204,6 +204,16 @@ if __name__ == "__main__":
         dict(name="geo-c51-r2", arch="fc", obs=(8,), feats=(16, 16), K=12, A=1, B=5, n_bins=256, categorical=True),
         dict(name="geo-qr-r1", arch="fc", obs=(8,), feats=(16, 16), K=20, A=1, B=3, n_quantiles=256),
         dict(name="geo-hl-widest", arch="fc", obs=(8,), feats=(16, 16), K=10, A=2, B=4, n_bins=248),
+        # the geometries of tests/helpers/conv_routes.py: several 128-pixel tiles per image and per stride class (a ragged last one), the
+        # u8 pair kernel's loop over halves, the one-tile u8 kernel at 64 channels and at three stacked frames, the generic forward at 64
+        # input channels and the generic weight gradients behind the image kernels' LDS checks, the smallest observation
+        dict(name="routes-100x100", arch="cnn", obs=(100, 100, 4), feats=(32, 64, 64, 32), K=3, A=5, B=6),
+        dict(name="routes-160x120", arch="cnn", obs=(160, 120, 4), feats=(32, 64, 64, 32), K=2, A=3, B=3),
+        dict(name="routes-128x128-w64", arch="cnn", obs=(128, 128, 4), feats=(64, 64, 64, 32), K=2, A=3, B=4),
+        dict(name="routes-64x64x3", arch="cnn", obs=(64, 64, 3), feats=(32, 64, 64, 32), K=3, A=4, B=6),
+        dict(name="routes-84-w64-48-24", arch="cnn", obs=(84, 84, 4), feats=(64, 48, 24, 32), K=2, A=5, B=5),
+        dict(name="routes-40x40x2", arch="cnn", obs=(40, 40, 2), feats=(16, 32, 64, 32), K=3, A=3, B=7),
+        dict(name="routes-8x8x1", arch="cnn", obs=(8, 8, 1), feats=(8, 8, 8, 32), K=2, A=3, B=3),
         # negative control: the checker must notice a tensor that was not registered
         dict(name="control-action-not-registered", arch="cnn", obs=(84, 84, 4), feats=(7, 9, 11, 13), K=3, A=5, B=6, omit="action"),
     ]

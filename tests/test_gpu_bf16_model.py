@@ -27,14 +27,18 @@ gradients running 3 passes (6: dz of every cnn case).
 Not covered here: the LayerNorm scale / bias leaves of g (their sums over B x pixels rows run through partial slabs whose order
 is not modelled).  The impala torso in bf16 and bf16x3 is covered stage by stage, with the same model and bounds, in
 tests/test_gpu_impala.py (test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands), the BatchNorm cnn and fc networks
-in tests/test_gpu_batchnorm.py (test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands).  Still uncovered in
-bf16: the BatchNorm sites inside the impala torso ("Stack_s/BatchNorm_b"; they reuse the six kernels of csrc/batchnorm.h)."""
+in tests/test_gpu_batchnorm.py (test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands).  Every cnn case here runs
+at the Atari frame (84x84x4): the convolution kernels that other frame sizes, stack depths and conv widths select -- several tiles per
+image or per stride class, the u8 pair kernel's loop over halves, the generic fallbacks behind the LDS checks -- are held to the same
+model in tests/test_gpu_conv_routes.py (cases and routes: tests/helpers/conv_routes.py).  Still uncovered in bf16: the BatchNorm
+sites inside the impala torso ("Stack_s/BatchNorm_b"; they reuse the six kernels of csrc/batchnorm.h)."""
 import numpy as np
 import pytest
 import torch
 
 from tests.gpu_helpers import adam_bounds, device_batch, make_frame_batch, perturbed_params
 from tests.helpers import bf16_model as M
+from tests.helpers import conv_routes as R
 
 pytestmark = pytest.mark.gpu
 
@@ -52,82 +56,13 @@ CASES = {
 }
 RUNS = [pytest.param(c, "bf16", id=f"{c}-bf16" if not c.endswith("-bf16") else c) for c in CASES] + [
     pytest.param(c, "bf16x3", id=f"{c}-bf16x3") for c in ("small", "B131", "fc-lunar", "fc-cols4")]
-FC_OBS = (8,)
 GAMMA = 0.99
-CONVS = ((8, 4), (4, 2), (3, 1))
-_ceil = lambda a, b: -(-a // b)
+# the geometry and the plan's tiling decisions, restated once for this file and tests/test_gpu_conv_routes.py
+FC_OBS, CONVS, _ceil = R.FC_OBS, R.CONVS, R._ceil
+_layers, _fwd_splits, _dense_wgrad_slabs, _conv_wgrad_chain = R.layers, R.fwd_splits, R.dense_wgrad_slabs, R.conv_wgrad_chain
 
 
 # ------------------------------------------------------------------ the selection code, restated (net_plan.h, net_kernels.hip)
-def _layers(cfg):
-    """Hidden layers in plan order: name, kind, ln name, true / padded width, pixels, conv (k, s), internal input width."""
-    out, n_ln = [], 0
-    if cfg["arch"] == "cnn":
-        h, cp = 84, 4
-        for i, (k, s) in enumerate(CONVS):
-            h = _ceil(h, s)
-            c = cfg["feats"][i]
-            out.append(dict(name=f"Conv_{i}", kind=0, ln=f"LayerNorm_{n_ln}" if cfg["ln"] else None, c=c, cp=_ceil(c, 8) * 8, npix=h * h,
-                            k=k, s=s, h=h, K=4 * 64 if i == 0 else k * k * cp))
-            cp = _ceil(c, 8) * 8
-            n_ln += cfg["ln"]
-        in_p, dense = h * h * cp, cfg["feats"][3:]
-    else:
-        in_p, dense = _ceil(FC_OBS[0], 8) * 8, cfg["feats"]
-    for j, c in enumerate(dense):
-        out.append(dict(name=f"Dense_{j}", kind=1, ln=f"LayerNorm_{n_ln}" if cfg["ln"] else None, c=c, cp=_ceil(c, 8) * 8, npix=1,
-                        K=in_p, in_p=in_p))
-        n_ln += cfg["ln"]
-        in_p = _ceil(c, 8) * 8
-    return out, in_p
-
-
-def _fwd_splits(N2, out_p, K, unpadded):
-    """split-K factor of a dense forward GEMM: net_plan.h:440-450 (fwd_splits, fwd_narrow), capped like effective_splits"""
-    ft = _ceil(N2, 128) * _ceil(out_p, 128)
-    if ft <= 64 and not unpadded and out_p % 64 == 0:
-        ft = _ceil(N2, 128) * _ceil(out_p, 64)
-    fs = 1 if ft >= 256 else 512 // ft
-    return max(1, min(fs, _ceil(K, 32)))
-
-
-def _dense_wgrad_slabs(B, in_p, out_p):
-    """split-K slabs of a dense weight gradient: net_plan.h:431-437"""
-    tiles = _ceil(out_p, 128) * _ceil(in_p, 128)
-    s = 1 if tiles >= 128 else 256 // tiles
-    return max(1, min(s, _ceil(B, 32)))
-
-
-def _conv_wgrad_chain(B, L):
-    """(K steps in one accumulator, slabs) of a convolution's weight gradient: generic engine slabs (net_plan.h:398-403), or the
-    image-resident kernel's groups of G images (net_plan.h:406-427)."""
-    K, npix = L["K"], L["npix"]
-    u8 = L["name"] == "Conv_0"
-    tiles_n = _ceil(K, 64)
-    ks = _ceil(B * npix, 32)
-    s = max(1, min(256 // tiles_n or 1, ks))
-    steps, slabs = _ceil(ks, s), s
-    cin_p = K // (L["k"] ** 2) if not u8 else 4
-    if K % 64 == 0 and (u8 or cin_p % 16 == 0):
-        ntw = 4 if K % 256 == 0 else 3 if K % 192 == 0 else 2 if K % 128 == 0 else 0
-        if K == 512:
-            ntw = 2
-        wide = L["cp"] == 64 and not u8 and K in (512, 576)
-        if wide:
-            ntw = K // 64
-        if ntw:
-            ncg = K // (64 * ntw)
-            G = (B * ncg + 255) // 256
-            if wide:
-                G = (B + 127) // 128
-                if G > 2:
-                    G = max(2, (B + 255) // 256)
-            G = max(G, 1)
-            groups = _ceil(B, G)
-            steps, slabs = max(steps, _ceil(G * npix, 32)), max(s, groups)
-    return steps, slabs
-
-
 def _dense_dgrad_ln(cfg, layers):
     """The fused data gradient + LayerNorm backward under the first dense layer of a cnn: None when it is not taken
     (net_kernels.hip:2186-2187), else its K groups (2: DenseDgradLN<P, 128, 2>, 1: DenseDgradLN<P, 128>; :2206, :2213-2214).
