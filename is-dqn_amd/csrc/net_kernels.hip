@@ -747,6 +747,13 @@ extern "C" int isdqn_selftest_gemm(const float* A, const float* B, float* C, int
     return plain_big<true, true, false>(x3, a, nullptr, 0, b, C, N, M, N, K, split_k, slab, st);
 }
 
+namespace isdqn {
+// (declared in net_launch.h in front of dense_wgrad)
+static int dense_wgrad_fp32(const Layer& l, bool x3, const MatSrc& A, const MatSrc& Bm, float* slabs, int rows, hipStream_t st) {
+    return plain_big<true, true, false>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);
+}
+}  // namespace isdqn
+
 // ---- soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift): host code here, the kernel in soft_shift_kernels.hip ----
 
 extern "C" int isdqn_net_soft_shift(const isdqn_net_config* cfg, float* params, float tau, void* workspace, void* stream) {

@@ -815,14 +815,21 @@ static int conv_wgrad(const Layer& l, bool x3, const NetInput& in, const float* 
     return x3 ? launch_conv_wgrad<3, false>(l, in, act_in, dz, slabs, rows, st) : launch_conv_wgrad<1, false>(l, in, act_in, dz, slabs, rows, st);
 }
 
+// dense_wgrad with both operands fp32 and no alignment promise.  It runs the kernels of isdqn_selftest_gemm and is defined behind it
+// (net_kernels.hip): naming their instantiation here would move them in the code object (tests/test_kernel_order_host.py)
+static int dense_wgrad_fp32(const Layer& l, bool x3, const MatSrc& A, const MatSrc& Bm, float* slabs, int rows, hipStream_t st);
+
 // weight gradient of dense layer `l` into its effective_splits(rows, l.gw_slabs) slabs:
 // dW[out][in_p] = sum_b dz[b][out] * a[b][in_p], both operands stored [K = b][rows]
 static int dense_wgrad(const Layer& l, bool x3, const NetInput& in, const float* act_in, const float* dz, int dz_ld, float* slabs, int rows,
                        hipStream_t st) {
     const MatSrc A{dz, dz_ld, rows, l.out_p, 1};
     const MatSrc Bm = l.in_unpadded_ld ? MatSrc{in.obs, l.in_unpadded_ld, rows, l.in_f, 0} : MatSrc{act_in, l.in_p, rows, l.in_p, 1};
-    if (l.in_unpadded_ld)  // fc first layer: caller's fp32 observations
+    if (l.in_unpadded_ld) {  // fc first layer: caller's fp32 observations
+        // (an fc network without a hidden layer: that first layer is the head, and its dz is the fp32 dL/dq, not an S8 tensor)
+        if (l.is_head) return dense_wgrad_fp32(l, x3, A, Bm, slabs, rows, st);
         return plain_big<true, true, false, false, DZ_S8>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);
+    }
     if (l.is_head)  // dL/dq is fp32, the hidden activations are S8
         return plain_big<true, true, true, false, 2>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);
     return plain_big<true, true, true, false, DZ_S8 | 2>(x3, A, nullptr, 0, Bm, slabs, l.in_p, l.out_p, l.in_p, rows, l.gw_slabs, l.w_size, st);

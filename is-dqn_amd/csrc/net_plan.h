@@ -413,7 +413,9 @@ static inline int plan_dense_tail(const isdqn_net_config* cfg, Plan& P, ParamCur
         l.in_f = in.f; l.in_p = in.p;
         l.in_unpadded_ld = (cfg->arch == ISDQN_ARCH_FC && i == 0) ? in.f : 0;
         l.out_f = l.is_head ? (P.dueling ? P.raw : P.nlog) : cfg->features[i];
-        ISDQN_REQUIRE(l.out_f >= 1 && l.out_f <= 8192, ISDQN_ERR_ARG, "bad dense width");
+        // what the row-wise kernels behind a Dense run: ln_bwd_wide_kernel holds 16 columns per thread (256 * LN_WIDE_MAX_COLS,
+        // row_kernels.h), dense_post_kernel stages a head row with its bias and LayerNorm rows in 64 KB of LDS (3 * 5456 floats)
+        ISDQN_REQUIRE(l.out_f >= 1 && l.out_f <= (l.is_head ? 5456 : 4096), ISDQN_ERR_ARG, "bad dense width");
         l.out_p = round_up(l.out_f, 8);
         l.K = l.in_p;
         l.in_elems_p = in.elems_p;

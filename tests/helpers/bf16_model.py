@@ -275,6 +275,27 @@ def ln_relu_bwd(z, gamma, mask, da, E_da, has_ln=True):
     return dz, prop + arith + stat + S8_STORE * dz.abs() + c_ln * FLOOR
 
 
+def ln_param_grads(z, mask, da, E_da, chain):
+    """The LayerNorm scale / bias leaves of y = relu(LayerNorm(z) gamma + beta): (dgamma, E_dgamma, dbeta, E_dbeta) per channel, the
+    sums over every leading axis of dy xhat and of dy, dy = mask da, xhat from the kernel's own fp32 z (ln_stats).  The bound of each is
+    the sum of three terms: E_da carried through (sum mask E_da |xhat|, sum mask E_da); the fp32 error of xhat itself (eps_x, as
+    derived in ln_relu_bwd) on sum |dy|, for the scale only; and a plain fp32 chain of `chain` additions -- the rows summed into one
+    partial row plus the partial rows summed behind it, from the route -- on the magnitude sum of the terms (chain_depth(0, chain):
+    the product dy xhat and the final store are its epilogue)."""
+    C = z.shape[-1]
+    mean, var, r, xhat = ln_stats(z)
+    dy = da * mask
+    ax, ady = xhat.abs(), dy.abs()
+    c_ln = ROUNDING * (C + 8)
+    eps_r = c_ln * U * ((z * z).mean(-1, keepdim=True) + mean * mean) / (var + LN_EPS)
+    eps_x = eps_r * ax + c_ln * U * r * z.abs().mean(-1, keepdim=True)
+    rows = lambda t: t.reshape(-1, C).sum(0)
+    c = chain_depth(0, slabs=chain)
+    Eg = rows(mask * E_da * ax) + rows(ady * eps_x) + bound(rows(ady * ax), c)
+    Eb = rows(mask * E_da) + bound(rows(ady), c)
+    return rows(dy * xhat), Eg, rows(dy), Eb
+
+
 def ln_relu_fwd(z, gamma, beta, E_z, has_ln=True):
     """a = relu(LayerNorm(z) gamma + beta) (or relu(z)) of a model z with per-element error bound E_z, and the bound of the kernel's
     S8 activation against it: E_z carried through the normalisation (first order; relu is 1-Lipschitz), the fp32 arithmetic of

@@ -47,7 +47,7 @@ def layers(cfg):
             n_ln += cfg["ln"]
         in_p, dense = h * w * cp, cfg["feats"][3:]
     else:
-        in_p, dense = _round_up(FC_OBS[0], 8), cfg["feats"]
+        in_p, dense = _round_up(cfg.get("obs", FC_OBS)[0], 8), cfg["feats"]  # (an fc case may name its own observation width)
     for j, c in enumerate(dense):
         out.append(dict(name=f"Dense_{j}", kind=1, ln=f"LayerNorm_{n_ln}" if cfg["ln"] else None, c=c, cp=_round_up(c, 8), npix=1,
                         K=in_p, in_p=in_p))

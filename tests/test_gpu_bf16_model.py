@@ -24,8 +24,14 @@ forward running 3 passes (9), DenseDgradLN<1, 128> skipping its last K step (3: 
 dropping the last transition of a partial workgroup (B1030's head test), round8 truncating (21), the bf16 convolution data
 gradients running 3 passes (6: dz of every cnn case).
 
-Not covered here: the LayerNorm scale / bias leaves of g (their sums over B x pixels rows run through partial slabs whose order
-is not modelled).  The impala torso in bf16 and bf16x3 is covered stage by stage, with the same model and bounds, in
+Not covered here: the LayerNorm scale / bias leaves of g at these sizes.  Their model (bf16_model.ln_param_grads: sum dy xhat and
+sum dy, bounded by a plain chain over the partial rows of the route that wrote them) and every Dense route the widths above do not
+select -- the four ln_bwd_small forms and ln_bwd_wide up to its 4096 columns, with and without a LayerNorm and with grid-stride rows;
+two hidden Dense layers behind the torso, DenseDgradLN at a ragged K; the generic head path in a learn step and in a gradient-only
+pass; the head chain at its widest; dense_post_kernel's second column pass and its slab tail; the big dense data gradient; a head
+with no hidden layer -- are held stage by stage in tests/test_gpu_dense_routes.py (cases and routes: tests/helpers/dense_routes.py,
+where _head_chain and _dense_dgrad_ln of this file now live).
+The impala torso in bf16 and bf16x3 is covered stage by stage, with the same model and bounds, in
 tests/test_gpu_impala.py (test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands), the BatchNorm cnn and fc networks
 in tests/test_gpu_batchnorm.py (test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands).  Every cnn case here runs
 at the Atari frame (84x84x4): the convolution kernels that other frame sizes, stack depths and conv widths select -- several tiles per
@@ -39,6 +45,7 @@ import torch
 from tests.gpu_helpers import adam_bounds, device_batch, make_frame_batch, perturbed_params
 from tests.helpers import bf16_model as M
 from tests.helpers import conv_routes as R
+from tests.helpers import dense_routes as D
 
 pytestmark = pytest.mark.gpu
 
@@ -62,34 +69,8 @@ FC_OBS, CONVS, _ceil = R.FC_OBS, R.CONVS, R._ceil
 _layers, _fwd_splits, _dense_wgrad_slabs, _conv_wgrad_chain = R.layers, R.fwd_splits, R.dense_wgrad_slabs, R.conv_wgrad_chain
 
 
-# ------------------------------------------------------------------ the selection code, restated (net_plan.h, net_kernels.hip)
-def _dense_dgrad_ln(cfg, layers):
-    """The fused data gradient + LayerNorm backward under the first dense layer of a cnn: None when it is not taken
-    (net_kernels.hip:2186-2187), else its K groups (2: DenseDgradLN<P, 128, 2>, 1: DenseDgradLN<P, 128>; :2206, :2213-2214).
-    part_rows of the conv layer below: net_plan.h:389-390, 463-464."""
-    if cfg["arch"] != "cnn":
-        return None
-    B, below, d0 = cfg["B"], layers[2], layers[3]
-    part_rows = max(256, _ceil(B, 64) * below["npix"]) if below["cp"] == 64 else 256
-    if below["cp"] != 64 or part_rows < _ceil(B, 128) * below["npix"]:
-        return None
-    return 2 if _ceil(B, 128) * (d0["in_p"] // 64) <= 256 and d0["cp"] % 64 == 0 else 1
-
-
-def _head_chain(cfg, hid_p, nha_p, K, passes):
-    """(S, COLS) the learn step's head chain runs with, or None when it is skipped: net_kernels.hip:1929-1941 (eligibility, S),
-    :471-475 (head_chain_lds_bytes), :2012-2015 (COLS).  part_rows: net_plan.h:389-390."""
-    B = cfg["B"]
-    if hid_p > 512 * 4 or hid_p % 8:
-        return None
-    S = 4 if B >= 1024 else 2 if B >= 512 else 1
-    part_rows = max(256, B)
-    pitch = _ceil(hid_p, 32) * 32 + 8
-    lds = (2 if passes >= 2 else 1) * 16 * pitch * 2 + (8 * 16 * nha_p + 16 * nha_p + S * nha_p + nha_p + 4 + 2 * S * hid_p) * 4 + S * K * 8 + 8 * 2 * S * 2 * 4 + 64
-    if _ceil(B, S) > part_rows or S * K > 512 or lds > 150 * 1024:
-        return None
-    cols = _ceil(hid_p, 512)
-    return S, (1 if cols == 1 else 2 if cols == 2 else 4)
+# the selection code, restated (net_plan.h, learn_step.h): tests/helpers/dense_routes.py holds it for this file and tests/test_gpu_dense_routes.py
+_dense_dgrad_ln, _head_chain = D._dense_dgrad_ln, D._head_chain
 
 
 # ------------------------------------------------------------------ one run
