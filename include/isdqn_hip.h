@@ -974,6 +974,43 @@ int isdqn_net_prune_update(const isdqn_net_config* cfg, float* params, const int
                            void* workspace, void* stream);
 int isdqn_net_prune_apply(const isdqn_net_config* cfg, float* params, const uint32_t* mask, void* workspace, void* stream);
 
+/* Normalize-and-Project (NaP: Lyle, Zheng, Khetarpal, Martens, van Hasselt, Pascanu, Dabney, "Normalization and effective learning rates
+ * in reinforcement learning", NeurIPS 2024): with a normalisation layer in front of every nonlinearity the function does not depend on
+ * the scale of a weight matrix, the parameter norm grows freely under Adam and the effective learning rate decays as 1 / |W|^2; after
+ * every optimizer update each layer's weights are therefore projected back to the norm they had at initialisation.  The reference has no
+ * counterpart.  Built BESIDE the plan, like pruning: no field of isdqn_net_config, no workspace region, no launch of any existing entry
+ * point.  On the device, stream-ordered, capturable, without a host synchronisation, an allocation or an atomic of any kind.  THE
+ * definition:
+ * Projected tensors: exactly the prunable tensors of isdqn_net_prune_layout -- every conv kernel and every Dense kernel (kinds 0 and 1)
+ *   except the LAST Dense (no normalisation follows it: its scale is the scale of Q), in layout order.  Only REAL elements (the predicate
+ *   of pruning, above) count and only real elements are written: padding rows and lanes keep their bits.  Biases, LayerNorm scales and
+ *   biases, both Adam moments, the step count and every other tensor are neither read nor written.
+ * Arithmetic: tensor i has real elements w_j (fp32) and a target norm rho_i = target_norms[i] (float64, device memory).
+ *   S_i = sum_j (double)w_j * (double)w_j: the squares are exact in float64, the additions are float64 in an order that is the
+ *   implementation's own but FIXED -- the same bits on every run, eager and captured, and in every workgroup that needs the sum.
+ *   n_i = sqrt(S_i) in float64; s_i = (float)(rho_i / n_i): IEEE sqrt and division in float64, one rounding to fp32.
+ *   If S_i is 0, inf or NaN, or rho_i is not finite or <= 0: s_i = 1.0f and nothing of the tensor is written.
+ *   Otherwise every real element becomes fl32(w_j * s_i), one fp32 multiply (denormals are not flushed), and, with a workspace, its entry
+ *   of the S8 weight mirror (region "wsplit") gets the bits isdqn_net_refresh_mirror would make of the new master: a mirror that was
+ *   current before the call is current after it.  (Where s_i rounds to 1.0f the stores may be skipped: they would change no bit.)
+ *   norms[i] = n_i (double), measured BEFORE the projection; scales[i] = s_i (float).
+ * isdqn_net_project_layout (host arithmetic on the plan, no GPU): *n_tensors = the number of projected tensors; infos (may be NULL to
+ *   query) receives for each of the first max_infos the four int64 of isdqn_net_prune_layout: {index into isdqn_net_param_layout's table,
+ *   offset, internal size, real element count}; *scratch_bytes = what the two calls below need (one double per chunk of 4096 floats of
+ *   every tensor; contents between calls do not matter).  Any output pointer may be NULL.
+ * isdqn_net_project_norms: measures only -- norms[i] of `params`, in the bits isdqn_net_project_apply would report for the same buffer.
+ *   Two launches: the chunk sums, then one workgroup per tensor.
+ * isdqn_net_project_apply: the node behind every gradient step.  Two launches over one workgroup per chunk: the chunk sums into the
+ *   scratch; then every workgroup adds up its tensor's chunk sums in one fixed order (so all of them derive the same s_i bit for bit),
+ *   the tensor's first workgroup stores norms[i] and scales[i], and all of them scale their chunk.  workspace == NULL: the master alone.
+ * ISDQN_ERR_UNSUPPORTED, nothing launched: the impala torso and batch_norm, as with pruning.  ISDQN_ERR_ARG, nothing launched: a NULL cfg /
+ *   params / target_norms / norms / scales / scratch; params not 16-byte aligned; target_norms, norms or scratch not 8-byte aligned;
+ *   scales not 4-byte aligned. */
+int isdqn_net_project_layout(const isdqn_net_config* cfg, int32_t* n_tensors, int64_t* infos, int32_t max_infos, int64_t* scratch_bytes);
+int isdqn_net_project_norms(const isdqn_net_config* cfg, const float* params, double* norms, void* scratch, void* stream);
+int isdqn_net_project_apply(const isdqn_net_config* cfg, float* params, const double* target_norms, double* norms, float* scales,
+                            void* scratch, void* workspace, void* stream);
+
 /* Engine self-test: C[M][N] = A . B on the MFMA tile engine for every operand-layout
  * combination (a_tr/b_tr: 0 = operand stored [rows][K], 1 = stored [K][rows]).  Test hook. */
 int isdqn_selftest_gemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int32_t a_tr,

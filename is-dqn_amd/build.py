@@ -27,6 +27,9 @@ PRUNE_SOURCES = ["prune_kernels.hip"]
 # are): compiled and linked into every variant in the same loop; its assembly comes from emit_mixture_asm(), which
 # tests/test_mixture_host.py lints.
 MIXTURE_SOURCES = ["mixture_kernels.hip"]
+# Normalize-and-Project, a translation unit of its own as well (tests/test_mixture_host.py holds the five lists above apart): compiled and
+# linked into every variant in the same loop; its assembly comes from emit_project_asm(), which tests/test_nap_host.py lints.
+PROJECT_SOURCES = ["project_kernels.hip"]
 HEADERS = sorted(f for f in os.listdir(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")) if f.endswith(".h")) + [
     os.path.join("..", "..", "include", "isdqn_hip.h")]
 # -fno-slp-vectorize: hipcc's SLP vectoriser turns scalar fp32 epilogue math into packed v_pk_*_f32 sequences, and one of
@@ -54,7 +57,7 @@ def build(force=False, verbose=True, variant=None, defines=(), extra_flags=()):
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     objs = []
     procs = []
-    for src in SOURCES + EXTRA_SOURCES + SIDE_SOURCES + PRUNE_SOURCES + MIXTURE_SOURCES:
+    for src in SOURCES + EXTRA_SOURCES + SIDE_SOURCES + PRUNE_SOURCES + MIXTURE_SOURCES + PROJECT_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
@@ -112,6 +115,11 @@ def emit_mixture_asm(force=False, verbose=False):
     return emit_asm(force=force, verbose=verbose, sources=MIXTURE_SOURCES)
 
 
+def emit_project_asm(force=False, verbose=False):
+    """emit_asm for PROJECT_SOURCES."""
+    return emit_asm(force=force, verbose=verbose, sources=PROJECT_SOURCES)
+
+
 if __name__ == "__main__":
     _variant = None
     _defs = []
@@ -124,4 +132,5 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, variant=_variant, defines=_defs, extra_flags=_extra))
     if "--emit-asm" in sys.argv:
         print("\n".join(emit_asm(force="--force" in sys.argv, verbose=True) + emit_side_asm(force="--force" in sys.argv, verbose=True)
-                        + emit_prune_asm(force="--force" in sys.argv, verbose=True) + emit_mixture_asm(force="--force" in sys.argv, verbose=True)))
+                        + emit_prune_asm(force="--force" in sys.argv, verbose=True) + emit_mixture_asm(force="--force" in sys.argv, verbose=True)
+                        + emit_project_asm(force="--force" in sys.argv, verbose=True)))

@@ -19,6 +19,7 @@
 #include "conservative.h"
 #include "soft_shift.h"
 #include "prune.h"
+#include "project.h"
 #include "mixture.h"
 #include "munchausen.h"
 #include "hl_gauss.h"
@@ -872,6 +873,55 @@ extern "C" int isdqn_net_prune_apply(const isdqn_net_config* cfg, float* params,
     a.mask = const_cast<uint32_t*>(mask);
     a.scratch = nullptr;
     return launch_prune_apply(a, (hipStream_t)stream);
+}
+
+// ---- Normalize-and-Project (include/isdqn_hip.h, isdqn_net_project_*): host code here, the kernels in project_kernels.hip.  The
+// projected tensors are the prunable ones: prune_table above, with its refusals ----
+
+extern "C" int isdqn_net_project_layout(const isdqn_net_config* cfg, int32_t* n_tensors, int64_t* infos, int32_t max_infos,
+                                        int64_t* scratch_bytes) {
+    const Plan* Pp;
+    PruneTable tab;
+    int32_t index[PRUNE_MAX_TENSORS];
+    if (int rc = prune_table(cfg, &Pp, tab, index)) return rc;
+    if (n_tensors) *n_tensors = tab.n;
+    for (int i = 0; infos && i < tab.n && i < max_infos; ++i) {
+        infos[4 * i + 0] = index[i];
+        infos[4 * i + 1] = tab.t[i].offset;
+        infos[4 * i + 2] = tab.t[i].size;
+        infos[4 * i + 3] = tab.t[i].n_real;
+    }
+    if (scratch_bytes) *scratch_bytes = project_scratch_bytes(tab);
+    return ISDQN_OK;
+}
+
+extern "C" int isdqn_net_project_norms(const isdqn_net_config* cfg, const float* params, double* norms, void* scratch, void* stream) {
+    const Plan* Pp;
+    ProjectArgs a;
+    if (int rc = prune_table(cfg, &Pp, a.tab, nullptr)) return rc;
+    ISDQN_REQUIRE(params && norms && scratch, ISDQN_ERR_ARG, "null pointer");
+    a.p = const_cast<float*>(params);
+    a.mirror = nullptr;
+    a.target = nullptr;
+    a.norms = norms;
+    a.scales = nullptr;
+    a.scratch = (double*)scratch;
+    return launch_project_norms(a, (hipStream_t)stream);
+}
+
+extern "C" int isdqn_net_project_apply(const isdqn_net_config* cfg, float* params, const double* target_norms, double* norms, float* scales,
+                                       void* scratch, void* workspace, void* stream) {
+    const Plan* Pp;
+    ProjectArgs a;
+    if (int rc = prune_table(cfg, &Pp, a.tab, nullptr)) return rc;
+    ISDQN_REQUIRE(params && target_norms && norms && scales && scratch, ISDQN_ERR_ARG, "null pointer");
+    a.p = params;
+    a.mirror = workspace != nullptr ? (float*)workspace + Pp->wsplit_off : nullptr;
+    a.target = target_norms;
+    a.norms = norms;
+    a.scales = scales;
+    a.scratch = (double*)scratch;
+    return launch_project_apply(a, (hipStream_t)stream);
 }
 
 // ---- random ensemble mixture (mixture.h, mixture_kernels.hip; include/isdqn_hip.h, isdqn_mixture_draw / isdqn_batch_mixture) ----

@@ -17,7 +17,7 @@ from experiments.base.dqn import train
 from experiments.atari.common import make_environment, make_replay, seeds
 from experiments.base.utils import prepare_logs
 from experiments.base.offline import environment_for
-from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, conservative_kwargs, prune_kwargs, augment_kwargs, quantile_kappa
+from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, conservative_kwargs, prune_kwargs, projection_kwargs, augment_kwargs, quantile_kappa
 from slimdqn.networks.tfdqn import TFDQN
 
 
@@ -56,6 +56,7 @@ def run(argvs=sys.argv[1:], root=None):
         **weight_decay_kwargs(p),
         **conservative_kwargs(p),
         **prune_kwargs(p),
+        **projection_kwargs(p),
         **augment_kwargs(p),
         huber_delta=quantile_kappa(p),
     )

@@ -84,6 +84,10 @@ def train(key, p: dict, agent, env, rb):
             # Gradual pruning (-prune, not in the reference): behind ReDo and the reset, which write pruned positions -- a mask update
             # when the step is a multiple of -prunef, else the mask applied once where one of them ran; "sparsity" in every log
             logs.update(agent.prune_target_update(step, wrote="recycled_neurons" in logs or "reset" in logs))
+        if p.get("normalize_and_project"):
+            # Normalize-and-Project (-nap, not in the reference): the smallest and largest scale the last gradient step applied.  Nothing is
+            # measured or projected here: a reset's fresh draw is projected by the next gradient step
+            logs.update(agent.nap_target_update(step))
         p["wandb"].log({"n_training_steps": step, **logs})
 
     # Replay ratio (-rr N > 1, not in the reference; SR-SPR, BBF): every environment step past n_initial_samples owes N gradient steps,

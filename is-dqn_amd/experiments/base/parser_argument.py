@@ -75,6 +75,7 @@ _ENGINE = [
     ("-prunes", "--prune_start", dict(type=int, default=0, help="Gradient step at which the sparsity of -prune leaves 0; 0 <= -prunes < -prunee. Means nothing without -prune.")),
     ("-prunee", "--prune_end", dict(type=int, default=100000, help="Gradient step from which the sparsity of -prune is the final one. Means nothing without -prune.")),
     ("-prunef", "--prune_frequency", dict(type=int, default=0, help="Steps between two mask updates of -prune, at target updates behind -redo and -reset: a positive multiple of -tuf (0 = -tuf). Means nothing without -prune.")),
+    ("-nap", "--normalize_and_project", dict(default=False, action="store_true", help="Normalize-and-Project (Lyle et al. 2024): after every gradient step every conv and dense kernel but the last Dense is scaled back, on the device, to the norm it had at initialisation, so that the effective learning rate of a -ln network no longer decays as the parameter norm grows; biases and LayerNorm vectors are left alone; 'weight_scale_min' / 'weight_scale_max' are logged at every target update. Off = the calls and the bits of a run without the flag. Needs -ln; with every agent, -prune, -wd, -redo, -reset, -ema, -sst, -rr, -rem, -cql and every head and loss flag; not with -noisy, -bn or -at impala.")),
     ("-rr", "--replay_ratio", dict(type=int, default=1, help="Gradient steps per environment step past -nis (SR-SPR, BBF: 2 to 16), issued together as one captured update where the agent has one. Above 1, -tuf, -redo, -reset and the step of their logs count gradient steps, as -anneal and the -isb schedule always do. 1 = the loop without the flag. Above 1: -utd must be 1, -tuf a multiple of -rr, not with -offline.")),
     ("-wd", "--weight_decay", dict(type=float, default=0.0, help="AdamW (optax.adamw; BBF, SR-SPR: 0.1): decoupled weight decay -- every learn step also takes learning_rate * weight_decay of its value off every element of the conv and dense kernels, on the device, in every Adam kernel. 0 = off (plain Adam, the bits of a run without the flag); finite and >= 0. With every agent, torso, loss and -gc; not with -noisy.")),
     ("-wdall", "--weight_decay_all", dict(default=False, action="store_true", help="-wd also decays the biases and the LayerNorm / BatchNorm scales and biases (never the running statistics). Means nothing without -wd.")),
@@ -352,6 +353,23 @@ def prune_kwargs(p) -> dict:
         return {}
     return dict(prune_sparsity=float(p["prune_sparsity"]), prune_start=int(p["prune_start"]), prune_end=int(p["prune_end"]),
                 prune_period=int(p["prune_frequency"] or p["target_update_frequency"]))
+
+
+# (-nap stays out of parameters.json like -prune)
+def check_projection(p: dict) -> None:
+    """-nap together with -noisy, -bn or -at impala, or without -ln, fails before anything is written, with the agents' own messages
+    (slimdqn/_projection.py)."""
+    from slimdqn import _projection
+
+    if not p.get("normalize_and_project"):
+        return
+    _projection.check_network(layer_norm=bool(p.get("layer_norm", False)), noisy=bool(p.get("noisy_nets", False)),
+                              batch_norm=bool(p.get("batch_norm", False)), architecture_type=p.get("architecture_type", "cnn"))
+
+
+def projection_kwargs(p) -> dict:
+    """The agents' projection keyword from parsed parameters; without -nap the keywords are the ones they were before the flag existed."""
+    return dict(weight_projection=True) if p.get("normalize_and_project") else {}
 
 
 # (-rr stays out of parameters.json like -sst)

@@ -43,6 +43,7 @@ def prepare_logs(env_name: str, algo_name: str, argvs: List[str], root: str = No
     parser_argument.check_ema(p, algo_name)
     parser_argument.check_soft_shift(p, algo_name)
     parser_argument.check_pruning(p)
+    parser_argument.check_projection(p)
     parser_argument.check_replay_ratio(p)
     parser_argument.check_weight_decay(p)
     parser_argument.check_conservative(p)

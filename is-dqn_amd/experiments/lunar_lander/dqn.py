@@ -17,7 +17,7 @@ import numpy as np
 from experiments.base.dqn import train
 from experiments.base.utils import prepare_logs
 from experiments.base.offline import environment_for
-from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, conservative_kwargs, rem_kwargs, prune_kwargs, quantile_kappa
+from experiments.base.parser_argument import histogram_loss_kwargs, munchausen_kwargs, quantile_kwargs, dueling_kwargs, grad_clip_kwargs, noisy_kwargs, ema_kwargs, weight_decay_kwargs, conservative_kwargs, rem_kwargs, prune_kwargs, projection_kwargs, quantile_kappa
 from experiments.lunar_lander.common import make_environment, make_replay, seeds
 from slimdqn.networks.dqn import DQN
 
@@ -56,6 +56,7 @@ def run(argvs=sys.argv[1:], root=None):
         **conservative_kwargs(p),
         **rem_kwargs(p),
         **prune_kwargs(p),
+        **projection_kwargs(p),
         huber_delta=quantile_kappa(p),
     )
     out = train(np.random.default_rng(train_seed), p, agent, env, rb)

@@ -17,6 +17,7 @@ from slimdqn import _hip
 from slimdqn import _conservative
 from slimdqn import _mixture
 from slimdqn import _optimizer
+from slimdqn import _projection
 from slimdqn import _sparsity
 
 
@@ -1019,6 +1020,67 @@ class QNetEngine:
         p, ws = self._prune_target(params)
         _hip.check(self.lib.isdqn_net_prune_apply(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.prune_mask), ws, _hip.stream_ptr(self.device)),
                    "isdqn_net_prune_apply")
+        if params is not None:
+            self._wrote_without_mirror(params)
+
+    project_target = None   # set_weight_projection: float64, the target norm rho_i of every projected tensor
+    project_norms_out = None  # set_weight_projection: float64, n_i of the last project_weights / project_norms call, before the projection
+    project_scales = None   # set_weight_projection: float32, s_i of the last project_weights call
+    project_scratch = None  # set_weight_projection: one double per chunk
+    project_infos = ()      # set_weight_projection: per projected tensor (index into ``infos``, offset, internal size, real element count)
+
+    def set_weight_projection(self, target_norms=None) -> list:
+        """Normalize-and-Project (include/isdqn_hip.h, isdqn_net_project_*) for this engine: allocates the scratch, ``project_norms_out``,
+        ``project_scales`` (ones) and ``project_target``, and returns the target norms as a list of floats, one per projected tensor --
+        every conv and Dense kernel but the last Dense's, in layout order.  ``target_norms`` None: the norms of the engine's current
+        parameters, measured once on the device (one host read, here and nowhere else).  Nothing else changes: learn steps, batches and
+        captured updates are those of an engine that never heard of it until ``project_weights`` / ``project_norms`` are called.
+        Noisy engines, batch_norm and the impala torso are refused (ValueError)."""
+        _projection.check_engine(noisy=self.noisy, batch_norm=self.batch_norm, architecture_type=self.architecture_type)
+        n, scratch = ctypes.c_int32(), ctypes.c_int64()
+        _hip.check(self.lib.isdqn_net_project_layout(ctypes.byref(self.cfg), ctypes.byref(n), None, 0, ctypes.byref(scratch)),
+                   "isdqn_net_project_layout")
+        infos = (ctypes.c_int64 * (4 * n.value))()
+        _hip.check(self.lib.isdqn_net_project_layout(ctypes.byref(self.cfg), ctypes.byref(n), infos, n.value, None), "isdqn_net_project_layout")
+        if target_norms is not None:
+            target_norms = _projection.check_targets(target_norms, n.value)
+        self.project_infos = tuple(tuple(int(x) for x in infos[4 * i:4 * i + 4]) for i in range(n.value))
+        self.project_scratch = torch.zeros(max(int(scratch.value) // 8, 1), dtype=torch.float64, device=self.device)
+        self.project_norms_out = torch.zeros(max(n.value, 1), dtype=torch.float64, device=self.device)
+        self.project_scales = torch.ones(max(n.value, 1), dtype=torch.float32, device=self.device)
+        self.project_target = torch.zeros(max(n.value, 1), dtype=torch.float64, device=self.device)
+        if target_norms is None:
+            target_norms = self.project_norms()
+        self.project_target[: n.value].copy_(torch.tensor(target_norms, dtype=torch.float64))
+        return list(target_norms)
+
+    def _project_buffer(self, params):
+        """(buffer, workspace pointer or 0) of a projection call: the engine's own parameters go with their mirror."""
+        if self.project_target is None:
+            raise ValueError(_projection.NAP_NOT_SET_REFUSED)
+        own = params is None
+        p = self.params if own else params
+        assert p.dtype == torch.float32 and p.numel() == self.n_param_floats and p.is_contiguous() and p.device == self.params.device
+        return p, (_hip.ptr(self.workspace) if own else 0)
+
+    def project_norms(self, params=None) -> list:
+        """The norm of every projected tensor of ``params`` (None: the engine's own) as the device measures it
+        (include/isdqn_hip.h, isdqn_net_project_norms): two launches and one host read.  Writes ``project_norms_out`` and no parameter."""
+        p, _ = self._project_buffer(params)
+        _hip.check(self.lib.isdqn_net_project_norms(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.project_norms_out),
+                                                    _hip.ptr(self.project_scratch), _hip.stream_ptr(self.device)), "isdqn_net_project_norms")
+        return [float(x) for x in self.project_norms_out[: len(self.project_infos)].cpu()]
+
+    def project_weights(self, params=None) -> None:
+        """Every projected tensor back to its target norm (include/isdqn_hip.h, isdqn_net_project_apply): two stream-ordered launches,
+        the node behind every gradient step; no host read -- ``project_norms_out`` (before the projection) and ``project_scales`` hold
+        what it measured and applied.  ``params`` None: the engine's own parameters, and the weight mirror is stored with them -- a
+        mirror that was current stays current, one that was not stays marked so.  Another buffer of the layout: that buffer alone,
+        master only -- handing in the engine's own ``params`` that way marks the mirror stale."""
+        p, ws = self._project_buffer(params)
+        _hip.check(self.lib.isdqn_net_project_apply(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.project_target),
+                                                    _hip.ptr(self.project_norms_out), _hip.ptr(self.project_scales),
+                                                    _hip.ptr(self.project_scratch), ws, _hip.stream_ptr(self.device)), "isdqn_net_project_apply")
         if params is not None:
             self._wrote_without_mirror(params)
 

@@ -245,6 +245,12 @@ _SIGNATURES = {
     "isdqn_net_prune_layout": (c_int32, [POINTER(NetConfig), POINTER(c_int32), c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64)]),
     "isdqn_net_prune_update": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isdqn_net_prune_apply": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
+    # Normalize-and-Project (include/isdqn_hip.h, isdqn_net_project_*): layout: cfg, &n_tensors, infos [n][4] int64, max_infos,
+    # &scratch_bytes; norms: cfg, params, norms, scratch, stream; apply: cfg, params, target_norms, norms, scales, scratch, workspace or
+    # NULL, stream
+    "isdqn_net_project_layout": (c_int32, [POINTER(NetConfig), POINTER(c_int32), c_void_p, c_int32, POINTER(c_int64)]),
+    "isdqn_net_project_norms": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isdqn_net_project_apply": (c_int32, [POINTER(NetConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # random ensemble mixture (include/isdqn_hip.h, isdqn_mixture_draw): n_heads, seed, draw count, alpha, stream
     "isdqn_mixture_draw": (c_int32, [c_int32, c_uint64, c_void_p, c_void_p, c_void_p]),
     "isdqn_selftest_gemm": (

@@ -7,7 +7,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from slimdqn import _conservative, _hip, _mixture, _optimizer, _sparsity
+from slimdqn import _conservative, _hip, _mixture, _optimizer, _projection, _sparsity
 from slimdqn._engine import NetOptions, QNetEngine, check_augment, check_noisy, check_redo
 
 
@@ -269,7 +269,7 @@ class EngineAgent:
     def _init_engine_agent(self, key, observation_dim, n_actions, n_heads, features, layer_norm, architecture_type,
                            learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options: NetOptions,
                            batch_norm=False, augment_pad=0, weight_decay=0.0, weight_decay_all=False, cql_alpha=0.0,
-                           prune_sparsity=0.0, prune_start=0, prune_end=0, prune_period=0):
+                           prune_sparsity=0.0, prune_start=0, prune_end=0, prune_period=0, weight_projection=False):
         """``options``: what the constructor picked and checked (NetOptions.check, behind its own rules); the two rules that stand
         behind it follow here.  Every option becomes a plain attribute of the agent and goes to every engine it builds.
         ``augment_pad`` > 0: DrQ random-shift augmentation (Kostrikov et al. 2020; include/isdqn_hip.h, isdqn_replay_augment_shift) --
@@ -286,11 +286,16 @@ class EngineAgent:
         head (QNetEngine.set_conservative): the offline recipe with ``n_quantiles`` is QR-DQN + CQL.  0 is off: the bits of an agent
         built without the argument.  Negative, NaN or infinite: ValueError, before anything is built.
         ``prune_sparsity`` > 0: gradual magnitude pruning (``_init_pruning`` below) from gradient step ``prune_start`` to ``prune_end``,
-        the mask updated every ``prune_period`` steps.  0 is off: the calls and the bits of an agent built without the argument."""
+        the mask updated every ``prune_period`` steps.  0 is off: the calls and the bits of an agent built without the argument.
+        ``weight_projection``: Normalize-and-Project (``_init_projection`` below) -- every gradient step is followed by the projection
+        of every conv and Dense kernel but the last Dense's back to its initial norm.  False is off: the calls and the bits of an agent
+        built without the argument."""
         check_augment(augment_pad, architecture_type)
         check_noisy(options.noisy, architecture_type, batch_norm, options.max_grad_norm)
         self._init_pruning(prune_sparsity, prune_start, prune_end, prune_period, noisy=options.noisy, batch_norm=batch_norm,
                            architecture_type=architecture_type)
+        self._init_projection(weight_projection, layer_norm=layer_norm, noisy=options.noisy, batch_norm=batch_norm,
+                              architecture_type=architecture_type)
         self.weight_decay = _optimizer.check_weight_decay(weight_decay, noisy=options.noisy)
         self.weight_decay_all = bool(weight_decay_all)
         self.cql_alpha = _conservative.check_cql_alpha(cql_alpha)
@@ -357,6 +362,11 @@ class EngineAgent:
                 self._prune = _sparsity.Schedule(*self._prune_args, n_real)
             if old is not None and old.prune_mask is not None:
                 eng.prune_mask.copy_(old.prune_mask)
+        if self.weight_projection:  # (off: no buffer, no call -- the engine is the one built without the option)
+            # the first engine measures the initial parameters; every later one is handed the same target norms
+            self._nap_targets = eng.set_weight_projection(self._nap_targets)
+            if old is not None and old.project_scales is not None:
+                eng.project_scales.copy_(old.project_scales)
         self._drop_graph()  # captured against the old engine's buffers
         self._engine = eng
         if self._trust_mirror is not None:
@@ -811,6 +821,61 @@ class EngineAgent:
             if target is not None:
                 eng.prune_apply(params=target)
         return {"sparsity": self._prune.sparsity}
+
+    # ------------------------------------------------------------------ Normalize-and-Project
+    weight_projection = False  # the option; False: off, call for call
+    _nap_targets = None        # the target norm of every projected tensor: measured once, on the agent's initial parameters
+
+    def _init_projection(self, on, *, layer_norm, noisy, batch_norm, architecture_type) -> None:
+        """Normalize-and-Project (Lyle et al. 2024; include/isdqn_hip.h, isdqn_net_project_*; the rules: slimdqn/_projection.py).  Every
+        conv and Dense kernel but the last Dense's is scaled back to the Frobenius norm it had at initialisation after every gradient
+        step -- right behind the learn call (and behind pruning's apply launch where that is active, so the norm is the masked
+        tensor's) in the eager step, two more launches on the same stream in the captured one, whose key says so.  Biases and LayerNorm
+        vectors are left alone.  The target norms are measured on the first engine's initial parameters and never again: not at a
+        reset, whose fresh draw is simply projected at the next step, not at ReDo, not when an engine for another batch size is built.
+        A DQN target is never projected itself: a hard copy already is, an EMA is a convex combination of projected parameters.
+        Needs ``layer_norm``; refused with noisy layers, batch_norm and the impala torso, before anything is built."""
+        if not on:
+            return
+        _projection.check_network(layer_norm=bool(layer_norm), noisy=bool(noisy), batch_norm=bool(batch_norm),
+                                  architecture_type=architecture_type)
+        self.weight_projection = True
+
+    @property
+    def _nap_first(self) -> bool:
+        """Whether the projection comes directly behind the learn call: the option is on and no prune apply stands in between."""
+        return self.weight_projection and not self.prune_active
+
+    def _nap_learn(self, eng, learn=None):
+        """``learn`` (default: the engine's learn_on_batch) with the projection behind it on the same stream."""
+        learn = eng.learn_on_batch if learn is None else learn
+
+        def projected(cb):
+            learn(cb)
+            eng.project_weights()
+
+        return projected
+
+    def _nap_step(self, kw: dict, eng) -> dict:
+        """What _graphed_update is handed (``learn`` / ``key`` / ``state``; {}: the engine's own learn call) with the projection behind
+        the learn call and a key that says so.  Unchanged while the option is off."""
+        if not self.weight_projection:
+            return kw
+        return dict(kw, learn=self._nap_learn(eng, kw.get("learn")), key=(kw.get("key"), "nap"))
+
+    def _nap_eager(self, eng) -> None:
+        """Behind the learn call (and the prune apply) of an eager gradient step."""
+        if self.weight_projection:
+            eng.project_weights()
+
+    def nap_target_update(self, step: int) -> dict:
+        """The logs of the target update at ``step``, where the losses are read anyway: the smallest and the largest scale the last
+        gradient step applied.  Scales that sit at 1 say the run is not growing its norms; at 0.99 it would lose 2 % of its effective
+        learning rate per step without the option.  {} while the option is off."""
+        if not self.weight_projection:
+            return {}
+        eng = self._engine
+        return _projection.scale_logs(eng.project_scales[: len(eng.project_infos)].cpu().numpy())
 
     # ------------------------------------------------------------------ periodic resets
     _resets = 0  # resets done so far: selects the seed of the next fresh parameters

@@ -62,6 +62,7 @@ class DQN(EngineAgent):
         prune_end: int = 0,
         prune_period: int = 0,
         rem_heads: int = 0,
+        weight_projection: bool = False,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
@@ -81,6 +82,8 @@ class DQN(EngineAgent):
         ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning) of
         the online parameters; the target buffer is masked at every mask update, and the apply launch of a gradient step comes in front
         of the EMA, so the target's zeros stay zero under the hard copy and under ``ema_tau``.
+        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection) of the online parameters, behind the prune apply and
+        in front of the EMA; the target buffer is never projected itself.
         ``rem_heads`` = H > 0: REM, the random ensemble mixture (Agarwal et al. 2020; include/isdqn_hip.h, isdqn_batch_mixture) -- the
         network has H heads on one torso, every gradient step (eager and captured: one more node in front of the learn call, on the
         step's stream) draws a new convex combination of the heads on the device and regresses the mixture on the target network's
@@ -102,7 +105,7 @@ class DQN(EngineAgent):
         self._init_engine_agent(key, observation_dim, n_actions, max(H, 1), features, layer_norm, architecture_type, learning_rate,
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, options, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
                                 cql_alpha=cql_alpha, prune_sparsity=prune_sparsity, prune_start=prune_start, prune_end=prune_end,
-                                prune_period=prune_period)
+                                prune_period=prune_period, weight_projection=weight_projection)
         self.target_params = self.params.copy()  # dqn.py:34
         self.target_sigma = self._engine.sigma.clone() if self.noisy else None  # (one persistent buffer, refreshed in place like the target)
         self.cumulated_loss = 0
@@ -124,6 +127,14 @@ class DQN(EngineAgent):
             pruned = self.prune_active  # (the apply launch right behind the learn call, in front of the EMA; the key says it is there)
             if pruned:
                 step_learn = self._prune_learn(eng, step_learn)
+            nap = self.weight_projection  # (the projection behind the prune apply, in front of the EMA: the target averages projected
+            if nap:                       # parameters and is never projected itself; the key says it is there)
+                step_learn = self._nap_learn(eng, step_learn)
+
+            def tagged(key):
+                key = (key, "prune") if pruned else key
+                return (key, "nap") if nap else key
+
             if self.ema_tau > 0.0:
                 # the learn call and the EMA of the target behind it, enqueued on one stream: the captured step gets no new branch.
                 # (the target buffers are state of the step now: a capture's warm-up must not move them)
@@ -132,17 +143,18 @@ class DQN(EngineAgent):
                     self._ema_target(eng, target)
 
                 key = (target.data_ptr(), self.ema_tau) + (("rem",) if self.rem_heads else ())
-                g = self._graphed_update(replay_buffer, learn=learn, key=(key, "prune") if pruned else key,
+                g = self._graphed_update(replay_buffer, learn=learn, key=tagged(key),
                                          state=[target] + ([self.target_sigma] if self.noisy else []) + rem_state)
             else:
                 key = (target.data_ptr(), "rem") if self.rem_heads else target.data_ptr()
-                g = self._graphed_update(replay_buffer, learn=step_learn, key=(key, "prune") if pruned else key, state=rem_state)
+                g = self._graphed_update(replay_buffer, learn=step_learn, key=tagged(key), state=rem_state)
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
                 self._run_graph(g)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.target_params, self.optimizer_state, batch_samples)
             self._prune_eager(self._engine)
+            self._nap_eager(self._engine)
             if self.ema_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
                 self._ema_target(self._engine, target)
             if getattr(self, "priority_writeback", False) and hasattr(replay_buffer, "update_device"):  # (as the captured step does)

@@ -72,6 +72,7 @@ class iSDQN(EngineAgent):
         prune_start: int = 0,
         prune_end: int = 0,
         prune_period: int = 0,
+        weight_projection: bool = False,
     ):
         """The option keywords from ``huber_delta`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Here ``double_q`` lets online head 1 + k pick the next action that head k values, and
@@ -82,7 +83,9 @@ class iSDQN(EngineAgent):
         one, on the step's own stream; ``update_target_params`` then shifts nothing and only reports its logs.  0 keeps the hard shift
         every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
         ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning);
-        the apply launch comes behind the soft shift where both are on."""
+        the apply launch comes behind the soft shift where both are on.
+        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection): in front of the soft shift, or -- where pruning is
+        active -- directly behind its apply launch (the soft shift writes the last Dense alone, which neither of the two touches)."""
         options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
         self.soft_shift_tau = check_soft_shift_tau(soft_shift_tau, supported=True)
@@ -101,7 +104,7 @@ class iSDQN(EngineAgent):
                                 learning_rate, gamma, update_horizon, adam_eps, batch_size, precision, device, options,
                                 batch_norm=batch_norm, augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
                                 cql_alpha=cql_alpha, prune_sparsity=prune_sparsity, prune_start=prune_start, prune_end=prune_end,
-                                prune_period=prune_period)
+                                prune_period=prune_period, weight_projection=weight_projection)
         self._action_rng = np.random.default_rng(self._seed + 1)
         self.cumulated_losses = np.zeros(self.n_bellman_iterations)
 
@@ -140,9 +143,14 @@ class iSDQN(EngineAgent):
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
+            nap_first = self._nap_first
+            if nap_first:
+                self._nap_eager(self._engine)
             if self.soft_shift_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
                 self._engine.soft_shift(self.soft_shift_tau)
             self._prune_eager(self._engine)
+            if not nap_first:
+                self._nap_eager(self._engine)
             if self.priority_writeback and hasattr(replay_buffer, "update_device"):
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_losses += losses` (isdqn.py:62) happens on the device inside the step
@@ -150,19 +158,24 @@ class iSDQN(EngineAgent):
     def _soft_shift_step(self, replay_buffer) -> dict:
         """What _graphed_update is handed under ``soft_shift_tau`` > 0: the learn call and the soft shift behind it, enqueued on one
         stream -- the captured step gets one more node and no new branch -- and a key that holds the tau.  {} without.  With pruning
-        active the apply launch follows as one more node (EngineAgent._prune_step)."""
-        if not (self.soft_shift_tau > 0.0 or self.prune_active):
+        active the apply launch follows as one more node (EngineAgent._prune_step).  With ``weight_projection`` the projection comes
+        in front of the soft shift, or directly behind the prune apply where that is active (EngineAgent._nap_step)."""
+        if not (self.soft_shift_tau > 0.0 or self.prune_active or self.weight_projection):
             return {}
         eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
-        if not self.soft_shift_tau > 0.0:
-            return self._prune_step({}, eng)
-        tau = self.soft_shift_tau
+        nap_first = self._nap_first
+        kw = self._nap_step({}, eng) if nap_first else {}
+        if self.soft_shift_tau > 0.0:
+            tau = self.soft_shift_tau
+            first = kw.get("learn", eng.learn_on_batch)
 
-        def learn(cb):
-            eng.learn_on_batch(cb)
-            eng.soft_shift(tau)
+            def learn(cb):
+                first(cb)
+                eng.soft_shift(tau)
 
-        return self._prune_step(dict(learn=learn, key=("soft_shift", tau)), eng)
+            kw = dict(learn=learn, key=(kw["key"], "soft_shift", tau) if kw else ("soft_shift", tau))
+        kw = self._prune_step(kw, eng)
+        return kw if nap_first else self._nap_step(kw, eng)
 
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:

@@ -65,6 +65,7 @@ class TFDQN(EngineAgent):
         prune_start: int = 0,
         prune_end: int = 0,
         prune_period: int = 0,
+        weight_projection: bool = False,
     ):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to target-free DQN:
@@ -72,7 +73,8 @@ class TFDQN(EngineAgent):
         ``munchausen_tau`` > 0 is, unlike ``double_q``, well defined here: the single head is regularised by its own stop-gradient policy.
         ``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.  ``weight_decay`` / ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term
         (EngineAgent._init_engine_agent).  ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head, nothing to shift.
-        ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning)."""
+        ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning).
+        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection), behind the prune apply."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
         options = NetOptions.pick(locals())
@@ -87,15 +89,16 @@ class TFDQN(EngineAgent):
                                 gamma, update_horizon, adam_eps, batch_size, precision, device, options, batch_norm=batch_norm,
                                 augment_pad=augment_pad, weight_decay=weight_decay, weight_decay_all=weight_decay_all,
                                 cql_alpha=cql_alpha, prune_sparsity=prune_sparsity, prune_start=prune_start, prune_end=prune_end,
-                                prune_period=prune_period)
+                                prune_period=prune_period, weight_projection=weight_projection)
         self.cumulated_loss = 0
 
     # ------------------------------------------------------------------ tfdqn.py:38-54
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
             kw = {}
-            if self.prune_active:  # (the apply launch as one more node of the captured step)
-                kw = self._prune_step({}, self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine)
+            if self.prune_active or self.weight_projection:  # (the apply launch, then the projection, as further nodes of the captured step)
+                eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
+                kw = self._nap_step(self._prune_step({}, eng), eng)
             g = self._graphed_update(replay_buffer, **kw)
             if g is not None:
                 self._run_graph(g)  # same draws, same kernels, same bits as the eager branch below
@@ -103,6 +106,7 @@ class TFDQN(EngineAgent):
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
             self._prune_eager(self._engine)
+            self._nap_eager(self._engine)
 
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:
