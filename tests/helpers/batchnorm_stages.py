@@ -1,7 +1,8 @@
 """float64 restatements of each stage of the BatchNorm learn path (csrc/batchnorm.h) on given operands, each with the error bound
 the kernel's own fp32 arithmetic may use, and of the plan's BatchNorm sites (csrc/net_plan.h: BnSite).  torch float64 on the
 device of the inputs, like bf16_model.py: nothing here needs a GPU.  tests/test_batchnorm_stages_host.py checks every function
-against torch autograd and the oracle on the CPU; tests/test_gpu_batchnorm.py runs them on the HIP run's own tensors.
+against torch autograd and the oracle on the CPU; tests/test_gpu_batchnorm.py runs them on the HIP run's own tensors (cnn, fc), and
+tests/test_gpu_impala_backward.py on the impala torso's sites (layers / site_layout with arch="impala").
 
 Layout: a site's tensor is [N][P][Cp] -- rows, positions, channels padded to 8.  A spatial site (BatchNorm(axis=(1, 2)) on an image)
 keeps one statistic per position p over the rows AND the C true channels; a feature site one per internal column p * Cp + c over
@@ -72,11 +73,29 @@ def _same(size, k, s):
     return out, max((out - 1) * s + k - size, 0) // 2
 
 
+def impala_geometry(cfg):
+    """the three Stacks of an impala case (impala_stages.geometry: H, W, Hp, Wp, pad, cin, cin_p, C, C_p)"""
+    from tests.helpers import impala_stages as IS
+
+    geo = IS.geometry(cfg["obs"], cfg["feats"])
+    assert geo is not None, "the plan refuses this observation (the two sides need different pool padding)"
+    return geo
+
+
 def layers(cfg):
-    """Hidden layers of a BatchNorm cnn / fc plan in order: name, kind (0 conv, 1 dense), LayerNorm name, c / cp (true / padded
-    width), npix, conv k / s / hin / win / hout / wout / cin / cin_p, K (contraction length) and in_p (dense input width)."""
+    """Hidden layers of a BatchNorm cnn / fc / impala plan in order: name, kind (0 conv, 1 dense, 2 the impala torso as one layer),
+    LayerNorm name, c / cp (true / padded width), npix, conv k / s / hin / win / hout / wout / cin / cin_p, K (contraction length)
+    and in_p (dense input width)."""
     out, n_ln, ln = [], 0, cfg["ln"]
-    if cfg["arch"] == "cnn":
+    if cfg["arch"] == "impala":
+        # the torso is ONE hidden layer (net_plan.h: the pseudo-layer "Impala", kind 2): the residual stream behind Stack_2 with the
+        # top-level LayerNorm_0 and the ReLU behind it, in a conv layer's output geometry; the Dense layers follow it
+        g = impala_geometry(cfg)[-1]
+        co, cp, npix = g["C"], g["C_p"], g["Hp"] * g["Wp"]
+        out.append(dict(name="Impala", kind=2, ln="LayerNorm_0" if ln else None, c=co, cp=cp, npix=npix, hout=g["Hp"], wout=g["Wp"]))
+        n_ln += ln
+        in_f, in_p, dense = npix * co, npix * cp, cfg["feats"][3:]
+    elif cfg["arch"] == "cnn":
         h, w, c = cfg["obs"]
         cp = 8  # the input site's S8 rows: 8-padded channels
         for i, (k, s) in enumerate(CONVS):
@@ -101,15 +120,31 @@ def layers(cfg):
 
 def site_layout(cfg):
     """BatchNorm sites in Flax's call order: name ("BatchNorm_i"), region prefix "bn/<name>/", the hidden layer whose activation
-    the site normalises (-1: the cnn's input x / 255), the region holding its input, spatial, P, C, Cp, G (statistic groups:
-    P for a spatial site, P * Cp internal columns for a feature site) and the Flax shape of its scale / bias / mean / var."""
+    the site normalises (-1: the cnn's / impala's input x / 255), the region holding its input, spatial, P, C, Cp, G (statistic
+    groups: P for a spatial site, P * Cp internal columns for a feature site) and the Flax shape of its scale / bias / mean / var.
+    impala (net_plan.h: plan_impala_torso, place_bn_regions): the input site on bn/x0, then inside every Stack s the two block sites
+    "Stack_s/BatchNorm_b" (layer -2 - (2 s + b), as BnSite.layer) on imp/s{s}/a1_{b} -- spatial, one statistic per pooled pixel --
+    then the feature site behind the flatten on act/Impala and the Dense sites; the top-level sites count on their own
+    (BatchNorm_0, BatchNorm_1, ...), the block sites are named inside their Stack."""
     out = []
+    n_top = [0]
 
-    def add(layer, src, spatial, P, C, Cp, shape):
-        name = f"BatchNorm_{len(out)}"
+    def add(layer, src, spatial, P, C, Cp, shape, name=None):
+        if name is None:
+            name = f"BatchNorm_{n_top[0]}"
+            n_top[0] += 1
         out.append(dict(name=name, prefix=f"bn/{name}/", layer=layer, src=src, spatial=bool(spatial), P=P, C=C, Cp=Cp, G=P if spatial else P * Cp,
                         flax_shape=shape))
 
+    if cfg["arch"] == "impala":
+        h, w, c = cfg["obs"]
+        add(-1, "bn/x0", True, h * w, c, 8, (h, w))
+        for s, g in enumerate(impala_geometry(cfg)):
+            for b in range(2):
+                add(-2 - (2 * s + b), f"imp/s{s}/a1_{b}", True, g["Hp"] * g["Wp"], g["C"], g["C_p"], (g["Hp"], g["Wp"]), name=f"Stack_{s}/BatchNorm_{b}")
+        for i, L in enumerate(layers(cfg)):
+            add(i, f"act/{L['name']}", False, L["npix"], L["c"], L["cp"], (L["npix"] * L["c"],))
+        return out
     if cfg["arch"] == "cnn":
         h, w, c = cfg["obs"]
         add(-1, "bn/x0", True, h * w, c, 8, (h, w))

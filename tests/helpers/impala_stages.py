@@ -2,7 +2,8 @@
 (csrc/net_plan.h): the frame decode, the 3x3 / 2 SAME max-pool with its winners and its backward, the ReLU-mask + S8 conversion
 with its column sums, the residual add.  torch on the device of the inputs (float64 wherever a sum is taken), like bf16_model.py:
 nothing here needs a GPU, tests/test_impala_stages_host.py checks every function against torch / the oracle on the CPU, and the GPU
-test (tests/test_gpu_impala.py) runs them on the HIP run's own tensors.
+tests (tests/test_gpu_impala.py; tests/test_gpu_impala_backward.py for block_backward and what it is built from: one residual block
+of impala_backward with every intermediate, every leaf and the bound each carries) run them on the HIP run's own tensors.
 
 The tie rule of the pool: the winner of a window is the FIRST maximum in row-major window order (ky * 3 + kx) among the positions
 inside the image -- what `vv[e] > best[e]` gives in imp_pool_fwd_kernel, what `a == ky * 3 + kx` reads back in
@@ -138,6 +139,167 @@ def to_s8_masked(d, mask_hi=None):
 def residual_add(a, b):
     """imp_add_kernel: one float32 addition per element"""
     return torch.as_tensor(a).to(torch.float32) + torch.as_tensor(b).to(torch.float32)
+
+
+# ------------------------------------------------------------------ the cases of tests/test_gpu_impala_backward.py
+# The smallest shapes that still force each route (the first two are STAGE_CASES of tests/test_gpu_impala.py).
+BACKWARD_CASES = {
+    # 84x84: B 42 42 = 7056 rows, the row kernels' grid-stride loop twice
+    "tiny-ln-B4": dict(arch="impala", obs=(84, 84, 4), feats=(8, 16, 16, 24), K=2, A=5, B=4, ln=True, bn=False),
+    # C_p 16 / 24 / 16, a ragged last 16-row block, H != W
+    "nonsquare-44x36x3-noln-B2": dict(arch="impala", obs=(44, 36, 3), feats=(12, 20, 9, 16), K=3, A=4, B=2, ln=False, bn=False),
+    # Stacks 1 and 2 (C_p 40, 64) take launch_conv_fwd<64> and launch_conv_dgrad<64>
+    "wide-20x20x2-ln-B3": dict(arch="impala", obs=(20, 20, 2), feats=(16, 40, 64, 24), K=2, A=4, B=3, ln=True, bn=False),
+    # BatchNorm: the backward runs over the 2B = 4 rows, 4 * 1764 = 7056 rows of Stack 0's blocks: the loop twice
+    "bn-84x84x4-noln-B2": dict(arch="impala", obs=(84, 84, 4), feats=(8, 16, 8, 32), K=2, A=3, B=2, ln=False, bn=True),
+    # BatchNorm with LayerNorm, padded channels at every site, C = 3 < Cp = 8 at the input site
+    "bn-44x36x3-ln-B3": dict(arch="impala", obs=(44, 36, 3), feats=(12, 20, 9, 16), K=3, A=4, B=3, ln=True, bn=True),
+}
+BACKWARD_RUNS = [(c, "bf16x3") for c in BACKWARD_CASES] + [(c, "bf16") for c in ("tiny-ln-B4", "wide-20x20x2-ln-B3", "bn-44x36x3-ln-B3")]
+
+
+def conv_routes(geo):
+    """Per Stack the template width of its convolutions' launches (csrc/impala.h): imp_conv_fwd takes launch_conv_fwd<32> for
+    cout_p <= 32, else <64>; impala_backward's dgrad takes launch_conv_dgrad<32> for cin_p <= 32, else <64>.  Returns per Stack
+    dict(fwd0, fwd_block, dgrad0, dgrad_block): Conv_0 maps cin_p -> C_p, the block convolutions C_p -> C_p."""
+    bm = lambda p: 32 if p <= 32 else 64
+    return [dict(fwd0=bm(g["C_p"]), fwd_block=bm(g["C_p"]), dgrad0=bm(g["cin_p"]), dgrad_block=bm(g["C_p"])) for g in geo]
+
+
+# ------------------------------------------------------------------ one residual block of impala_backward
+# A MODELLED fp32 tensor v (error bound E against the kernel's own fp32 tensor) that a kernel splits into S8 planes and contracts:
+# the model contracts split(v).  Where the kernel's planes can differ from the model's at all (model_planes says where), they do
+# so by, per element of the modelled operand and relative to the OTHER operand's whole magnitude (|hi| + |lo|):
+#   three passes   |(hi + lo) - (hi' + lo')| <= E + U |v| (the model's own rounding to fp32) + 2 S8_STORE |v| (each side's lo half
+#                  is rounded); and hi may differ from hi' by a whole bf16 ulp, at most 2^-7 |v| (+ E), which only the product
+#                  hi * lo' sees: |lo'| <= 2^-8 |w| (half an ulp at the bottom of a binade), so 2^-15 |v| |w| more.  Together
+#                  E + (6 S8_STORE + 2 U) |v|;
+#   one pass       hi against hi': E + 2^-7 |v| -- a whole bf16 ulp, further than the two pass counts are apart.  Charged to every
+#                  element, that would bury a single-pass chain; model_planes charges it only where hi can flip, which at one
+#                  pass is about E / 2^-8 |v| of the elements, so the chain holds in single-pass bf16 as well.
+# tests/test_impala_stages_host.py holds both to operands that sit exactly between two bf16 values.
+SPLIT_MODEL = {3: 6 * M.S8_STORE + 2 * M.U, 1: 2.0**-7 + 2 * M.U}
+DGRAD_EPILOGUE = 4  # launch_conv_dgrad's fp32 operations behind the K chain, as tests/test_gpu_batchnorm.py counts them
+
+
+def model_planes(v, E, passes, split=M.split):
+    """(planes, E_planes) of a modelled operand v whose kernel counterpart lies within E of it.  Rounding is monotone: where
+    split(v - E) and split(v + E) are the same planes (the hi plane alone at one pass, which reads nothing else), every fp32 value
+    between them splits to those planes too, so the kernel contracts exactly what the model does and that element carries no error
+    at all.  Elsewhere the interval crosses a rounding boundary of hi or lo and the element carries E + SPLIT_MODEL |v|.
+    `split`: the host test's exact variant passes (v, None) and E through."""
+    if split is not M.split:
+        return split(v), E
+    below, above = split(v - E), split(v + E)
+    stable = below[0] == above[0]
+    if passes != 1:
+        stable = stable & (below[1] == above[1])
+    return split(v), torch.where(stable, torch.zeros_like(E), E + SPLIT_MODEL[passes] * v.abs())
+
+
+def row_chain(rows):
+    """fp32 additions one value of a row-wise kernel's column sum goes through (imp_to_s8_kernel's bpart, imp_lnrelu_bwd_kernel's
+    lnpart, then adam_kernel's sum of the workgroups' partial rows): a lane's rows in sequence, the 16 row groups of its workgroup,
+    the workgroups."""
+    blocks, per_lane = row_blocks(rows)
+    return per_lane + ROWS_PER_BLOCK + blocks
+
+
+def dgrad_depth(cout_p):
+    """c of launch_conv_dgrad<32 | 64, passes> on a 3x3 / 1 convolution: one accumulator over K = 9 cout_p (net_launch.h: Kc = T T cout_p,
+    T = 3), no split-K."""
+    return M.chain_depth(9 * cout_p, 1, DGRAD_EPILOGUE)
+
+
+def wgrad_depth(n_img, npix, cin_p):
+    """c of a block convolution's weight gradient on the generic engine (conv_wgrad_slabs), as the Conv_0 row of the forward test"""
+    steps, slabs = wgrad_chain(n_img, npix, 9 * cin_p)
+    return M.ROUNDING * (M.MFMA_TREE + steps + slabs + 2)
+
+
+def _abs_planes(p):
+    return (p[0].abs() if p[1] is None else p[0].abs() + p[1].abs(), None)
+
+
+def column_sums(v, E_v, rows):
+    """(sum, bound) over every leading axis of v [..., C]: the bias leaf of the convolution whose output gradient v is"""
+    C = v.shape[-1]
+    flat = lambda t: t.reshape(-1, C)
+    return flat(v).sum(0), flat(E_v).sum(0) + M.bound(flat(v).abs().sum(0), M.ROUNDING * row_chain(rows))
+
+
+def conv_leaves(passes, x, dz, E_dz, c_w, split=M.split):
+    """kernel leaf of a 3x3 / 1 SAME convolution from its own input planes x [N][H][W][Cin] and a MODELLED output gradient dz
+    [N][H][W][Cout] with bound E_dz: (gw HWIO, E_gw)."""
+    N, H, W, C = dz.shape
+    dp, E_p = model_planes(dz, E_dz, passes, split)
+    flat = lambda p: tuple(None if t is None else t.reshape(N, H * W, C) for t in p)
+    gw, S = M.conv_wgrad(passes, x, flat(dp), 3, 1)
+    carried, _ = M.conv_wgrad(1, _abs_planes(x), (E_p.reshape(N, H * W, C), None), 3, 1)
+    return gw, carried + M.bound(S, c_w)
+
+
+def conv_data_gradient(passes, dz, E_dz, w, split=M.split):
+    """data gradient of a 3x3 / 1 SAME convolution from a MODELLED output gradient dz [N][H][W][Cout] (bound E_dz) and the weights'
+    planes w (HWIO): (da [N][H][W][Cin], E_da)."""
+    N, H, W, C = dz.shape
+    cin = w[0].shape[2]
+    dp, E_p = model_planes(dz, E_dz, passes, split)
+    flat = lambda p: tuple(None if t is None else t.reshape(N, H * W, C) for t in p)
+    da, S = M.conv_dgrad(passes, flat(dp), w, (H, W), 1)
+    carried, _ = M.conv_dgrad(1, (E_p.reshape(N, H * W, C), None), _abs_planes(w), (H, W), 1)
+    E = carried + M.bound(S, dgrad_depth(-(-C // 8) * 8))
+    return da.reshape(N, H, W, cin), E.reshape(N, H, W, cin)
+
+
+def block_backward(passes, G, E_G, r, mask1, x1, a2, w1, w2, gamma, has_ln, bn=None, split=M.split):
+    """Residual block b of impala_backward in the kernel's order, in float64, on true channels:
+        stream = Conv_{2+2b}(a2) + r,  a2 = relu(Conv_{1+2b}(x1)),  x1 = [BatchNorm](a1),  a1 = relu([LayerNorm](r)).
+    G [N][Hp][Wp][C]: the gradient of the stream above the block (a model) with its bound E_G; r: the block's own fp32 input;
+    mask1: its own first ReLU decisions (a1 > 0); x1, a2: the own S8 planes the two convolutions read; w1, w2: the planes of the two
+    kernels (HWIO); gamma: LayerNorm scale [C] (has_ln).  bn: dict(x = a1 [N][P][Cp] float64, mean, var, scale [P], s1, s2 = the
+    run's own sums or None) -- the block's BatchNorm site between the first convolution's data gradient and the LayerNorm backward.
+    Stages, each with its first-order bound (E carried through the contraction with magnitudes + the stage's own bound(S, c)):
+        to_s8(G)            -> bias2 = column sums of G;                      planes of G (model_planes)
+        wgrad, dgrad of Conv_{2+2b}: gw2 on own a2; da2
+        to_s8(da2, a2 > 0)  -> v = da2 [a2 > 0], bias1 = column sums of v;   planes of v
+        wgrad, dgrad of Conv_{1+2b}: gw1 on own x1; da1
+        bn_backward         -> s1, s2, da1 <- dx (in place in the kernel)
+        ln_relu_bwd         -> dz; ln_param_grads -> dgamma, dbeta;  G_out = G + dz (one fp32 addition)
+    Returns a dict of every intermediate X with its bound E_X."""
+    from tests.helpers import batchnorm_stages as BS
+
+    N, Hp, Wp, C = G.shape
+    C_p = -(-C // 8) * 8
+    rows = N * Hp * Wp
+    c_w = wgrad_depth(N, Hp * Wp, C_p)
+    out = dict(G_in=G, E_G_in=E_G)
+    out["bias2"], out["E_bias2"] = column_sums(G, E_G, rows)
+    out["gw2"], out["E_gw2"] = conv_leaves(passes, a2, G, E_G, c_w, split)
+    da2, E_da2 = conv_data_gradient(passes, G, E_G, w2, split)
+    mask2 = (a2[0] > 0).to(G.dtype)
+    v, E_v = da2 * mask2, E_da2 * mask2
+    out.update(da2=da2, E_da2=E_da2, v=v, E_v=E_v, mask2=mask2)
+    out["bias1"], out["E_bias1"] = column_sums(v, E_v, rows)
+    out["gw1"], out["E_gw1"] = conv_leaves(passes, x1, v, E_v, c_w, split)
+    da1, E_da1 = conv_data_gradient(passes, v, E_v, w1, split)
+    out.update(da1=da1, E_da1=E_da1)
+    if bn is not None:
+        pad = lambda t: BS._pad_channels(t.reshape(N, Hp * Wp, C), C_p)
+        dy, E_dy = pad(da1), pad(E_da1)
+        s1, d_s1, s2, d_s2, _, _ = BS.bn_backward(bn["x"], dy, bn["mean"], bn["var"], bn["scale"], True, C, E_dy=E_dy)
+        _, _, _, _, dx, d_dx = BS.bn_backward(bn["x"], dy, bn["mean"], bn["var"], bn["scale"], True, C, E_dy=E_dy, s1=bn.get("s1"), s2=bn.get("s2"))
+        out.update(s1=s1, E_s1=d_s1, s2=s2, E_s2=d_s2)
+        da1, E_da1 = dx[..., :C].reshape(N, Hp, Wp, C), d_dx[..., :C].reshape(N, Hp, Wp, C)
+        out.update(dx=da1, E_dx=E_da1)
+    mask1 = mask1.to(G.dtype)
+    dz, E_dz = M.ln_relu_bwd(r, gamma, mask1, da1, E_da1, has_ln=has_ln)
+    out.update(dz=dz, E_dz=E_dz, mask1=mask1)
+    if has_ln:
+        out["dgamma"], out["E_dgamma"], out["dbeta"], out["E_dbeta"] = M.ln_param_grads(r, mask1, da1, E_da1, row_chain(rows))
+    G_out = G + dz
+    out.update(G_out=G_out, E_G_out=E_G + E_dz + M.ROUNDING * M.U * G_out.abs())
+    return out
 
 
 # ------------------------------------------------------------------ structured frames (flat backgrounds, rectangles)

@@ -133,8 +133,8 @@ def _net_cfg(cfg):
     from slimdqn import _hip
 
     c = _hip.NetConfig()
-    c.arch = _hip.ARCH_CNN if cfg["arch"] == "cnn" else _hip.ARCH_FC
-    if cfg["arch"] == "cnn":
+    c.arch = {"cnn": _hip.ARCH_CNN, "impala": _hip.ARCH_IMPALA, "fc": _hip.ARCH_FC}[cfg["arch"]]
+    if cfg["arch"] != "fc":
         c.obs_h, c.obs_w, c.obs_c = cfg["obs"]
     else:
         c.obs_h = c.obs_w = 1
@@ -192,6 +192,67 @@ def test_site_layout_matches_the_engines_parameter_layout_and_regions(case):
         assert sites[-1]["G"] == 512 and sites[3]["G"] == 11 * 11 * 64
     if case == "fc-d6-B37":
         assert N2 == 74 and N2 % 8 == 2 and sites[0]["G"] == 304 and 256 < 304 < 512 and cfg["n_heads"] == 1
+
+
+@pytest.mark.parametrize("case", list(IS.BACKWARD_CASES))
+def test_impala_site_layout_matches_the_oracle_the_parameter_layout_and_the_regions(case):
+    """Every case of tests/test_gpu_impala_backward.py, planned with BatchNorm: the sites' names and Flax shapes are the oracle's
+    (init_params(..., batch_norm=True), init_batch_stats) in Flax's call order, and name / kind / dims / region sizes are the
+    engine's own (host arithmetic of the plan: plan_impala_torso, place_bn_regions)."""
+    from slimdqn import _hip
+
+    cfg = dict(IS.BACKWARD_CASES[case], n_heads=1 + IS.BACKWARD_CASES[case]["K"])
+    sites = BS.site_layout(cfg)
+    params = onet.init_params(0, cfg["obs"], list(cfg["feats"]), "impala", cfg["n_heads"] * cfg["A"], cfg["ln"], batch_norm=True)
+    stats = onet.init_batch_stats(params)
+    assert [s["name"] for s in sites] == [m for m in params if m.rsplit("/", 1)[-1].startswith("BatchNorm_")] == list(stats)
+    assert [s["name"] for s in sites] == ["BatchNorm_0"] + [f"Stack_{s}/BatchNorm_{b}" for s in range(3) for b in range(2)] + [
+        f"BatchNorm_{1 + j}" for j in range(len(cfg["feats"]) - 2)]
+    for s in sites:
+        for leaf in ("scale", "bias"):
+            assert params[s["name"]][leaf].shape == tuple(s["flax_shape"]), (s["name"], leaf)
+        for leaf in ("mean", "var"):
+            assert stats[s["name"]][leaf].shape == tuple(s["flax_shape"]), (s["name"], leaf)
+    geo = IS.geometry(cfg["obs"], cfg["feats"])
+    assert [s["src"] for s in sites[:8]] == ["bn/x0"] + [f"imp/s{s}/a1_{b}" for s in range(3) for b in range(2)] + ["act/Impala"]
+    assert [s["layer"] for s in sites] == [-1] + [-2 - k for k in range(6)] + list(range(len(cfg["feats"]) - 2))
+    assert [s["spatial"] for s in sites] == [True] * 7 + [False] * (len(sites) - 7)
+    assert [(s["P"], s["C"], s["Cp"]) for s in sites[1:7]] == [(g["Hp"] * g["Wp"], g["C"], g["C_p"]) for g in geo for _ in range(2)]
+    assert (sites[7]["P"], sites[7]["C"], sites[7]["Cp"]) == (geo[2]["Hp"] * geo[2]["Wp"], geo[2]["C"], geo[2]["C_p"])
+
+    c = _net_cfg(cfg)
+    n, cnt = ctypes.c_int64(), ctypes.c_int32()
+    _hip.check(_hip.lib().isdqn_net_param_layout(ctypes.byref(c), ctypes.byref(n), None, 0, ctypes.byref(cnt)))
+    infos = (_hip.TensorInfo * cnt.value)()
+    _hip.check(_hip.lib().isdqn_net_param_layout(ctypes.byref(c), ctypes.byref(n), infos, cnt.value, ctypes.byref(cnt)))
+    by_name = {i.name.decode(): i for i in infos if i.kind >= 5}
+    assert len(by_name) == 4 * len(sites)
+    N2 = 2 * cfg["B"]
+
+    def region_floats(name):
+        off, size = ctypes.c_int64(), ctypes.c_int64()
+        _hip.check(_hip.lib().isdqn_net_workspace_region(ctypes.byref(c), name.encode(), ctypes.byref(off), ctypes.byref(size)))
+        return size.value // 4
+
+    for s in sites:
+        for kind, leaf in ((5, "scale"), (6, "bias"), (7, "mean"), (8, "var")):
+            i = by_name[f"{s['name']}/{leaf}"]
+            assert i.kind == kind and list(i.dims)[:4] == [s["G"], s["P"], s["C"], s["Cp"]], (s["name"], leaf, list(i.dims))
+            assert tuple(i.flax_shape[: i.ndim]) == tuple(s["flax_shape"]) and i.size == _up(s["G"], 8)
+        assert region_floats(s["prefix"] + "out") == _up(N2 * s["P"] * s["Cp"], 64)
+        assert region_floats(s["src"]) == _up(N2 * s["P"] * s["Cp"], 64)
+        for r in ("mean", "var", "dbias", "dscale"):
+            assert region_floats(s["prefix"] + r) == _up(_up(s["G"], 8), 64)
+    for l in BS.layers(cfg):
+        for r in ("act", "z", "dz"):  # with BatchNorm the backward runs over all 2B rows
+            assert region_floats(f"{r}/{l['name']}") == _up(N2 * l["npix"] * l["cp"], 64)
+    for s, g in enumerate(geo):  # and so does the torso's: its gradient regions hold 2B images
+        assert region_floats(f"imp/s{s}/dz0") == _up(N2 * g["H"] * g["W"] * g["C_p"], 64)
+        assert region_floats(f"imp/s{s}/da") == _up(N2 * max(g["H"] * g["W"] * g["cin_p"], g["Hp"] * g["Wp"] * g["C_p"]), 64)
+    if case == "bn-84x84x4-noln-B2":
+        assert IS.row_blocks(N2 * 42 * 42) == (256, 2)  # the 2B-row backward's grid-stride loop runs twice
+    if case == "bn-44x36x3-ln-B3":
+        assert all(s["C"] < s["Cp"] for s in sites[:8]) and (sites[0]["C"], sites[0]["Cp"]) == (3, 8)
 
 
 # ------------------------------------------------------------------ the GPU cases separate the references from wrong variants

@@ -362,8 +362,10 @@ def test_batchnorm_stages_match_a_model_of_each_kernel_on_its_own_operands(case,
     workspace: bn/x0, every bn/<site>/out from its own input and the running averages, every act/<layer> through the model of its
     contraction (z is not stored by forward), q from the last site's out, with the pass-count control.
 
-    Not covered: the impala + BatchNorm sites ("Stack_s/BatchNorm_b" reuse these six kernels; the impala stage test in
-    tests/test_gpu_impala.py covers that torso's own kernels), the LayerNorm scale / bias leaves (as in test_gpu_bf16_model.py).
+    The impala torso's BatchNorm sites (the input site on bn/x0, "Stack_s/BatchNorm_b" on imp/s{s}/a1_{b}, the feature site on
+    act/Impala: the same six kernels) are held the same way in tests/test_gpu_impala_backward.py, forward, backward, running averages
+    and acting.  Not covered here: the LayerNorm scale / bias leaves (tests/test_gpu_dense_routes.py, and the impala blocks' in
+    tests/test_gpu_impala_backward.py).
 
     Measured on the MI355X, max over the 6 runs (max |d| / bound; against 2^-24 S where S is the whole bound, with c):
       mean 0.139, var 0.118                      bn/<site>/out 0.971 (S8 storage's worst case 2^-17 |y| dominates)

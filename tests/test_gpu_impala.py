@@ -7,7 +7,10 @@ test_impala_stages_match_a_model_of_each_kernel_on_its_own_operands then takes t
 every convolution between them against a float64 model of that one stage on the run's own input (tests/helpers/impala_stages.py,
 tests/helpers/bf16_model.py), in bf16x3 and in single-pass bf16, on a non-square observation, and on flat frames whose pool
 windows are ties.  The pool's tie rule -- the first maximum in row-major window order -- is pinned there (winners compared
-exactly) and on the CPU in tests/test_impala_stages_host.py.
+exactly) and on the CPU in tests/test_impala_stages_host.py.  On the backward side that test holds the pool backward, dzs and the
+Conv_0 leaves; what lies between the top of a Stack and its pool -- the masked S8 conversion, the SAME-padded 3x3 data gradients, the
+LayerNorm backward and its in-place accumulation, the leaves of Conv_1 .. Conv_4 and of the block LayerNorms -- and the torso's
+BatchNorm sites are held the same way in tests/test_gpu_impala_backward.py, in bf16x3 and in single-pass bf16.
 
 Mutations (arithmetic only, applied to a scratch copy, one run of the stage test each; none is committed) and what fails:
   * imp_pool_fwd_kernel `vv[e] > best[e]` -> `>=` (last maximum): flat-frames only -- "imp/s0/argmax: 21778 winners differ from
