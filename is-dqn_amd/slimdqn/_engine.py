@@ -716,6 +716,11 @@ class QNetEngine:
     decay_kinds = 0     # bit k: tensors of TensorInfo.kind k decay
     _captured = None    # weak set of the captured updates whose batches this engine made (slimdqn/_graph.py)
 
+    def _drop_captured(self) -> None:
+        """Destroy every captured update of this engine: what its batches carry changed, so each captures again at its next run."""
+        for g in list(self._captured or ()):
+            g.destroy()
+
     def set_weight_decay(self, weight_decay: float, all_kinds: bool = False) -> None:
         """AdamW (Loshchilov & Hutter 2019; optax.adamw, torch.optim.AdamW) for the following learn steps of this engine: every element
         of a decaying tensor also loses ``learning_rate * weight_decay`` times its value before the step (include/isdqn_hip.h,
@@ -727,8 +732,7 @@ class QNetEngine:
         wd = _optimizer.check_weight_decay(weight_decay, noisy=self.noisy)
         self.weight_decay = wd
         self.decay_kinds = _optimizer.decay_kinds(all_kinds) if wd > 0.0 else 0
-        for g in list(self._captured or ()):
-            g.destroy()
+        self._drop_captured()
 
     cql_alpha = 0.0  # weight of the conservative term of the following loss / gradient / learn calls (set_conservative); 0: none
 
@@ -744,8 +748,7 @@ class QNetEngine:
         if alpha > 0.0 and self.mix_alpha is not None:  # (the library refuses the two together at every call: refuse them here)
             raise ValueError(_mixture.REM_CQL_REFUSED)
         self.cql_alpha = alpha
-        for g in list(self._captured or ()):
-            g.destroy()
+        self._drop_captured()
 
     mix_alpha = None  # float32 [n_heads]: the mixture weights of the following loss / gradient / learn calls (set_mixture); None: none
     mix_count = None  # int64 [1]: draws so far (selects the next draw; mixture_draw advances it on the device)
@@ -763,8 +766,7 @@ class QNetEngine:
         with torch.cuda.device(self.device):
             self.mix_alpha = torch.full((self.n_heads,), 1.0 / self.n_heads, dtype=torch.float32, device=self.device)
             self.mix_count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        for g in list(self._captured or ()):
-            g.destroy()
+        self._drop_captured()
 
     def mixture_draw(self) -> None:
         """The next mixture weights into ``mix_alpha`` on the current stream; the device count advances by one (nothing is read back)."""
@@ -989,10 +991,8 @@ class QNetEngine:
         self.prune_scratch = torch.zeros(max(int(scratch.value) // 4, 1), dtype=torch.int32, device=self.device)
         return [i[3] for i in self.prune_infos]
 
-    def _prune_target(self, params):
-        """(buffer, workspace pointer or 0) of a pruning call: the engine's own parameters go with their mirror."""
-        if self.prune_mask is None:
-            raise ValueError(_sparsity.PRUNE_NOT_SET_REFUSED)
+    def _layout_buffer(self, params):
+        """(buffer, workspace pointer or 0) of a pruning or projection call: the engine's own parameters go with their mirror."""
         own = params is None
         p = self.params if own else params
         assert p.dtype == torch.float32 and p.numel() == self.n_param_floats and p.is_contiguous() and p.device == self.params.device
@@ -1004,7 +1004,9 @@ class QNetEngine:
         and the apply launch stores the weight mirror of what it wrote -- a mirror that was current stays current, one that was not stays
         marked so.  Another buffer of the layout: the magnitudes are read there, that buffer alone is written, master only -- handing in
         the engine's own ``params`` that way marks the mirror stale.  Stream-ordered, no host synchronisation."""
-        p, ws = self._prune_target(params)
+        if self.prune_mask is None:
+            raise ValueError(_sparsity.PRUNE_NOT_SET_REFUSED)
+        p, ws = self._layout_buffer(params)
         if len(counts) != len(self.prune_infos) or any(int(k) != k or not 0 <= int(k) <= i[3] for k, i in zip(counts, self.prune_infos)):
             raise ValueError(_sparsity.PRUNE_COUNTS_REFUSED)
         k = (ctypes.c_int32 * len(self.prune_infos))(*[int(c) for c in counts])
@@ -1017,7 +1019,9 @@ class QNetEngine:
     def prune_apply(self, params=None) -> None:
         """+0.0 wherever the mask says pruned (include/isdqn_hip.h, isdqn_net_prune_apply): one stream-ordered launch, the node behind
         every gradient step.  ``params`` as in ``prune_update``."""
-        p, ws = self._prune_target(params)
+        if self.prune_mask is None:
+            raise ValueError(_sparsity.PRUNE_NOT_SET_REFUSED)
+        p, ws = self._layout_buffer(params)
         _hip.check(self.lib.isdqn_net_prune_apply(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.prune_mask), ws, _hip.stream_ptr(self.device)),
                    "isdqn_net_prune_apply")
         if params is not None:
@@ -1054,19 +1058,12 @@ class QNetEngine:
         self.project_target[: n.value].copy_(torch.tensor(target_norms, dtype=torch.float64))
         return list(target_norms)
 
-    def _project_buffer(self, params):
-        """(buffer, workspace pointer or 0) of a projection call: the engine's own parameters go with their mirror."""
-        if self.project_target is None:
-            raise ValueError(_projection.NAP_NOT_SET_REFUSED)
-        own = params is None
-        p = self.params if own else params
-        assert p.dtype == torch.float32 and p.numel() == self.n_param_floats and p.is_contiguous() and p.device == self.params.device
-        return p, (_hip.ptr(self.workspace) if own else 0)
-
     def project_norms(self, params=None) -> list:
         """The norm of every projected tensor of ``params`` (None: the engine's own) as the device measures it
         (include/isdqn_hip.h, isdqn_net_project_norms): two launches and one host read.  Writes ``project_norms_out`` and no parameter."""
-        p, _ = self._project_buffer(params)
+        if self.project_target is None:
+            raise ValueError(_projection.NAP_NOT_SET_REFUSED)
+        p, _ = self._layout_buffer(params)
         _hip.check(self.lib.isdqn_net_project_norms(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.project_norms_out),
                                                     _hip.ptr(self.project_scratch), _hip.stream_ptr(self.device)), "isdqn_net_project_norms")
         return [float(x) for x in self.project_norms_out[: len(self.project_infos)].cpu()]
@@ -1077,7 +1074,9 @@ class QNetEngine:
         what it measured and applied.  ``params`` None: the engine's own parameters, and the weight mirror is stored with them -- a
         mirror that was current stays current, one that was not stays marked so.  Another buffer of the layout: that buffer alone,
         master only -- handing in the engine's own ``params`` that way marks the mirror stale."""
-        p, ws = self._project_buffer(params)
+        if self.project_target is None:
+            raise ValueError(_projection.NAP_NOT_SET_REFUSED)
+        p, ws = self._layout_buffer(params)
         _hip.check(self.lib.isdqn_net_project_apply(ctypes.byref(self.cfg), _hip.ptr(p), _hip.ptr(self.project_target),
                                                     _hip.ptr(self.project_norms_out), _hip.ptr(self.project_scales),
                                                     _hip.ptr(self.project_scratch), ws, _hip.stream_ptr(self.device)), "isdqn_net_project_apply")

@@ -3,6 +3,7 @@ conversion, single-observation forward.  No arithmetic of the hot path lives her
 from __future__ import annotations
 
 import dataclasses
+import typing
 
 import numpy as np
 import torch
@@ -137,6 +138,14 @@ def augment_seed(seed: int) -> int:
     return int.from_bytes(state.tobytes(), "little")
 
 
+class Stage(typing.NamedTuple):
+    """One launch behind the learn call of a gradient step ("The step as a schedule")."""
+
+    tag: tuple            # what the captured step's key says of it
+    run: typing.Callable  # takes no arguments, enqueues on the current stream
+    state: tuple = ()     # the device tensors it writes besides the engine's own
+
+
 class EngineAgent:
     """Common state: ``n_heads`` network heads of ``n_actions`` outputs each on the HIP engine."""
 
@@ -231,11 +240,57 @@ class EngineAgent:
 
     def _run_graph(self, g) -> None:
         """One replay of the captured update ``g``: the betas and the (horizon, discount) pairs of its S steps are its input."""
-        if self._prune is not None:
-            self._prune_t += g.S
+        self._stepped(g.S)
         betas = self._next_betas(g.S)
         pairs = self._next_horizons(g.S, g.rb)
         g.run(betas) if pairs is None else g.run(betas, horizons=pairs[0], gammas=pairs[1])
+
+    # ------------------------------------------------------------------ what stands behind the learn call (DESIGN.md section 6)
+    def _after_learn(self, eng) -> list:
+        """The Stages behind the learn call of a gradient step on ``eng``, in order: stated once per agent, read by the eager and by
+        the captured step.  Here the two every agent shares, the prune apply (only while ``prune_active``), then the projection
+        (only with ``weight_projection``); iSDQN and DQN place their own around them."""
+        prune = [Stage(("prune",), eng.prune_apply)] if self.prune_active else []
+        return prune + ([Stage(("nap",), eng.project_weights)] if self.weight_projection else [])
+
+    def _step_engine(self, replay_buffer):
+        """The engine of a gradient step on ``replay_buffer``'s batches."""
+        return self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
+
+    def _captured_step(self, eng, learn=None, key=(), state=()) -> dict:
+        """What _graphed_update is handed: ``learn`` on a C batch (None: the engine's learn_on_batch) with the stages behind it on the
+        same stream -- further nodes of the captured step, no new branch --, the agent's base ``key`` with the stages' tags behind it
+        as one flat tuple (None when empty), and the tensors the stages write in front of the base ``state``.  An agent with nothing
+        on hands over no learn call, no state and no key: the captured step is the engine's own."""
+        stages = self._after_learn(eng)
+        if learn is None and not stages:
+            return {}
+        first = eng.learn_on_batch if learn is None else learn
+
+        def step(cb):
+            first(cb)
+            for s in stages:
+                s.run()
+
+        key = tuple(key) + tuple(x for s in stages for x in s.tag)
+        return dict(learn=step, key=key or None, state=[t for s in stages for t in s.state] + list(state))
+
+    def _own_step(self, replay_buffer) -> dict:
+        """``_captured_step`` of an agent whose learn call is the engine's own (iSDQN, TFDQN); the engine is asked for only where a
+        stage needs it, else behind the guards of _graphed_update as ever."""
+        return self._captured_step(self._step_engine(replay_buffer)) if self._after_learn(self._engine) else {}
+
+    def _eager_after_learn(self) -> None:
+        """Behind the agent's learn_on_batch in an eager gradient step: the same stages, in the same order."""
+        self._stepped(1)
+        for s in self._after_learn(self._engine):
+            s.run()
+
+    def _stepped(self, n: int) -> None:
+        """``n`` gradient steps were taken, eager or replayed: the pruning schedule's clock runs while the option is on, whether or not
+        anything is pruned yet."""
+        if self._prune is not None:
+            self._prune_t += n
 
     def _horizon_logs(self) -> dict:
         """The update horizon and the discount of the last gradient step, logged where the loss is; {} when the schedule is off."""
@@ -760,8 +815,8 @@ class EngineAgent:
         slimdqn/_sparsity.py).  Every conv and Dense kernel but the last Dense's is pruned by magnitude towards ``sparsity`` on the
         cubic schedule between gradient steps ``start`` and ``end``; the mask is chosen on the device at target updates whose step is
         a multiple of ``period`` (``prune_target_update``), and once anything is pruned every gradient step is followed by the apply
-        launch -- right behind the learn call in the eager step, one more node on the same stream in the captured one (the graph's
-        key says whether it is there: until the schedule starts the captured step is the one without the option).  Gradients and
+        launch: the first shared stage of ``_after_learn`` (until the schedule starts the step, eager or captured,
+        is the one without the option).  Gradients and
         Adam moments stay dense.  A target buffer (DQN) is masked at every mask update, so its zeros survive the hard copy and the
         EMA.  Refused with noisy layers, batch_norm and the impala torso, before anything is built."""
         if _sparsity.check_sparsity(sparsity) == 0.0:
@@ -775,31 +830,6 @@ class EngineAgent:
     def prune_active(self) -> bool:
         """Whether a gradient step is followed by the apply launch: the option is on and the last mask update pruned something."""
         return self._prune is not None and self._prune.active
-
-    def _prune_learn(self, eng, learn=None):
-        """``learn`` (default: the engine's learn_on_batch) with the apply launch behind it on the same stream."""
-        learn = eng.learn_on_batch if learn is None else learn
-
-        def pruned(cb):
-            learn(cb)
-            eng.prune_apply()
-
-        return pruned
-
-    def _prune_step(self, kw: dict, eng) -> dict:
-        """What _graphed_update is handed (``learn`` / ``key`` / ``state``; {}: the engine's own learn call) with the apply node behind
-        the learn call and a key that says so.  Unchanged while nothing is pruned."""
-        if not self.prune_active:
-            return kw
-        return dict(kw, learn=self._prune_learn(eng, kw.get("learn")), key=(kw.get("key"), "prune"))
-
-    def _prune_eager(self, eng) -> None:
-        """Behind the learn call of an eager gradient step."""
-        if self._prune is None:
-            return
-        self._prune_t += 1
-        if self._prune.active:
-            eng.prune_apply()
 
     def prune_target_update(self, step: int, wrote: bool = False) -> dict:
         """Behind the -redo and -reset hooks of the target update at ``step``: a multiple of ``prune_period`` updates the mask with the
@@ -829,9 +859,8 @@ class EngineAgent:
     def _init_projection(self, on, *, layer_norm, noisy, batch_norm, architecture_type) -> None:
         """Normalize-and-Project (Lyle et al. 2024; include/isdqn_hip.h, isdqn_net_project_*; the rules: slimdqn/_projection.py).  Every
         conv and Dense kernel but the last Dense's is scaled back to the Frobenius norm it had at initialisation after every gradient
-        step -- right behind the learn call (and behind pruning's apply launch where that is active, so the norm is the masked
-        tensor's) in the eager step, two more launches on the same stream in the captured one, whose key says so.  Biases and LayerNorm
-        vectors are left alone.  The target norms are measured on the first engine's initial parameters and never again: not at a
+        step: the second shared stage of ``_after_learn``, behind pruning's apply launch where that is active,
+        so the norm is the masked tensor's.  Biases and LayerNorm vectors are left alone.  The target norms are measured on the first engine's initial parameters and never again: not at a
         reset, whose fresh draw is simply projected at the next step, not at ReDo, not when an engine for another batch size is built.
         A DQN target is never projected itself: a hard copy already is, an EMA is a convex combination of projected parameters.
         Needs ``layer_norm``; refused with noisy layers, batch_norm and the impala torso, before anything is built."""
@@ -840,33 +869,6 @@ class EngineAgent:
         _projection.check_network(layer_norm=bool(layer_norm), noisy=bool(noisy), batch_norm=bool(batch_norm),
                                   architecture_type=architecture_type)
         self.weight_projection = True
-
-    @property
-    def _nap_first(self) -> bool:
-        """Whether the projection comes directly behind the learn call: the option is on and no prune apply stands in between."""
-        return self.weight_projection and not self.prune_active
-
-    def _nap_learn(self, eng, learn=None):
-        """``learn`` (default: the engine's learn_on_batch) with the projection behind it on the same stream."""
-        learn = eng.learn_on_batch if learn is None else learn
-
-        def projected(cb):
-            learn(cb)
-            eng.project_weights()
-
-        return projected
-
-    def _nap_step(self, kw: dict, eng) -> dict:
-        """What _graphed_update is handed (``learn`` / ``key`` / ``state``; {}: the engine's own learn call) with the projection behind
-        the learn call and a key that says so.  Unchanged while the option is off."""
-        if not self.weight_projection:
-            return kw
-        return dict(kw, learn=self._nap_learn(eng, kw.get("learn")), key=(kw.get("key"), "nap"))
-
-    def _nap_eager(self, eng) -> None:
-        """Behind the learn call (and the prune apply) of an eager gradient step."""
-        if self.weight_projection:
-            eng.project_weights()
 
     def nap_target_update(self, step: int) -> dict:
         """The logs of the target update at ``step``, where the losses are read anyway: the smallest and the largest scale the last

@@ -50,14 +50,7 @@ class AnalysisDQN(iSDQN):
             batch_samples_eval = self._sample_eval(replay_buffer)
             (self.params, self.optimizer_state, losses, churn_train, churn_eval, cos_is_tb, cos_tf_tb) = self.learn_on_batch(
                 self.params, self.target_params, self.optimizer_state, batch_samples, batch_samples_eval)
-            nap_first = self._nap_first  # (the projection in front of the soft shift, or behind an active prune apply: iSDQN's eager step)
-            if nap_first:
-                self._nap_eager(self._engine)
-            if self.soft_shift_tau > 0.0:  # (behind the step and its diagnostics, as in iSDQN's eager step)
-                self._engine.soft_shift(self.soft_shift_tau)
-            self._prune_eager(self._engine)
-            if not nap_first:
-                self._nap_eager(self._engine)
+            self._eager_after_learn()  # (behind the step and its diagnostics: iSDQN's stages)
             # (the step accumulates `losses` on the device as iSDQN does; the diagnostics are host sums like the reference's)
             self.cumulated_target_churns_train += churn_train
             self.cumulated_target_churns_eval += churn_eval

@@ -18,8 +18,7 @@ class AnalysisTFDQN(TFDQN):
             batch_samples_eval = self._sample_eval(replay_buffer)
             self.params, self.optimizer_state, _, churn_train, churn_eval = self.learn_on_batch(
                 self.params, self.optimizer_state, batch_samples, batch_samples_eval)
-            self._prune_eager(self._engine)
-            self._nap_eager(self._engine)
+            self._eager_after_learn()
             self.cumulated_target_churn_train += churn_train
             self.cumulated_target_churn_eval += churn_eval
 

@@ -12,7 +12,7 @@ import torch
 
 from slimdqn import _mixture
 from slimdqn._engine import NetOptions, check_munchausen
-from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau, check_soft_shift_tau
+from slimdqn.networks._agent import DeviceParams, EngineAgent, Stage, check_ema_tau, check_soft_shift_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -67,9 +67,8 @@ class DQN(EngineAgent):
         """The option keywords from ``n_bins`` to ``noisy_sigma0``: NetOptions (slimdqn/_engine.py); ``augment_pad``:
         EngineAgent._init_engine_agent.  Particular to DQN:
         ``ema_tau`` > 0: EMA (Polyak) target network (include/isdqn_hip.h, isdqn_net_ema; SR-SPR, BBF) -- every gradient step is
-        followed by target <- (1 - tau) * target + tau * online on the device (noisy: ``target_sigma`` likewise), in the eager step
-        and inside the captured one, on the step's own stream; ``update_target_params`` then copies nothing and only reports its
-        logs.  0 keeps the hard copy every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
+        followed by target <- (1 - tau) * target + tau * online on the device (noisy: ``target_sigma`` likewise), the last stage of
+        ``_after_learn``; ``update_target_params`` then copies nothing and only reports its logs.  0 keeps the hard copy every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
         ``noisy``: the target network has a sigma of its own (copied with the parameters at every target update) and, in every learn
         step, a draw of its own (stream 1), as in Fortunato's DQN.
         ``double_q``: the online parameters pick the next action, the target parameters value it: one more forward per step.
@@ -80,13 +79,13 @@ class DQN(EngineAgent):
         ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent) on the online parameters' state rows.
         ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head; the soft target here is ``ema_tau``.
         ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning) of
-        the online parameters; the target buffer is masked at every mask update, and the apply launch of a gradient step comes in front
-        of the EMA, so the target's zeros stay zero under the hard copy and under ``ema_tau``.
-        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection) of the online parameters, behind the prune apply and
-        in front of the EMA; the target buffer is never projected itself.
+        the online parameters; the target buffer is masked at every mask update, so its zeros stay zero under the hard copy and under
+        ``ema_tau``, whose stage stands behind the apply launch (``_after_learn``).
+        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection) of the online parameters; the target buffer is
+        never projected itself.
         ``rem_heads`` = H > 0: REM, the random ensemble mixture (Agarwal et al. 2020; include/isdqn_hip.h, isdqn_batch_mixture) -- the
-        network has H heads on one torso, every gradient step (eager and captured: one more node in front of the learn call, on the
-        step's stream) draws a new convex combination of the heads on the device and regresses the mixture on the target network's
+        network has H heads on one torso, every gradient step (the draw is part of the learn call: DESIGN.md section 6) draws a new
+        convex combination of the heads on the device and regresses the mixture on the target network's
         mixture; acting, ``q_values``, ``loss`` and ``compute_target`` use the head average.  0 is off: the agent built without the
         argument.  Refused with ``noisy``, ``n_bins``, ``n_quantiles``, ``munchausen_tau`` and ``cql_alpha`` (slimdqn/_mixture.py)."""
         options = NetOptions.pick(locals())
@@ -118,57 +117,34 @@ class DQN(EngineAgent):
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
             target = self._target_tensor(self.target_params)
-            eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
-            step_learn = lambda cb: eng.learn_on_batch_target(cb, target, **self._target_sigma_kw())
-            if self.rem_heads:  # (the step's draw: one more node in front of the learn call; the key below says it is there)
-                step_learn = self._rem_learn(eng, step_learn)
-            # (what the draw writes is state of the step: a capture's warm-up must not advance the count)
-            rem_state = [eng.mix_count, eng.mix_alpha] if self.rem_heads else []
-            pruned = self.prune_active  # (the apply launch right behind the learn call, in front of the EMA; the key says it is there)
-            if pruned:
-                step_learn = self._prune_learn(eng, step_learn)
-            nap = self.weight_projection  # (the projection behind the prune apply, in front of the EMA: the target averages projected
-            if nap:                       # parameters and is never projected itself; the key says it is there)
-                step_learn = self._nap_learn(eng, step_learn)
+            eng, rem = self._step_engine(replay_buffer), bool(self.rem_heads)
 
-            def tagged(key):
-                key = (key, "prune") if pruned else key
-                return (key, "nap") if nap else key
+            def learn(cb):  # (the mixture draw is part of the learn call: one more node in front of it, which the key names)
+                if rem:
+                    eng.mixture_draw()
+                eng.learn_on_batch_target(cb, target, **self._target_sigma_kw())
 
-            if self.ema_tau > 0.0:
-                # the learn call and the EMA of the target behind it, enqueued on one stream: the captured step gets no new branch.
-                # (the target buffers are state of the step now: a capture's warm-up must not move them)
-                def learn(cb):
-                    step_learn(cb)
-                    self._ema_target(eng, target)
-
-                key = (target.data_ptr(), self.ema_tau) + (("rem",) if self.rem_heads else ())
-                g = self._graphed_update(replay_buffer, learn=learn, key=tagged(key),
-                                         state=[target] + ([self.target_sigma] if self.noisy else []) + rem_state)
-            else:
-                key = (target.data_ptr(), "rem") if self.rem_heads else target.data_ptr()
-                g = self._graphed_update(replay_buffer, learn=step_learn, key=tagged(key), state=rem_state)
+            # (what the draw writes is state of the step, like the EMA's target buffers: a capture's warm-up must not move either)
+            g = self._graphed_update(replay_buffer, **self._captured_step(
+                eng, learn, key=(target.data_ptr(), self.ema_tau) + (("rem",) if rem else ()), state=[eng.mix_count, eng.mix_alpha] if rem else []))
             if g is not None:  # (captured against the target BUFFER: update_target_params refreshes it in place, nothing is captured again)
                 self._run_graph(g)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.target_params, self.optimizer_state, batch_samples)
-            self._prune_eager(self._engine)
-            self._nap_eager(self._engine)
-            if self.ema_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
-                self._ema_target(self._engine, target)
+            self._eager_after_learn()  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
             if getattr(self, "priority_writeback", False) and hasattr(replay_buffer, "update_device"):  # (as the captured step does)
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_loss += loss` (dqn.py:47) happens on the device inside the step
 
-    @staticmethod
-    def _rem_learn(eng, learn):
-        """``learn`` with the step's mixture draw in front of it on the same stream."""
-        def drawn(cb):
-            eng.mixture_draw()
-            return learn(cb)
-
-        return drawn
+    def _after_learn(self, eng) -> list:
+        """learn . prune apply . projection . EMA of the target: DESIGN.md section 6.  The target averages masked and projected
+        parameters and is never projected itself.  ``ema_tau`` stands in the base key of the step, so the stage has no tag."""
+        stages = super()._after_learn(eng)
+        if self.ema_tau > 0.0:
+            target = self._target_tensor(self.target_params)
+            stages.append(Stage((), lambda: self._ema_target(eng, target), (target,) + ((self.target_sigma,) if self.noisy else ())))
+        return stages
 
     def _ema_target(self, eng, target: torch.Tensor) -> None:
         """target <- (1 - ema_tau) * target + ema_tau * online behind a gradient step (noisy: the target's sigma likewise)."""

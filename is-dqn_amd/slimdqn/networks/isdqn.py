@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from slimdqn._engine import NetOptions
-from slimdqn.networks._agent import DeviceParams, EngineAgent, check_ema_tau, check_soft_shift_tau
+from slimdqn.networks._agent import DeviceParams, EngineAgent, Stage, check_ema_tau, check_soft_shift_tau
 from slimdqn.networks.architectures.dqn import DQNNet
 
 
@@ -79,13 +79,12 @@ class iSDQN(EngineAgent):
         ``ema_tau`` > 0 is refused (EMA_REFUSED): the target is head 0 of the online parameters.  ``weight_decay`` /
         ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term (EngineAgent._init_engine_agent).
         ``soft_shift_tau`` > 0: the soft head shift (include/isdqn_hip.h, isdqn_net_soft_shift) -- every gradient step is followed by
-        head k <- (1 - tau) * head k + tau * head k+1 on the device (noisy: sigma likewise), in the eager step and inside the captured
-        one, on the step's own stream; ``update_target_params`` then shifts nothing and only reports its logs.  0 keeps the hard shift
+        head k <- (1 - tau) * head k + tau * head k+1 on the device (noisy: sigma likewise), a stage of ``_after_learn``;
+        ``update_target_params`` then shifts nothing and only reports its logs.  0 keeps the hard shift
         every ``target_update_frequency`` steps.  Outside [0, 1]: ValueError.
-        ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning);
-        the apply launch comes behind the soft shift where both are on.
-        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection): in front of the soft shift, or -- where pruning is
-        active -- directly behind its apply launch (the soft shift writes the last Dense alone, which neither of the two touches)."""
+        ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning).
+        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection).  Where the three stand behind the learn call:
+        ``_after_learn`` below and DESIGN.md section 6."""
         options = NetOptions.pick(locals())
         check_ema_tau(ema_tau)
         self.soft_shift_tau = check_soft_shift_tau(soft_shift_tau, supported=True)
@@ -123,7 +122,7 @@ class iSDQN(EngineAgent):
             steps = live.S
         else:
             steps = 1 if settled else n_steps
-        g = self._graphed_update(replay_buffer, steps=steps, **self._soft_shift_step(replay_buffer))
+        g = self._graphed_update(replay_buffer, steps=steps, **self._own_step(replay_buffer))
         if g is None:
             for _ in range(n_steps):
                 self.update_online_params(0, replay_buffer)
@@ -137,45 +136,24 @@ class iSDQN(EngineAgent):
             if live is not None and live.S > 1 and live.rb is replay_buffer:  # learn_steps' capture is the live graph: eager step
                 g = None
             else:
-                g = self._graphed_update(replay_buffer, **self._soft_shift_step(replay_buffer))
+                g = self._graphed_update(replay_buffer, **self._own_step(replay_buffer))
             if g is not None:
                 self._run_graph(g)  # same draws, same kernels, same bits as the eager branch below (tests/test_gpu_graphed_update.py)
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
-            nap_first = self._nap_first
-            if nap_first:
-                self._nap_eager(self._engine)
-            if self.soft_shift_tau > 0.0:  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
-                self._engine.soft_shift(self.soft_shift_tau)
-            self._prune_eager(self._engine)
-            if not nap_first:
-                self._nap_eager(self._engine)
+            self._eager_after_learn()  # (behind the step, not inside learn_on_batch: that stays a function of what it is given)
             if self.priority_writeback and hasattr(replay_buffer, "update_device"):
                 replay_buffer.update_device(batch_samples, self._engine.priorities)
             # `cumulated_losses += losses` (isdqn.py:62) happens on the device inside the step
 
-    def _soft_shift_step(self, replay_buffer) -> dict:
-        """What _graphed_update is handed under ``soft_shift_tau`` > 0: the learn call and the soft shift behind it, enqueued on one
-        stream -- the captured step gets one more node and no new branch -- and a key that holds the tau.  {} without.  With pruning
-        active the apply launch follows as one more node (EngineAgent._prune_step).  With ``weight_projection`` the projection comes
-        in front of the soft shift, or directly behind the prune apply where that is active (EngineAgent._nap_step)."""
-        if not (self.soft_shift_tau > 0.0 or self.prune_active or self.weight_projection):
-            return {}
-        eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
-        nap_first = self._nap_first
-        kw = self._nap_step({}, eng) if nap_first else {}
-        if self.soft_shift_tau > 0.0:
-            tau = self.soft_shift_tau
-            first = kw.get("learn", eng.learn_on_batch)
-
-            def learn(cb):
-                first(cb)
-                eng.soft_shift(tau)
-
-            kw = dict(learn=learn, key=(kw["key"], "soft_shift", tau) if kw else ("soft_shift", tau))
-        kw = self._prune_step(kw, eng)
-        return kw if nap_first else self._nap_step(kw, eng)
+    def _after_learn(self, eng) -> list:
+        """learn . projection (no pruning active) . soft shift . prune apply . projection (pruning active): DESIGN.md section 6.  The
+        soft shift writes the last Dense alone, which neither of the two others touches; the projection measures the masked tensor."""
+        tau = self.soft_shift_tau
+        shift = [Stage(("soft_shift", tau), lambda: eng.soft_shift(tau))] if tau > 0.0 else []
+        shared = super()._after_learn(eng)
+        return shift + shared if self.prune_active else shared + shift
 
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:

@@ -74,7 +74,8 @@ class TFDQN(EngineAgent):
         ``ema_tau`` > 0 is refused (EMA_REFUSED): there is no target network.  ``weight_decay`` / ``weight_decay_all``: AdamW; ``cql_alpha``: the conservative term
         (EngineAgent._init_engine_agent).  ``soft_shift_tau`` > 0 is refused (SOFT_SHIFT_REFUSED): one head, nothing to shift.
         ``prune_sparsity`` / ``prune_start`` / ``prune_end`` / ``prune_period``: gradual magnitude pruning (EngineAgent._init_pruning).
-        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection), behind the prune apply."""
+        ``weight_projection``: Normalize-and-Project (EngineAgent._init_projection).  The step is EngineAgent._after_learn's: learn,
+        prune apply, projection."""
         if double_q:
             raise ValueError(DOUBLE_Q_REFUSED)
         options = NetOptions.pick(locals())
@@ -95,18 +96,13 @@ class TFDQN(EngineAgent):
     # ------------------------------------------------------------------ tfdqn.py:38-54
     def update_online_params(self, step: int, replay_buffer):
         if step % self.data_to_update == 0:
-            kw = {}
-            if self.prune_active or self.weight_projection:  # (the apply launch, then the projection, as further nodes of the captured step)
-                eng = self._engine_for(replay_buffer._batch_size) if hasattr(replay_buffer, "_batch_size") else self._engine
-                kw = self._nap_step(self._prune_step({}, eng), eng)
-            g = self._graphed_update(replay_buffer, **kw)
+            g = self._graphed_update(replay_buffer, **self._own_step(replay_buffer))
             if g is not None:
                 self._run_graph(g)  # same draws, same kernels, same bits as the eager branch below
                 return
             batch_samples = self._sample(replay_buffer)
             self.params, self.optimizer_state, _ = self.learn_on_batch(self.params, self.optimizer_state, batch_samples)
-            self._prune_eager(self._engine)
-            self._nap_eager(self._engine)
+            self._eager_after_learn()
 
     def update_target_params(self, step: int):
         if step % self.target_update_frequency == 0:
