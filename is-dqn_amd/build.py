@@ -77,11 +77,11 @@ def build(force=False, verbose=True, variant=None, defines=(), extra_flags=()):
     return lib
 
 
-def emit_asm(force=False, verbose=False, sources=None):
+def emit_asm(force=False, verbose=False, sources=None, variant=None, defines=()):
     """Device-side assembly of every source of SOURCES + EXTRA_SOURCES (or of ``sources``) under the product flags (build/<name>.s), for
-    scripts/isa_lint.py."""
+    scripts/isa_lint.py.  `variant` / `defines`: of a development build, to build_<variant>/<name>.s (tests/test_store_policy_host.py)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objdir = os.path.join(HERE, "build")
+    objdir = os.path.join(HERE, "build" if not variant else "build_" + variant)
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in HEADERS]
     outs, procs = [], []
@@ -90,7 +90,7 @@ def emit_asm(force=False, verbose=False, sources=None):
         o = os.path.join(objdir, src.replace(".hip", ".s"))
         outs.append(o)
         if force or _stale(o, [s] + headers + [os.path.abspath(__file__)]):
-            cmd = [hipcc] + [f for f in FLAGS if f != "-fPIC"] + ["-S", "--cuda-device-only", "-w", s, "-o", o]
+            cmd = [hipcc] + [f for f in FLAGS if f != "-fPIC"] + ["-D" + d for d in defines] + ["-S", "--cuda-device-only", "-w", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((src, subprocess.Popen(cmd)))

@@ -651,6 +651,9 @@ __global__ __launch_bounds__(GEMM_THREADS * KG, (U8 && MT == 2 && PASSES == 2) ?
         }
         if (out_pix[nt] >= 0) {
             const int64_t pix = (int64_t)j * g.npix + out_pix[nt];
+            // the activations leave write-through (gemm_core.h): this image's rows are the buffer, the pixel's row the offset
+            const int row_off = out_pix[nt] * g.cout_p * 4;
+            const WriteThroughDst act_dst = write_through_dst(p.act + (int64_t)j * g.npix * g.cout_p, g.npix * g.cout_p * 4);
 #pragma unroll
             for (int mt = 0; mt < MTW; ++mt) {
                 int ch0 = (mt0 + mt) * 16 + grp * 4;
@@ -664,7 +667,7 @@ __global__ __launch_bounds__(GEMM_THREADS * KG, (U8 && MT == 2 && PASSES == 2) ?
                     ap[r] = (ch0 + r < g.cout) ? fmaxf(y, 0.f) : 0.f;
                     zp[r] = zv[nt][mt][r];
                 }
-                s8_store_quad_paired(p.act + pix * g.cout_p, ch0, a.x, a.y, a.z, a.w);  // activations: S8 (consumers stage by copy)
+                s8_store_quad_paired(act_dst, row_off, ch0, a.x, a.y, a.z, a.w);  // activations: S8 (consumers stage by copy)
                 if (j < p.z_img) *reinterpret_cast<float4*>(p.z + pix * g.cout_p + ch0) = zq;
             }
         }

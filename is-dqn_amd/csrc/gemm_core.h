@@ -30,6 +30,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int GEMM_BK = 32;
 constexpr int GEMM_THREADS = 256;
@@ -112,10 +113,11 @@ __device__ __forceinline__ void s8_store_quad(float* row, int c0, float v0, floa
 // every lane then stores 16 contiguous bytes and a wave store covers whole 32-byte groups, like the fp32 float4 store
 // did (two 8-byte stores per lane leave 16-byte holes in every store instruction: measured 2.5 % of the step).
 // Must be executed by both lanes of a pair (same pixel, channels c0 and c0 ^ 4).
-__device__ __forceinline__ void s8_store_quad_paired(float* row, int c0, float v0, float v1, float v2, float v3) {
+// `dst` is the store policy (PlainDst / WriteThroughDst below): `row_off` is the row's byte offset from its base.
+template <class Dst>
+__device__ __forceinline__ void s8_store_quad_paired(const Dst& dst, int row_off, int c0, float v0, float v1, float v2, float v3) {
     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     const float v[4] = {v0, v1, v2, v3};
     bf16x4 hi, lo;
 #pragma unroll
@@ -127,8 +129,8 @@ __device__ __forceinline__ void s8_store_quad_paired(float* row, int c0, float v
     const u32x2 h = __builtin_bit_cast(u32x2, hi), l = __builtin_bit_cast(u32x2, lo);
     const auto r0 = __builtin_amdgcn_permlane16_swap(h[0], l[0], false, false);
     const auto r1 = __builtin_amdgcn_permlane16_swap(h[1], l[1], false, false);
-    char* g = reinterpret_cast<char*>(row + (c0 & ~7)) + (c0 & 4) * 4;  // even row: the hi half, odd row: the lo half
-    *reinterpret_cast<u32x4*>(g) = u32x4{r0[0], r1[0], r0[1], r1[1]};
+    const int g = row_off + (c0 & ~7) * 4 + (c0 & 4) * 4;  // even row: the hi half, odd row: the lo half
+    dst.store(g, u32x4{r0[0], r1[0], r0[1], r1[1]});
 }
 
 // two adjacent elements c0, c0+1 (c0 even) / one element of the row starting at `row`
@@ -526,6 +528,37 @@ __device__ __forceinline__ void mask8(bool ok, float (&v)[8]) {  // for data tha
 // pre-activations made no difference (profiles/round4/cache_policy_ab.txt).
 __device__ __forceinline__ f32x4 nt_load4(const float* p) { return __builtin_nontemporal_load((const ISDQN_GLOBAL f32x4*)p); }
 __device__ __forceinline__ void nt_store4(float* p, const f32x4& v) { __builtin_nontemporal_store(v, (ISDQN_GLOBAL f32x4*)p); }
+// Write-through ("sc1") 16-byte stores for what a kernel leaves behind for LATER launches.  A plain (or nontemporal) store keeps its
+// line dirty in the writing XCD's L2 and the end of the kernel writes all of them back at once; an sc1 store goes through as it is
+// issued and leaves nothing for the end of the kernel.  It also drops the line from the writer's L2, so not for anything the same
+// launch reads again.  Visibility is what a kernel boundary gives either way.  Measured on the forward convolutions' activations
+// (docs/NOTEBOOK.md, 2026-10-21): 0.6 - 1.2 us per kernel where the whole grid is resident at once (B = 256, the step +1 %); where
+// the grid runs in several rounds (B = 1024) the kernels are 1 - 9 % SLOWER with it and the step loses 1 %; nothing for the
+// pre-activations, which no later forward kernel reads.
+// The destination is a buffer: a wave-uniform base (one image's rows of an output tensor: kernel argument + blockIdx arithmetic)
+// and a byte offset per lane; a store at or past `bytes` is dropped by the hardware.  The builtin is a store the compiler counts.
+// -DISDQN_PLAIN_STORES: the plain store at every use (tests/test_gpu_write_through_stores.py holds the two builds to the same bits).
+struct PlainDst {  // the store policy of everything else: plain 16-byte stores at base + offset
+    char* base;
+    __device__ __forceinline__ void store(int off, const u32x4& v) const { *reinterpret_cast<u32x4*>(base + off) = v; }
+    __device__ __forceinline__ void store(int off, const f32x4& v) const { *reinterpret_cast<f32x4*>(base + off) = v; }
+};
+__device__ __forceinline__ void s8_store_quad_paired(float* row, int c0, float v0, float v1, float v2, float v3) {
+    s8_store_quad_paired(PlainDst{reinterpret_cast<char*>(row)}, 0, c0, v0, v1, v2, v3);
+}
+#if defined(ISDQN_PLAIN_STORES)
+typedef PlainDst WriteThroughDst;
+__device__ __forceinline__ WriteThroughDst write_through_dst(float* base, int) { return WriteThroughDst{reinterpret_cast<char*>(base)}; }
+#else
+struct WriteThroughDst {
+    __amdgpu_buffer_rsrc_t rsrc;
+    __device__ __forceinline__ void store(int off, const u32x4& v) const { __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, /*aux: sc1*/ 16); }
+    __device__ __forceinline__ void store(int off, const f32x4& v) const { store(off, __builtin_bit_cast(u32x4, v)); }
+};
+__device__ __forceinline__ WriteThroughDst write_through_dst(float* base, int bytes) {
+    return WriteThroughDst{__builtin_amdgcn_make_buffer_rsrc(base, /*stride*/ 0, bytes, /*raw dwords, 32-bit data format*/ 0x00020000)};
+}
+#endif
 // optax.adam on one element (isdqn.py:46, 85-86; optax scale_by_adam + scale(-lr)):  m, v updated in place, returns the new parameter.
 // `inv_c1` / `inv_c2` = 1 / (1 - b^t), one IEEE division per thread; the square root and the reciprocal of (sqrt(v_hat) + eps) are the
 // hardware's 1-ulp v_sqrt_f32 / v_rcp_f32: the three IEEE divisions and the refined square root per element they replace were 66 vector
